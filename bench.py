@@ -30,8 +30,20 @@ the statistics all-gather + merge.  Rank 0 prints ONE JSON line.
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
 
 `value` is the DEFAULT product path at every N (one plain compute_bound per step, prep launch included); the loop inside
-`fixed_parameters()` (prep launch skipped on unchanged parameters) is the side leg legs.weak_prepared.  `roofline`,
-`cpu_baseline` and `parity` are in the line at every N (rank 0 times the CPU baseline, the other ranks wait).
+`fixed_parameters()` (prep launch skipped on unchanged parameters) is the side leg legs.weak_prepared.
+
+A plain run measures the headline only: set-up, spin-up and warm-up, the timed steps, then the line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, the ELBO of the last step).  `--full` adds everything else
+described above: the side and strong legs, `roofline` (from a separate kernel-timing loop), `saturated`, `second_order`,
+`vargrad` / `training_step`, and `cpu_baseline` / `parity` (rank 0 times the CPU baseline, the other ranks wait).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0's shard): DIR/losses.npy (float32),
+DIR/z.npy (float32) and DIR/stats.npy (float64; merged over the ranks when N > 1), non-finite entries set to 0 and recorded
+in DIR/<name>_nonfinite.npy (dump_outputs).  The seeds and parameters depend on the arguments only, so two builds can be
+compared output for output.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/
 """
 import argparse
 import json
@@ -253,6 +265,45 @@ def _strict(o):
     return o
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+NONFINITE_CODE = {"posinf": 1.0, "neginf": -1.0, "nan": 2.0}
+
+
+def finite_parts(a):
+    """-> (a with every non-finite entry set to 0, float32 code of the same shape: 0 finite, +1 +inf, -1 -inf, 2 NaN).
+    The two together hold all of `a`, and both are finite."""
+    code = np.zeros(a.shape, dtype=np.float32)
+    code[np.isposinf(a)] = NONFINITE_CODE["posinf"]
+    code[np.isneginf(a)] = NONFINITE_CODE["neginf"]
+    code[np.isnan(a)] = NONFINITE_CODE["nan"]
+    return np.where(code == 0, a, 0).astype(a.dtype), code
+
+
+def dump_outputs(directory, losses, z, stats, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays a caller of the timed forward receives, as DIR/<name>.npy (losses and z float32, stats
+    float64), each with its non-finite entries set to 0 and beside it DIR/<name>_nonfinite.npy (float32 code, see
+    finite_parts) saying where they were and what they held: particles that leave float32 range (+inf losses of the
+    untrained headline net) are outputs too, and every file stays finite.  When losses + z and their codes would exceed
+    `limit` bytes, a fixed seeded sample of particles (the same rows of all four, in ascending order) is written instead;
+    the sample depends on the particle count only."""
+    losses = np.ascontiguousarray(losses, dtype=np.float32)
+    z = np.ascontiguousarray(z, dtype=np.float32)
+    stats = np.ascontiguousarray(stats, dtype=np.float64)
+    n = losses.shape[0]
+    row_bytes = 2 * (losses.itemsize + z[:1].nbytes)                  # values + float32 codes
+    keep = max(min(n, (limit - stats.nbytes - 4 * stats.size) // row_bytes), 1)
+    if keep < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        losses, z = losses[rows], z[rows]
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in (("losses", losses), ("z", z), ("stats", stats)):
+        values, code = finite_parts(arr)
+        np.save(os.path.join(directory, name + ".npy"), values)
+        np.save(os.path.join(directory, name + "_nonfinite.npy"), code)
+
+
 class Leg:
     """One workload of the job: `n_global` particles of a synthetic configuration, sharded contiguously over the ranks
     (or `n_global` per rank when weak)."""
@@ -287,7 +338,7 @@ class Leg:
         return _lib.last_kernel_name()
 
 
-def time_leg(leg, steps, warmup, use_dist, device, world, sharded=True, spinup=0, pipelined=False):
+def time_leg(leg, steps, warmup, use_dist, device, world, sharded=True, spinup=0, pipelined=False, kernel_time=True):
     """W untimed + K timed forward steps of `leg` on this rank's shard: barrier + synchronize on both sides, MAX over ranks.
     (The untimed part ends with one rehearsal of the timed region's own shape — barrier, K steps, barrier — so that the timed
     region is not the process's first region of that shape: r04, 0.191 - 0.202 -> 0.183 - 0.186 ms per step over five interleaved
@@ -301,7 +352,8 @@ def time_leg(leg, steps, warmup, use_dist, device, world, sharded=True, spinup=0
     every step's all-gather and merge still run inside the timed region (the last one is drained before the closing barrier).
     The timed region contains NO measurement code: the per-launch HIP-event hook (cmcd_profile_enable) is off; the kernel's
     own duration (`kern_ms` / `launches`) comes from a SECOND, separate loop of the same forward calls behind the closing
-    barrier, with the hook on and no collective."""
+    barrier, with the hook on and no collective; kernel_time=False (a plain run) skips that loop and leaves both None.
+    `losses`, `z`, `stats` are what the last timed step returned (stats merged over the ranks when gathered)."""
     from cmcd_amd import _lib, parallel
     gathered = [torch.zeros(world * parallel.NSTATS, dtype=torch.float64, device=device) for _ in range(2)]
     pending = []
@@ -369,42 +421,49 @@ def time_leg(leg, steps, warmup, use_dist, device, world, sharded=True, spinup=0
     # over both loops, profiles/r05_c_kernel_stats_bench_forward_only.csv).  The kernel's duration does not depend on who
     # formed its tables; `value` / `ms_per_step` above stay the default path with the prep launch in every call.
     from cmcd_amd import mcdboundingmachine as _mcdbm
-    with _mcdbm.fixed_parameters():
-        leg.forward()
-        _lib.profile_enable(True)
-        for k in range(min(steps, 500)):      # the hook holds 512 event pairs
+    kern_ms, launches = None, None
+    if kernel_time:
+        with _mcdbm.fixed_parameters():
             leg.forward()
-        torch.cuda.synchronize()
-        kern_ms, launches = _lib.profile_collect()
-        _lib.profile_enable(False)
+            _lib.profile_enable(True)
+            for k in range(min(steps, 500)):      # the hook holds 512 event pairs
+                leg.forward()
+            torch.cuda.synchronize()
+            kern_ms, launches = _lib.profile_collect()
+            _lib.profile_enable(False)
     if gc_was:
         gc.enable()
     if use_dist and sharded:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return dict(elapsed=elapsed, kern_ms=kern_ms, launches=launches, losses=losses, stats=stats, kernel=_lib.last_kernel_name())
+    return dict(elapsed=elapsed, kern_ms=kern_ms, launches=launches, losses=losses, z=z, stats=stats,
+                kernel=_lib.last_kernel_name())
 
 
 def leg_report(leg, t, steps):
-    """The per-leg object of the JSON line."""
+    """The per-leg object of the JSON line (without the kernel figures when `t` has no kernel-timing loop)."""
     from cmcd_amd import parallel
     cfg = leg.b["cfg"]
     units = leg.n_global * leg.K
     f_alg, f_survey = flops_per_particle_step(cfg, leg.dim, leg.spec.width)
+    fin = parallel.finalize(t["stats"], leg.n_global)
+    var = float(fin["var"])
+    rep = {
+        "workload": leg.cfg_name, "scaling": "weak" if leg.weak else "strong", "global_particles": leg.n_global,
+        "particles_per_gpu": leg.n_local, "nbridges": leg.K, "value": units * steps / t["elapsed"],
+        "ms_per_step": t["elapsed"] / steps * 1e3, "kernel": t.get("kernel") or leg.kernel_name(),
+        "elbo": float(-fin["mean"]), "ln_z": float(fin["ln_z"]), "loss_var": var, "n_finite": float(fin["n_finite"]),
+    }
+    if t["launches"] is None:
+        return rep
     if t["launches"] == 0:
         kern_s = t["elapsed"] / steps
     else:
         kern_s = t["kern_ms"] / 1e3 / t["launches"]
-    fin = parallel.finalize(t["stats"], leg.n_global)
-    var = float(fin["var"])
-    return {
-        "workload": leg.cfg_name, "scaling": "weak" if leg.weak else "strong", "global_particles": leg.n_global,
-        "particles_per_gpu": leg.n_local, "nbridges": leg.K, "value": units * steps / t["elapsed"],
-        "ms_per_step": t["elapsed"] / steps * 1e3, "kernel": t.get("kernel") or leg.kernel_name(), "kernel_ms": kern_s * 1e3,
-        "kernel_frac_of_fp32_peak": leg.n_local * leg.K * f_alg / kern_s / 1e12 / PEAK_FP32_TFLOPS,
-        "elbo": float(-fin["mean"]), "ln_z": float(fin["ln_z"]), "loss_var": var, "n_finite": float(fin["n_finite"]),
-    }
+    rep["kernel_ms"] = kern_s * 1e3
+    rep["kernel_frac_of_fp32_peak"] = leg.n_local * leg.K * f_alg / kern_s / 1e12 / PEAK_FP32_TFLOPS
+    return rep
 
 
 def main():
@@ -420,6 +479,13 @@ def main():
                          "of a fresh box unsettled for a 20-step run (r02: 0.202 ms against 0.191 ms for 300 steps)")
     ap.add_argument("--config", default=None, help="name in cmcd_amd.synthetic.CONFIGS")
     ap.add_argument("--particles", type=int, default=None, help="override N per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: side and strong legs, roofline, saturated batch, "
+                         "2nd-order mode, VarGrad and training steps, CPU baseline and parity (--no-cpu-baseline, "
+                         "--forward-only, --no-legs, --cpu-particles and --saturated trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write losses / z / stats of the last timed step to DIR/<name>.npy (non-finite entries 0, recorded in "
+                         "DIR/<name>_nonfinite.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-step", action="store_true",
                     help="with --config: also time value-and-gradient of that configuration's own training loss (training_step)")
@@ -431,6 +497,8 @@ def main():
     ap.add_argument("--saturated", type=int, default=1 << 18,
                     help="also time a saturating batch of this many particles (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if os.environ.get("CMCD_BENCH_TRACE_AFTER"):     # diagnostics: dump every thread's stack if the run is still going then
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["CMCD_BENCH_TRACE_AFTER"]), exit=True)
@@ -502,28 +570,31 @@ def main():
     # HEADLINE = the default product path: every step is one plain compute_bound call (cmcd_bound_forward: prep launch +
     # trajectory kernel + statistics), what a training step or any caller without further statements pays.
     mcdbm.PREP_CACHE = False
-    tw = time_leg(weak, args.steps, args.warmup, use_dist, device, world, spinup=args.spinup)
+    tw = time_leg(weak, args.steps, args.warmup, use_dist, device, world, spinup=args.spinup, kernel_time=args.full)
     legs["weak"] = leg_report(weak, tw, args.steps)
-    # Side leg, at every N: the same loop inside `with mcdbm.fixed_parameters():` — an evaluation loop that STATES its
-    # parameters are unchanged (the shape of the reference's 30 loss_fn calls on one params_flat,
-    # /root/reference/src/opt.py:185-190), so all but the first call skip the prep launch (cmcd_bound_forward_prepared).
-    # Never the headline (r04 reported it as `value`; no default caller of this package takes that path).
-    calls0 = dict(mcdbm.PREP_CALLS)
-    mcdbm.PREP_CACHE = True
-    try:
-        tprep = time_leg(weak, args.steps, args.warmup, use_dist, device, world, spinup=min(args.spinup, 300))
-    finally:
-        mcdbm.PREP_CACHE = False
-    legs["weak_prepared"] = leg_report(weak, tprep, args.steps)
-    legs["weak_prepared"]["what"] = ("the headline loop inside fixed_parameters(): per-parameter tables of the first call reused, "
-                                     "prep launch skipped; results bit-identical (tests/test_gpu_fullsize.py)")
-    legs["weak_prepared"]["prepared_calls"] = mcdbm.PREP_CALLS["prepared"] - calls0["prepared"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tw["losses"].cpu().numpy(), tw["z"].cpu().numpy(), tw["stats"].cpu().numpy())
+    if args.full:
+        # Side leg, at every N: the same loop inside `with mcdbm.fixed_parameters():` — an evaluation loop that STATES its
+        # parameters are unchanged (the shape of the reference's 30 loss_fn calls on one params_flat, the reference's
+        # src/opt.py:185-190), so all but the first call skip the prep launch (cmcd_bound_forward_prepared).
+        # Never the headline (r04 reported it as `value`; no default caller of this package takes that path).
+        calls0 = dict(mcdbm.PREP_CALLS)
+        mcdbm.PREP_CACHE = True
+        try:
+            tprep = time_leg(weak, args.steps, args.warmup, use_dist, device, world, spinup=min(args.spinup, 300))
+        finally:
+            mcdbm.PREP_CACHE = False
+        legs["weak_prepared"] = leg_report(weak, tprep, args.steps)
+        legs["weak_prepared"]["what"] = ("the headline loop inside fixed_parameters(): per-parameter tables of the first call "
+                                         "reused, prep launch skipped; results bit-identical (tests/test_gpu_fullsize.py)")
+        legs["weak_prepared"]["prepared_calls"] = mcdbm.PREP_CALLS["prepared"] - calls0["prepared"]
     elapsed, kern_ms, launches, losses, stats = tw["elapsed"], tw["kern_ms"], tw["launches"], tw["losses"], tw["stats"]
     default_workload = name == synthetic.NORTH_STAR and not args.particles
 
     head_leg, head_t = weak, tw
     collective = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same batch with the statistics all-gather taken off the critical path (merged one step late)
         tp = time_leg(weak, args.steps, args.warmup, use_dist, device, world, spinup=0, pipelined=True)
         legs["weak_pipelined"] = leg_report(weak, tp, args.steps)
@@ -548,7 +619,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         collective = {"what": "all_gather_into_tensor of 5 float64 per rank + fixed-order merge kernel, stream-ordered",
                       "backend": dist.get_backend(), "us_per_call": float(tt.item()), "bytes_per_rank": 40}
-    if default_workload and not args.no_legs:
+    if args.full and default_workload and not args.no_legs:
         # strong scaling on the named batch (2000 / N per rank) and on configs[3] (16000 x 132-wide net split over the ranks)
         strong = Leg("strong_named", name, n_named, False, device, rank, world) if world > 1 else None
         cfg4 = Leg("strong_sharded_cfg4", CFG4, synthetic.CONFIGS[CFG4]["N"], False, device, rank, world)
@@ -625,14 +696,7 @@ def main():
     # and `strong_scaling` lifts the strong legs' same-job speed-ups to the top level.
     hl = legs["weak"]
     hcfg = head_leg.b["cfg"]
-    f_alg, f_survey = flops_per_particle_step(hcfg, head_leg.dim, head_leg.spec.width)
     value, n, K, dim = hl["value"], head_leg.n_local, head_leg.K, head_leg.dim
-    kern_s = hl["kernel_ms"] / 1e3
-    achieved = n * K * f_alg / kern_s / 1e12
-    launches = head_t["launches"] or args.steps
-    traffic, traffic_src = (None, None)
-    if head_leg is weak and default_workload:
-        traffic, traffic_src = stored_traffic("coop_kernel")
 
     result = {
         "metric": "bridge-steps*particles/sec", "value": value, "unit": "bridge-steps*particles/s",
@@ -644,20 +708,30 @@ def main():
                    "particles_per_gpu": n, "nbridges": K, "nn_arch": hcfg["nn_arch"], "dim": dim,
                    "global_particles": head_leg.n_global,
                    "parallelism": f"particles sharded x{world}, stats all-gather"},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_FP32_TFLOPS, "traffic": traffic, "traffic_unit": "bytes/launch (PMC)",
-                     "traffic_source": (f"profiles/{traffic_src}/summary.json (kernel sources {kernel_sources_sha()})"
-                                        if traffic is not None else "none for this kernel build"),
-                     "kernel": hl["kernel"], "kernel_ms": kern_s * 1e3, "launches": launches,
-                     "flop_per_particle_step": f_alg, "flop_per_particle_step_survey": f_survey,
-                     "achieved_survey_flops": n * K * f_survey / kern_s / 1e12,
-                     "state_bytes_gbs": n * K * (8 * dim + 8) / kern_s / 1e9,
-                     "issue_occupancy": stored_issue_occupancy("coop_kernel") if traffic is not None else None},
-        "elbo": hl["elbo"], "ln_z": hl["ln_z"], "n_finite": hl["n_finite"],
-        "legs": legs,
+        "kernel": hl["kernel"], "elbo": hl["elbo"], "ln_z": hl["ln_z"], "n_finite": hl["n_finite"],
+        "full": args.full,
     }
+    if args.full:
+        f_alg, f_survey = flops_per_particle_step(hcfg, head_leg.dim, head_leg.spec.width)
+        kern_s = hl["kernel_ms"] / 1e3
+        achieved = n * K * f_alg / kern_s / 1e12
+        launches = head_t["launches"] or args.steps
+        traffic, traffic_src = (None, None)
+        if head_leg is weak and default_workload:
+            traffic, traffic_src = stored_traffic("coop_kernel")
+        result["roofline"] = {
+            "bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved / PEAK_FP32_TFLOPS, "traffic": traffic, "traffic_unit": "bytes/launch (PMC)",
+            "traffic_source": (f"profiles/{traffic_src}/summary.json (kernel sources {kernel_sources_sha()})"
+                               if traffic is not None else "none for this kernel build"),
+            "kernel": hl["kernel"], "kernel_ms": kern_s * 1e3, "launches": launches,
+            "flop_per_particle_step": f_alg, "flop_per_particle_step_survey": f_survey,
+            "achieved_survey_flops": n * K * f_survey / kern_s / 1e12,
+            "state_bytes_gbs": n * K * (8 * dim + 8) / kern_s / 1e9,
+            "issue_occupancy": stored_issue_occupancy("coop_kernel") if traffic is not None else None}
+        result["legs"] = legs
     result["headline_leg"] = "weak"
-    if world > 1:
+    if world > 1 and args.full:
         result["collective"] = collective
         result["value_per_call"] = legs["weak"]["value"]
         result["value_pipelined"] = legs["weak_pipelined"]["value"]
@@ -681,9 +755,9 @@ def main():
     result["elbo_finite_particles"] = float(-lfin.double().mean()) if lfin.numel() else None
     n, K, dim = weak.n_local, weak.K, weak.dim
     f_alg, f_survey = flops_per_particle_step(cfg, dim, spec.width)
-    kern_s = legs["weak"]["kernel_ms"] / 1e3
+    kern_s = legs["weak"]["kernel_ms"] / 1e3 if args.full else None
 
-    if rank == 0 and args.saturated and world == 1:
+    if args.full and rank == 0 and args.saturated and world == 1:
         ns = args.saturated
         sseeds = torch.from_numpy(synthetic.throughput_seeds(ns, stream=7)).to(device)
         forward(sseeds)
@@ -700,7 +774,7 @@ def main():
                                "achieved": ns * K * f_alg / ks / 1e12,
                                "frac": ns * K * f_alg / ks / 1e12 / PEAK_FP32_TFLOPS}
 
-    if rank == 0 and world == 1 and default_workload and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and default_workload and not args.no_legs:
         # The reference's 2nd-order mode (config.boundmode = "MCD_CAIS_UHA_sn") on the SAME batch shape:
         # an extra measured line, not the headline (BASELINE.json's metric is quoted on MCD_CAIS_sn).  Two network
         # evaluations per bridge on concat(z, rho); unit = the headline's (particles x bridge steps per second).
@@ -739,7 +813,7 @@ def main():
             torch.cuda.synchronize()
             result["second_order"]["value_and_grad_ms"] = (time.perf_counter() - tg0) / 20 * 1e3
 
-    if cfg["model"] == "lgcp":
+    if args.full and cfg["model"] == "lgcp":
         IN = dim + cfg["emb_dim"]
         if n >= 225:     # cmcd_common.h: kLgcpWideMin
             # wide batches (cmcd_lgcp_wide.hip; the reference's evaluation batches): every particle shares ONE weight pass per
@@ -768,7 +842,7 @@ def main():
                                        "traffic_unit": "bytes/call (PMC)", "weight_bytes_per_call": wbytes,
                                        "kernel": legs["weak"]["kernel"]})
 
-    if rank == 0 and world == 1 and name == synthetic.NORTH_STAR and not args.forward_only:
+    if args.full and rank == 0 and world == 1 and name == synthetic.NORTH_STAR and not args.forward_only:
         # value-and-gradient of the VarGrad loss on the same batch (boundmode MCD_CAIS_var_sn, same net/target)
         try:
             bv = synthetic.build(name, device=device, boundmode="MCD_CAIS_var_sn", **over)
@@ -824,7 +898,7 @@ def main():
         except NotImplementedError as e:
             result["training_step"] = {"error": str(e)}
 
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # at EVERY N: rank 0 times the CPU baseline on its own shard's seeds (bounded sample, host cores of this box) and checks
         # its GPU losses against it; the other ranks wait at the barrier (process-group timeout raised in main's init)
         if rank == 0:

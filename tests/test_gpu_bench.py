@@ -22,8 +22,8 @@ def _line(out):
 
 
 def test_bench_single_gpu_line(hip_lib):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                          "--saturated", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                          "--no-cpu-baseline", "--saturated", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _line(out.stdout)
     for f in FIELDS:
@@ -52,10 +52,50 @@ def test_bench_single_gpu_line(hip_lib):
     assert so["value_and_grad_ms"] > so["ms_per_step"]
 
 
+PLAIN_FIELDS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config")
+FULL_ONLY = ("roofline", "legs", "saturated", "second_order", "vargrad", "training_step", "cpu_baseline", "parity")
+
+
+def test_bench_plain_line_is_the_headline_and_dumps_its_outputs(hip_lib, tmp_path):
+    """The plain command measures the headline only (no side legs, roofline or CPU baseline), times exactly --steps steps,
+    and --dump-outputs writes what the last timed step returned; a second run with the same arguments computes the same."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = _line(out.stdout)
+        for f in PLAIN_FIELDS:
+            assert f in r, f
+        assert not [f for f in FULL_ONLY if f in r] and r["full"] is False
+        assert r["steps"] == 7 and r["warmup"] == 2 and r["dtype"] == "f32" and r["higher_is_better"] is True
+        assert r["config"]["workload"] == "many_gmm_n2000_k256_dds"
+        assert r["value"] == pytest.approx(2000 * 256 * 1e3 / r["ms_per_step"])
+        files = {p.name for p in d.iterdir()}
+        assert files == {f"{name}{tail}.npy" for name in ("losses", "z", "stats") for tail in ("", "_nonfinite")}, files
+        got = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+        assert all(np.isfinite(a).all() for a in got.values())
+        losses, z, stats = got["losses"], got["z"], got["stats"]
+        assert losses.dtype == np.float32 and losses.shape == (2000,)
+        assert z.dtype == np.float32 and z.shape == (2000, r["config"]["dim"])
+        assert stats.dtype == np.float64 and stats.shape == (5,)
+        for name in ("losses", "z", "stats"):
+            code = got[name + "_nonfinite"]
+            assert code.dtype == np.float32 and code.shape == got[name].shape and np.all(got[name][code != 0] == 0)
+        # the untrained headline net sends some particles out of float32 range (loss +inf): recorded as codes, not dropped
+        assert int((got["losses_nonfinite"] == 0).sum()) == int(stats[0]) == int(r["n_finite"])
+        assert int(r["n_finite"]) < 2000 and np.all(got["losses_nonfinite"][got["losses_nonfinite"] != 0] == 1)
+        dumps.append(got)
+    for name in dumps[0]:
+        np.testing.assert_allclose(dumps[0][name], dumps[1][name], rtol=1e-6)
+
+
 def test_bench_two_ranks_share_the_gpu(hip_lib):
     env = dict(os.environ, CMCD_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--no-cpu-baseline", "--saturated", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
@@ -93,7 +133,7 @@ def test_bench_plain_command_starts_its_own_ranks(hip_lib):
     env = dict(os.environ, CMCD_BENCH_SHARED_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     r = _line(out.stdout)
@@ -126,7 +166,7 @@ def test_bench_single_rank_over_rccl(hip_lib):
     per-step all-gather of the statistics, the all-reduce of the timings and the barriers all go through the library the
     8-GPU run uses (two ranks cannot share one device under RCCL, so the two-rank test above runs over gloo)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29657", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--master-port", "29657", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
            "--no-cpu-baseline", "--saturated", "0", "--no-legs"]
     env = {k: v for k, v in os.environ.items() if k != "CMCD_BENCH_SHARED_GPU"}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -141,8 +181,8 @@ def test_bench_config_line_carries_its_training_step(hip_lib, cfg, loss):
     gradient of its own training loss on the same batch."""
     # (20 steps: a 3-step timed region of a 25 us call is mostly the closing synchronisation)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "20", "--warmup", "3",
-                          "--no-cpu-baseline", "--saturated", "0", "--no-legs", "--train-step"], capture_output=True, text=True,
-                         timeout=600, cwd=ROOT)
+                          "--full", "--no-cpu-baseline", "--saturated", "0", "--no-legs", "--train-step"], capture_output=True,
+                         text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _line(out.stdout)
     assert r["config"]["workload"] == cfg and r["value"] > 0

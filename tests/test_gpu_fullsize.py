@@ -418,8 +418,8 @@ def test_the_boundary_only_library_runs_the_path_and_the_bench(hip_lib):
     want = f"SUM {float(l.double().sum())!r} {float(z.double().sum())!r}"
     assert want in out.stdout, (want, out.stdout)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "gmm_n300_k8", "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline", "--saturated", "0", "--no-legs"], capture_output=True, text=True, timeout=600,
-                         cwd=root, env=env)
+                          "--full", "--no-cpu-baseline", "--saturated", "0", "--no-legs"], capture_output=True, text=True,
+                         timeout=600, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert r["value"] > 0 and r["roofline"]["kernel"] == "" and r["roofline"]["kernel_ms"] == pytest.approx(r["ms_per_step"], rel=0.35)

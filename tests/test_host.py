@@ -240,3 +240,53 @@ def test_bench_self_launch_builds_the_launcher_command(monkeypatch):
                          env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "CMCD_BENCH_SHARED_GPU")})
     if torch.cuda.device_count() < 2:
         assert out.returncode == 2 and "GPU(s) visible" in out.stderr
+
+
+def test_bench_dump_outputs_writes_the_arrays_within_the_cap(tmp_path):
+    """bench.py --dump-outputs: losses / z float32 and stats float64 as DIR/<name>.npy, every file finite: non-finite entries
+    are 0 there and coded in DIR/<name>_nonfinite.npy (+1 +inf, -1 -inf, 2 NaN); above the byte cap the same fixed sample of
+    particles (rows in ascending order) of losses, z and their codes, within the cap."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    names = [f"{n}{tail}" for n in ("losses", "z", "stats") for tail in ("", "_nonfinite")]
+
+    def load(d):
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in names)
+        got = {n: np.load(d / f"{n}.npy") for n in names}
+        assert all(np.isfinite(a).all() for a in got.values())
+        return got
+
+    rng = np.random.default_rng(3)
+    losses = rng.standard_normal(1000).astype(np.float32)
+    losses[5], losses[6], losses[7] = -np.inf, np.inf, np.nan
+    z = rng.standard_normal((1000, 10)).astype(np.float32)
+    z[5, 3] = -np.inf
+    stats = rng.standard_normal(5)
+    stats[1] = -np.inf
+    bench.dump_outputs(str(tmp_path / "whole"), losses, z, stats)
+    got = load(tmp_path / "whole")
+    assert got["losses"].dtype == np.float32 and got["z"].dtype == np.float32 and got["stats"].dtype == np.float64
+    assert all(got[n + "_nonfinite"].dtype == np.float32 for n in ("losses", "z", "stats"))
+    assert list(got["losses_nonfinite"][5:8]) == [-1.0, 1.0, 2.0] and not got["losses_nonfinite"][8:].any()
+    assert list(got["losses"][5:8]) == [0.0, 0.0, 0.0]
+    fin = np.isfinite(losses)
+    assert np.array_equal(got["losses"][fin], losses[fin]) and np.array_equal(got["stats"][[0, 2, 3, 4]], stats[[0, 2, 3, 4]])
+    assert got["z_nonfinite"][5, 3] == -1.0 and got["z"][5, 3] == 0.0 and np.count_nonzero(got["z_nonfinite"]) == 1
+    assert got["stats_nonfinite"][1] == -1.0 and got["stats"][1] == 0.0
+    zf = np.isfinite(z)
+    assert np.array_equal(got["z"][zf], z[zf])
+    limit = 100 * 88 + 60
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"cut{k}"), losses, z, stats, limit=limit)
+    cut = [load(tmp_path / f"cut{k}") for k in range(2)]
+    assert sum(a.nbytes for a in cut[0].values()) <= limit and cut[0]["losses"].shape == (100,)
+    rows = np.sort(np.random.default_rng(0).choice(1000, 100, replace=False))      # the documented fixed sample
+    assert np.array_equal(z[rows][np.isfinite(z[rows])], cut[0]["z"][np.isfinite(z[rows])])
+    assert np.array_equal(cut[0]["losses_nonfinite"], got["losses_nonfinite"][rows])
+    for n in names:
+        assert np.array_equal(cut[0][n], cut[1][n])
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 10 ** 6

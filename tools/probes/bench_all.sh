@@ -1,7 +1,7 @@
 # one bench line per BASELINE configuration (forward throughput; the north star also carries the training objects)
 cd $GRAFT_REPO_ROOT
 for c in gmm_n300_k8 funnel_n300_k64 many_gmm_n2000_k256_dds many_gmm_var_n16000_k256 lgcp_n20_k128; do
-  python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --saturated 0 2>/dev/null | tail -1
+  python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline --saturated 0 2>/dev/null | tail -1
 done > gpurun_out/r01_k_all_configs.jsonl
 python3 - <<'PY'
 import json

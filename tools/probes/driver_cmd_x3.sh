@@ -7,6 +7,5 @@ import json, sys
 T = sys.argv[1]
 for k in (1, 2, 3):
     d = json.loads(open('gpurun_out/%s_%d.json' % (T, k)).read())
-    print(T, 'run', k, 'ms_per_step %.5f' % d['ms_per_step'], 'value %.4g' % d['value'], 'kernel_ms %.5f' % d['roofline']['kernel_ms'],
-          'frac %.4f' % d['roofline']['frac'], 'prepared %.5f' % d['legs']['weak_prepared']['ms_per_step'])
+    print(T, 'run', k, 'ms_per_step %.5f' % d['ms_per_step'], 'value %.4g' % d['value'])   # the plain line: headline only
 PY

@@ -8,7 +8,7 @@ O=gpurun_out/$T
 mkdir -p $O
 for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" "SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_LDS SQ_INSTS_LDS"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/p_$tag -- python3 bench.py --config lgcp_n20_k128 --particles $N --steps 2 --warmup 1 --spinup 0 --no-cpu-baseline --saturated 0 --no-legs > /dev/null 2>&1 || echo "pass failed: $set"
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/p_$tag -- python3 bench.py --full --config lgcp_n20_k128 --particles $N --steps 2 --warmup 1 --spinup 0 --no-cpu-baseline --saturated 0 --no-legs > /dev/null 2>&1 || echo "pass failed: $set"
 done
 python3 - $O <<'PY'
 import glob, csv, collections, json, sys

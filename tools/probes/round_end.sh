@@ -27,6 +27,6 @@ print(json.dumps(out))
 PY
 rm -rf gpurun_out/$T/prof gpurun_out/$T/pmc
 for c in gmm_n300_k8 funnel_n300_k64 many_gmm_n2000_k256_dds many_gmm_var_n16000_k256 lgcp_n20_k128; do
-  python3 bench.py --config $c --no-cpu-baseline --saturated 0 2>/dev/null | tail -1
+  python3 bench.py --full --config $c --no-cpu-baseline --saturated 0 2>/dev/null | tail -1
 done > gpurun_out/$T/all_configs.jsonl
 head -c 1200 gpurun_out/$T/bench.json; echo; head -8 gpurun_out/$T/kernel_stats.csv

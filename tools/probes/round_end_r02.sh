@@ -10,10 +10,10 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$T
 mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1
+python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo "bench done"
 rm -rf $O/prof
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 300 --warmup 50 --no-cpu-baseline --saturated 0 --forward-only --no-legs > $O/prof_bench.json 2> /dev/null || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --steps 300 --warmup 50 --no-cpu-baseline --saturated 0 --forward-only --no-legs > $O/prof_bench.json 2> /dev/null || exit 1
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf $O/prof
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 tools/probes/t9_grad_run.py 2000 > /dev/null 2>&1 || exit 1
@@ -23,7 +23,7 @@ echo "stats done"
 # --pmc passes (own runs, --kernel-trace only): headline batch through bench.py, config 4's shard through the probe
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_MFMA" "SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CYCLES" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc/a_$tag -- python3 bench.py --steps 5 --warmup 2 --spinup 0 --no-cpu-baseline --saturated 0 --forward-only --no-legs > /dev/null 2>&1 || echo "pass failed: $set"
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc/a_$tag -- python3 bench.py --full --steps 5 --warmup 2 --spinup 0 --no-cpu-baseline --saturated 0 --forward-only --no-legs > /dev/null 2>&1 || echo "pass failed: $set"
   rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc/b_$tag -- python3 tools/probes/t9_grad_run.py 2000 > /dev/null 2>&1 || echo "pass failed (t9): $set"
   echo "pmc $tag done"
 done
@@ -57,7 +57,7 @@ PY
 rm -rf $O/pmc
 # lgcp launch sequence: FETCH_SIZE / WRITE_SIZE per GEMM launch type (separate --pmc passes), with the kernel-source sha
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_lgcp/$c -- python3 bench.py --config lgcp_n20_k128 --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --saturated 0 --no-legs > /dev/null 2>&1 || echo "lgcp pass failed: $c"
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_lgcp/$c -- python3 bench.py --full --config lgcp_n20_k128 --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --saturated 0 --no-legs > /dev/null 2>&1 || echo "lgcp pass failed: $c"
 done
 python3 - $T <<'PY'
 import glob, csv, collections, json, sys, os
@@ -81,6 +81,6 @@ print(json.dumps(out)[:800])
 PY
 rm -rf $O/pmc_lgcp
 for c in gmm_n300_k8 funnel_n300_k64 many_gmm_n2000_k256_dds many_gmm_var_n16000_k256 lgcp_n20_k128; do
-  python3 bench.py --config $c --no-cpu-baseline --saturated 0 --no-legs 2>/dev/null | tail -1
+  python3 bench.py --full --config $c --no-cpu-baseline --saturated 0 --no-legs 2>/dev/null | tail -1
 done > $O/all_configs.jsonl
 head -c 600 $O/bench.json; echo; head -6 $O/kernel_stats.csv | cut -c1-160; head -5 $O/kernel_stats_cfg4_shard.csv | cut -c1-160

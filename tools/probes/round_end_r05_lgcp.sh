@@ -6,7 +6,7 @@ O=gpurun_out/$T
 mkdir -p $O
 rm -rf $O/pmc_lgcp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_lgcp/$c -- python3 bench.py --config lgcp_n20_k128 --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --saturated 0 --no-legs > /dev/null 2>&1 || echo "lgcp pass failed: $c"
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_lgcp/$c -- python3 bench.py --full --config lgcp_n20_k128 --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline --saturated 0 --no-legs > /dev/null 2>&1 || echo "lgcp pass failed: $c"
 done
 python3 - $T <<'PY'
 import glob, csv, collections, json, sys, os
@@ -32,5 +32,5 @@ rm -rf $O/pmc_lgcp
 python3 tools/probes/lgcp_time.py 20 32 64 128 600 2048 15000 > $O/lgcp_sizes.txt 2>/dev/null
 bash tools/probes/lgcp_nsk_prof.sh $T > /dev/null 2>&1
 bash tools/probes/lgcp_wide_prof.sh 600 $T > /dev/null 2>&1
-python3 bench.py --config lgcp_n20_k128 --no-cpu-baseline --saturated 0 --no-legs --train-step 2>/dev/null | tail -1 > $O/lgcp_config_line.json
+python3 bench.py --full --config lgcp_n20_k128 --no-cpu-baseline --saturated 0 --no-legs --train-step 2>/dev/null | tail -1 > $O/lgcp_config_line.json
 echo "lgcp done"

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/$T
 mkdir -p $O
 for k in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags_$k.json 2> $O/bench.err || exit 1; done
-python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1
+python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo "bench done"
 rm -rf $O/prof
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 tools/probes/uha_run.py 2000 > $O/uha_times.json 2>/dev/null || exit 1
