@@ -149,7 +149,8 @@ _grad_item_sent = None
 
 def sync_grad_item_override():
     """Forwards CMCD_GRAD_ITEM (unset / "0" / "1"; tests and tools/probes) to the library when it changed since the
-    last gradient call of this process: the library reads no environment on its per-call path."""
+    last gradient call of this process: the library reads no environment on its per-call path.  Returns the value in force
+    (the gradient workspace sizes depend on it: mcdboundingmachine._nbytes)."""
     global _grad_item_sent
     want = os.environ.get("CMCD_GRAD_ITEM")
     if want != _grad_item_sent:
@@ -159,6 +160,7 @@ def sync_grad_item_override():
         elif want is not None:
             raise RuntimeError("CMCD_GRAD_ITEM needs a library built with the diagnostic hooks (include/cmcd_hip_diag.h)")
         _grad_item_sent = want
+    return want
 
 
 def last_kernel_name():

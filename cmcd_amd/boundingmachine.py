@@ -6,13 +6,11 @@ mean-field VI bound (`nbridges = 0`) that /root/reference/src/main.py:82-109 opt
 `nbridges`; `compute_bound` / `grad_and_loss` run on the GPU through the C ABI (`cmcd_mfvi_bound_grad`)
 for `nbridges = 0` and raise `NotImplementedError` for the UHA chain (`nbridges >= 1`, ais_utils.evolve —
 outside this build's scope)."""
-import ctypes as C
-
 import torch
 
 from . import _lib
 from . import variationaldist as vd
-from .mcdboundingmachine import ravel_pytree, _workspace
+from .mcdboundingmachine import ravel_pytree, _inputs, _outputs, _stream, _workspace, _zero_notrain
 
 
 def initialize(dim, vdparams=None, nbridges=0, lfsteps=1, eps=0.0, eta=0.5, mdparams=None, ngridb=32,
@@ -52,39 +50,29 @@ def _call(seeds, params_flat, unflatten, params_fixed, log_prob, want_grad, n_to
         raise TypeError("log_prob must be a cmcd_amd.model_handler.Target (see load_model)")
     if log_prob.dim != dim:
         raise ValueError(f"target dim {log_prob.dim} != params_fixed dim {dim}")
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
+    seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    seeds = torch.as_tensor(seeds)
-    if seeds.device != device or seeds.dtype != torch.int32 or not seeds.is_contiguous():
-        seeds = seeds.to(device=device, dtype=torch.int32).contiguous()
-    n = seeds.numel()
-    if n < 1:
-        raise ValueError("seeds is empty")
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return _call(seeds, params_flat, unflatten, params_fixed, log_prob, want_grad, n_total)
+    dev_index, stream, capturing = here
     nbytes = L.cmcd_mfvi_workspace_bytes(log_prob.target_id, dim, n)
     if nbytes <= 0:
         raise NotImplementedError(_lib.last_error() or "no mean-field kernel for this target")
-    ws = _workspace(device, nbytes, "mfvi")
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "mfvi")
     consts = log_prob.consts_on(device)
-    losses = torch.empty(n, dtype=torch.float32, device=device)
-    z = torch.empty(n, dim, dtype=torch.float32, device=device)
-    stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
+    losses, z, stats = _outputs(n, dim, device)
     grad = torch.empty_like(params_flat) if want_grad else None
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(L.cmcd_mfvi_bound_grad(
-            log_prob.target_id, dim, unflatten.offset("vd", "mean"), unflatten.offset("vd", "logdiag"),
-            seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-            consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-            1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
-            losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr() if want_grad else None, stream))
+    _lib.check(L.cmcd_mfvi_bound_grad(
+        log_prob.target_id, dim, unflatten.offset("vd", "mean"), unflatten.offset("vd", "logdiag"),
+        seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
+        1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
+        losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr() if want_grad else None, stream))
     if want_grad:
-        # params_notrain = stop_gradient(params_notrain) (boundingmachine.py:75): "vd" outside `trainable` => zero
-        n_train = min((off for path, (off, _) in unflatten.layout.items() if path[0] == 1), default=params_flat.numel())
-        grad[n_train:].zero_()
+        _zero_notrain(grad, unflatten)      # "vd" outside `trainable` => zero
     return grad, losses, z, stats
 
 

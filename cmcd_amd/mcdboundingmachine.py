@@ -7,8 +7,8 @@ place of jax arrays and a `Target` descriptor (cmcd_amd.model_handler) in place 
 there is no CPU fallback.
 """
 import ctypes as C
-
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -202,34 +202,69 @@ class fixed_parameters:
 PREP_CALLS = {"prepared": 0, "full": 0}      # forward calls that skipped / ran the prep launch (tests, bench)
 
 
-def _workspace(device, nbytes, tag=""):
+def _workspace(dev_index, device, stream, capturing, nbytes, tag):
     """Scratch buffer of one (device, HIP stream, purpose): calls enqueued on different streams of one device — from
     one host thread or several — never share a workspace, so they may overlap on the GPU (include/cmcd_hip.h: the
-    library itself keeps nothing between calls).  Calls on the same stream are ordered and reuse the buffer."""
-    dev = torch.device(device)
-    is_cuda = dev.type == "cuda"
-    if is_cuda:
-        # the capture status and the stream handle are both those of `device` — which need not be the current device
-        with torch.cuda.device(dev):
-            capturing = torch.cuda.is_current_stream_capturing()
-            stream = torch.cuda.current_stream().cuda_stream
-            dev_key = torch.cuda.current_device()       # "cuda" and "cuda:0" are one device
-    else:
-        capturing, stream, dev_key = False, 0, str(dev)
+    library itself keeps nothing between calls).  Calls on the same stream are ordered and reuse the buffer.
+    `dev_index`, `stream`, `capturing` are those of `device` (see _stream)."""
     if capturing:
         # inside torch.cuda.graph(): the buffer must come from (and stay with) the graph's private pool, so it is neither
         # taken from the cache nor put into it — an eager call that later runs on a recycled stream handle never sees it
         return torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-    per_dev = _workspaces.setdefault(dev_key, {})      # one LRU per device: a busy device never evicts another's buffers
+    per_dev = _workspaces.setdefault(dev_index, {})      # one LRU per device: a busy device never evicts another's buffers
     key = (stream, tag)
     ws = per_dev.pop(key, None)              # re-inserted below: the dict is ordered by last use
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _prepared.pop((dev_key, ws.data_ptr()), None)      # a fresh buffer holds nobody's tables, whatever lived at its address
+        _prepared.pop((dev_index, ws.data_ptr()), None)      # a fresh buffer holds nobody's tables, whatever lived at its address
     per_dev[key] = ws
     while len(per_dev) > _WORKSPACE_CACHE:         # least recently used first: streams that died, one-off streams
         per_dev.pop(next(iter(per_dev)))
     return ws
+
+
+def _stream(device):
+    """-> (device index, raw handle of the device's current HIP stream, whether that stream is being captured), or None when
+    `device` is not the current device: the caller then re-enters itself under torch.cuda.device(device), so that every HIP
+    call belongs to the tensor's device (rare; the common case pays no context manager)."""
+    dev_index, current = device.index, torch._C._cuda_getDevice()
+    if dev_index is None:
+        dev_index = current                  # "cuda" is the current device
+    elif dev_index != current:
+        return None
+    return dev_index, torch._C._cuda_getCurrentRawStream(dev_index), torch._C._cuda_isCurrentStreamCapturing()
+
+
+def _inputs(seeds, params_flat):
+    """The tensor checks every entry point makes -> (seeds as a contiguous int32 tensor on params_flat's device, n)."""
+    if not params_flat.is_cuda:
+        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
+    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
+        raise ValueError("params_flat must be contiguous float32")
+    device = params_flat.device
+    if not isinstance(seeds, torch.Tensor) or seeds.device != device or seeds.dtype != torch.int32 or not seeds.is_contiguous():
+        seeds = torch.as_tensor(seeds).to(device=device, dtype=torch.int32).contiguous()
+    n = seeds.numel()
+    if n < 1:
+        raise ValueError("seeds is empty")
+    return seeds, n
+
+
+def _outputs(n, dim, device):
+    """-> (losses[n] f32, z[n, dim] f32, stats[NSTATS] f64), for the library to fill."""
+    return (torch.empty(n, dtype=torch.float32, device=device), torch.empty((n, dim), dtype=torch.float32, device=device),
+            torch.empty(_lib.NSTATS, dtype=torch.float64, device=device))
+
+
+def _zero_notrain(grad, unflatten):
+    """params_notrain = stop_gradient(params_notrain) (the reference's mcdboundingmachine.py:142, boundingmachine.py:75): only
+    the leaves of params_train carry a gradient; they are the leading block of params_flat.  Where that block ends is found
+    once per Unflatten."""
+    n_train = unflatten.__dict__.get("_n_train", -1)
+    if n_train == -1:
+        n_train = unflatten._n_train = min((off for path, (off, _) in unflatten.layout.items() if path[0] == 1), default=None)
+    if n_train is not None:
+        grad[n_train:].zero_()
 
 
 def _layout(unflatten, spec):
@@ -271,14 +306,17 @@ def _layout_no_net(unflatten):
     return lay
 
 
-_plans = {}      # what one forward call needs besides its tensors, per (parameter tree, net, mode, target, flags): see _plan
+_plans = {}      # what one call needs besides its tensors, per (parameter tree, net, mode, target, flags): see _plan
+_Plan = namedtuple("_Plan", "unflatten_ref target_ref desc lay desc_b lay_b spec nbytes_of")
 
 
 def _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping):
     """The descriptor, the layout struct and their byte images for one (unflatten, params_fixed, target, static flags): built
-    once, looked up per call.  A forward call of the smallest configuration is 18 us of GPU time; building two ctypes structs,
+    once, looked up per call, by every entry point of this module — the one place that validates params_fixed / the target
+    and builds a cmcd_desc.  A forward call of the smallest configuration is 18 us of GPU time; building two ctypes structs,
     their byte keys and twenty dictionary searches per call made the HOST the bound there (29 us per call, r05
-    tools/probes/host_overhead.py)."""
+    tools/probes/host_overhead.py).  `nbytes_of` holds the workspace sizes the library reported for this descriptor
+    (see _nbytes)."""
     key = (id(unflatten), params_fixed, id(log_prob), eps_schedule, bool(grad_clipping), KERNEL_VARIANT)
     plan = _plans.get(key)
     if plan is not None and plan[0]() is unflatten and plan[1]() is log_prob:
@@ -300,71 +338,47 @@ def _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping):
                      eps_schedule=_lib.EPS_SCHEDULE[sched], grad_clipping=int(bool(grad_clipping)),
                      ngrid=unflatten.shape("mgridref_y")[0] - 1, reserved=KERNEL_VARIANT)
     lay = _layout(unflatten, spec) if mode != "MCD_ULA" else _layout_no_net(unflatten)
-    plan = (weakref.ref(unflatten), weakref.ref(log_prob), desc, lay, bytes(desc), bytes(lay), spec, {})
+    plan = _Plan(weakref.ref(unflatten), weakref.ref(log_prob), desc, lay, bytes(desc), bytes(lay), spec, {})
     while len(_plans) > 256:
         _plans.pop(next(iter(_plans)))
     _plans[key] = plan
     return plan
 
 
+def _nbytes(plan, query, n, grad_item=None):
+    """What the library's size query `query` (cmcd_workspace_bytes, cmcd_grad_workspace_bytes,
+    cmcd_bound_grad_workspace_bytes) answers for the plan's descriptor and n particles, asked once per (query, n, grad_item).
+    The two gradient sizes depend on the CMCD_GRAD_ITEM override: the gradient entry points pass the value in force (what
+    _lib.sync_grad_item_override() returns) and it is PART OF THE KEY, so a size cached under one setting is never used
+    under another.  An answer <= 0 (no kernel; the caller raises) is not kept."""
+    key = (query, n, grad_item)
+    nbytes = plan.nbytes_of.get(key)
+    if nbytes is None:
+        nbytes = getattr(_lib.lib(), query)(C.byref(plan.desc), n)
+        if nbytes > 0 and len(plan.nbytes_of) < 64:
+            plan.nbytes_of[key] = nbytes
+    return nbytes
+
+
 def bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
     """One launch sequence of the hot path.  Returns (losses[N] f32, z[N,dim] f32, stats[5] f64),
     all device tensors, enqueued asynchronously on the current stream."""
-    _, _, desc, lay, desc_b, lay_b, spec, nbytes_of = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
-    device = params_flat.device
-    dev_index = device.index
-    if dev_index is None or torch._C._cuda_getDevice() != dev_index:
-        # the tensor's device is not the current one: every HIP call below belongs to `device` (rare; the common case pays
-        # no context manager)
-        with torch.cuda.device(device):
-            return _bound_forward_here(seeds, params_flat, log_prob, desc, lay, desc_b, lay_b, spec, nbytes_of,
-                                       torch.cuda.current_device(), params_fixed[0])
-    return _bound_forward_here(seeds, params_flat, log_prob, desc, lay, desc_b, lay_b, spec, nbytes_of, dev_index, params_fixed[0])
-
-
-def _forward_workspace(dev_index, device, stream, capturing, nbytes):
-    """_workspace for the forward call, with the stream handle and capture status already in hand (same cache, same rules)."""
-    if capturing:
-        return torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-    per_dev = _workspaces.setdefault(dev_index, {})
-    key = (stream, "")
-    ws = per_dev.pop(key, None)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _prepared.pop((dev_index, ws.data_ptr()), None)
-    per_dev[key] = ws
-    while len(per_dev) > _WORKSPACE_CACHE:
-        per_dev.pop(next(iter(per_dev)))
-    return ws
-
-
-def _bound_forward_here(seeds, params_flat, log_prob, desc, lay, desc_b, lay_b, spec, nbytes_of, dev_index, dim):
-    """bound_forward with `params_flat.device` current."""
+    plan = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    _, _, desc, lay, desc_b, lay_b, spec, _ = plan
+    seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    if not isinstance(seeds, torch.Tensor) or seeds.device != device or seeds.dtype != torch.int32 or not seeds.is_contiguous():
-        seeds = torch.as_tensor(seeds).to(device=device, dtype=torch.int32).contiguous()
-    n = seeds.numel()
-    if n < 1:
-        raise ValueError("seeds is empty")
-    nbytes = nbytes_of.get(n)
-    if nbytes is None:
-        nbytes = L.cmcd_workspace_bytes(C.byref(desc), n)
-        if nbytes <= 0:
-            _lib.check(-2 if "not implemented" in _lib.last_error() or "no kernel" in _lib.last_error() else -1)
-        if len(nbytes_of) < 64:
-            nbytes_of[n] = nbytes
-    stream = torch._C._cuda_getCurrentRawStream(dev_index)
-    capturing = torch._C._cuda_isCurrentStreamCapturing()
-    ws = _forward_workspace(dev_index, device, stream, capturing, nbytes)
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    dev_index, stream, capturing = here
+    nbytes = _nbytes(plan, "cmcd_workspace_bytes", n)
+    if nbytes <= 0:
+        _lib.check(-2 if "not implemented" in _lib.last_error() or "no kernel" in _lib.last_error() else -1)
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "")
     consts = log_prob.consts_on(device)
-    losses = torch.empty(n, dtype=torch.float32, device=device)
-    z = torch.empty((n, dim), dtype=torch.float32, device=device)
-    stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
+    losses, z, stats = _outputs(n, params_fixed[0], device)
     # the tables this workspace holds: formed by the previous call from exactly these inputs?  (see _prepared)
     # `slot` names the buffer on EVERY call — in or out of fixed_parameters(), capturing or not — because every call
     # overwrites the buffer's tables and must therefore retire whatever claim an earlier call left on it (r04 advisor:
@@ -432,63 +446,42 @@ def compute_log_var_grad(seeds, params_flat, unflatten, params_fixed, log_prob, 
     is what the HIP kernel exploits.  Multi-GPU: pass the global particle count `n_total` and `stats_total` —
     the merged statistics, or a callable `local_stats -> merged_stats` that runs the all-gather between the
     forward and the gradient launch — and all-reduce the returned gradient."""
-    dim, nbridges, mode, spec = params_fixed
-    if mode != "MCD_CAIS_var_sn":
+    if params_fixed[2] != "MCD_CAIS_var_sn":
         raise NotImplementedError("Mode not implemented.")
-    if not isinstance(spec, ScoreNet):
-        raise ValueError("params_fixed[3] must be the ScoreNet returned by initialize()")
-    if not hasattr(log_prob, "target_id"):
-        raise TypeError("log_prob must be a cmcd_amd.model_handler.Target (see load_model)")
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
+    plan = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    seeds = torch.as_tensor(seeds)
-    if seeds.device != device or seeds.dtype != torch.int32 or not seeds.is_contiguous():
-        seeds = seeds.to(device=device, dtype=torch.int32).contiguous()
-    n = seeds.numel()
-    if n < 1:
-        raise ValueError("seeds is empty")
-    if eps_schedule not in _lib.EPS_SCHEDULE:
-        eps_schedule = None
-    desc = _lib.Desc(dim=dim, nbridges=nbridges, mode=_lib.MODE[mode], arch=_lib.ARCH[spec.arch],
-                     emb_dim=spec.emb_dim, target=log_prob.target_id,
-                     eps_schedule=_lib.EPS_SCHEDULE[eps_schedule], grad_clipping=int(bool(grad_clipping)),
-                     ngrid=unflatten.shape("mgridref_y")[0] - 1, reserved=KERNEL_VARIANT)
-    lay = _layout(unflatten, spec)
-    _lib.sync_grad_item_override()
-    nbytes = L.cmcd_grad_workspace_bytes(C.byref(desc), n)
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return compute_log_var_grad(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping,
+                                        n_total, stats_total)
+    dev_index, stream, capturing = here
+    desc, lay = C.byref(plan.desc), C.byref(plan.lay)
+    nbytes = _nbytes(plan, "cmcd_grad_workspace_bytes", n, _lib.sync_grad_item_override())
     if nbytes <= 0:
         raise NotImplementedError(_lib.last_error() or "no gradient kernel for this configuration")
-    ws = _workspace(device, nbytes, "grad")
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "grad")
     consts = log_prob.consts_on(device)
     cptr, cnum = (consts.data_ptr(), consts.numel()) if consts is not None else (None, 0)
-    losses = torch.empty(n, dtype=torch.float32, device=device)
-    z = torch.empty(n, dim, dtype=torch.float32, device=device)
-    stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
+    losses, z, stats = _outputs(n, params_fixed[0], device)
     omega = torch.empty(n, dtype=torch.float32, device=device)
     grad = torch.empty_like(params_flat)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream().cuda_stream
-        # forward on the gradient workspace: the per-call tables (and, for small batches, the trajectory) stay
-        # there for the gradient call, so the chain runs once
-        _lib.check(L.cmcd_bound_var_forward(
-            C.byref(desc), C.byref(lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-            cptr, cnum, ws.data_ptr(), ws.numel(), losses.data_ptr(), z.data_ptr(), stats.data_ptr(), stream))
-        st = stats if stats_total is None else stats_total
-        if callable(st):   # multi-GPU: the caller merges the local statistics across ranks here
-            st = st(stats)
-        _lib.check(L.cmcd_vargrad_weights(losses.data_ptr(), st.data_ptr(), n, n if n_total is None else int(n_total),
-                                          omega.data_ptr(), stream))
-        _lib.check(L.cmcd_bound_var_grad_kept(
-            C.byref(desc), C.byref(lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-            cptr, cnum, omega.data_ptr(), ws.data_ptr(), ws.numel(), grad.data_ptr(), stream))
-    # params_notrain = stop_gradient(params_notrain) (mcdboundingmachine.py:142): only the leaves of
-    # params_train carry a gradient; they are the leading block of params_flat
-    n_train = min((off for path, (off, _) in unflatten.layout.items() if path[0] == 1), default=params_flat.numel())
-    grad[n_train:].zero_()
+    # forward on the gradient workspace: the per-call tables (and, for small batches, the trajectory) stay
+    # there for the gradient call, so the chain runs once
+    _lib.check(L.cmcd_bound_var_forward(
+        desc, lay, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        cptr, cnum, ws.data_ptr(), ws.numel(), losses.data_ptr(), z.data_ptr(), stats.data_ptr(), stream))
+    st = stats if stats_total is None else stats_total
+    if callable(st):   # multi-GPU: the caller merges the local statistics across ranks here
+        st = st(stats)
+    _lib.check(L.cmcd_vargrad_weights(losses.data_ptr(), st.data_ptr(), n, n if n_total is None else int(n_total),
+                                      omega.data_ptr(), stream))
+    _lib.check(L.cmcd_bound_var_grad_kept(
+        desc, lay, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        cptr, cnum, omega.data_ptr(), ws.data_ptr(), ws.numel(), grad.data_ptr(), stream))
+    _zero_notrain(grad, unflatten)
     return grad, (losses, z)
 
 
@@ -502,54 +495,32 @@ def compute_bound_grad(seeds, params_flat, unflatten, params_fixed, log_prob, ep
     launch sequence (keeping z_0..z_K in the workspace) and the reverse sweep.
     Returns (grad_flat, (losses, z)) [+ stats with return_stats]; multi-GPU: pass the global particle count
     as `n_total` and all-reduce the returned gradient."""
-    dim, nbridges, mode, spec = params_fixed
     # the two overdamped baselines and 2nd-order CMCD (no stop_gradient either) take the same call
-    if mode not in ("MCD_CAIS_sn", "MCD_ULA_sn", "MCD_ULA", "MCD_CAIS_UHA_sn"):
+    if params_fixed[2] not in ("MCD_CAIS_sn", "MCD_ULA_sn", "MCD_ULA", "MCD_CAIS_UHA_sn"):
         raise NotImplementedError("Mode not implemented.")
-    if mode == "MCD_ULA":
-        spec = ScoreNet("dds", dim, 64, 0, 64)   # placeholder: MCD_ULA has no network (apply_fun_sn is None)
-    elif not isinstance(spec, ScoreNet):
-        raise ValueError("params_fixed[3] must be the ScoreNet returned by initialize()")
-    if not hasattr(log_prob, "target_id"):
-        raise TypeError("log_prob must be a cmcd_amd.model_handler.Target (see load_model)")
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
+    plan = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    seeds = torch.as_tensor(seeds)
-    if seeds.device != device or seeds.dtype != torch.int32 or not seeds.is_contiguous():
-        seeds = seeds.to(device=device, dtype=torch.int32).contiguous()
-    n = seeds.numel()
-    if n < 1:
-        raise ValueError("seeds is empty")
-    if eps_schedule not in _lib.EPS_SCHEDULE:
-        eps_schedule = None
-    desc = _lib.Desc(dim=dim, nbridges=nbridges, mode=_lib.MODE[mode], arch=_lib.ARCH[spec.arch],
-                     emb_dim=spec.emb_dim, target=log_prob.target_id,
-                     eps_schedule=_lib.EPS_SCHEDULE[eps_schedule], grad_clipping=int(bool(grad_clipping)),
-                     ngrid=unflatten.shape("mgridref_y")[0] - 1, reserved=KERNEL_VARIANT)
-    lay = _layout(unflatten, spec) if mode != "MCD_ULA" else _layout_no_net(unflatten)
-    _lib.sync_grad_item_override()
-    nbytes = L.cmcd_bound_grad_workspace_bytes(C.byref(desc), n)
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return compute_bound_grad(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping,
+                                      n_total, return_stats)
+    dev_index, stream, capturing = here
+    nbytes = _nbytes(plan, "cmcd_bound_grad_workspace_bytes", n, _lib.sync_grad_item_override())
     if nbytes <= 0:
         raise NotImplementedError(_lib.last_error() or "no gradient kernel for this configuration")
-    ws = _workspace(device, nbytes, "bptt")
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "bptt")
     consts = log_prob.consts_on(device)
-    losses = torch.empty(n, dtype=torch.float32, device=device)
-    z = torch.empty(n, dim, dtype=torch.float32, device=device)
-    stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
+    losses, z, stats = _outputs(n, params_fixed[0], device)
     grad = torch.empty_like(params_flat)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(L.cmcd_bound_grad(
-            C.byref(desc), C.byref(lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-            consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-            1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
-            losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr(), stream))
-    n_train = min((off for path, (off, _) in unflatten.layout.items() if path[0] == 1), default=params_flat.numel())
-    grad[n_train:].zero_()
+    _lib.check(L.cmcd_bound_grad(
+        C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
+        1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
+        losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr(), stream))
+    _zero_notrain(grad, unflatten)
     if return_stats:
         return grad, (losses, z), stats
     return grad, (losses, z)

@@ -290,3 +290,131 @@ def test_bench_dump_outputs_writes_the_arrays_within_the_cap(tmp_path):
     for n in names:
         assert np.array_equal(cut[0][n], cut[1][n])
     assert bench.DUMP_LIMIT_BYTES <= 64 * 10 ** 6
+
+
+def _entry_points():
+    """(name, call(seeds, params_flat, unflatten, params_fixed, target)) of every bound / gradient entry point, with a CPU
+    build whose mode that entry point accepts."""
+    from cmcd_amd import boundingmachine as bm
+    sn = synthetic.build("gmm_n300_k8", device="cpu")
+    var = synthetic.build("many_gmm_var_n16000_k256", device="cpu")
+    flat, un, fixed = bm.initialize(dim=2, device="cpu")
+    mf = {"params_flat": flat, "unflatten": un, "params_fixed": fixed, "target": sn["target"]}
+    return [("compute_bound", mcdbm.compute_bound, sn), ("compute_bound_var", mcdbm.compute_bound_var, var),
+            ("compute_bound_grad", mcdbm.compute_bound_grad, sn), ("compute_log_var_grad", mcdbm.compute_log_var_grad, var),
+            ("bm.compute_bound", bm.compute_bound, mf), ("bm.grad_and_loss", bm.grad_and_loss, mf)]
+
+
+def test_every_entry_point_validates_alike_before_it_needs_a_device():
+    """One call path: forward, both gradients and the mean-field bound refuse the same inputs with the same exceptions, in the
+    same order (mode, target type, target dim, then the device), all before the library is loaded."""
+    seeds = torch.arange(1, 9, dtype=torch.int32)
+    wide = model_handler.load_model("funnel")[0]                       # dim 10 against the builds' dim 2
+    assert wide.dim == 10
+    for name, fn, b in _entry_points():
+        args = lambda **kw: [seeds] + [kw.get(k, b[k]) for k in ("params_flat", "unflatten", "params_fixed", "target")]
+        assert b["params_fixed"][0] == 2, name
+        with pytest.raises(RuntimeError, match="the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor"):
+            fn(*args())
+        with pytest.raises(TypeError, match="log_prob must be a cmcd_amd.model_handler.Target"):
+            fn(*args(target=lambda z: z.sum()))
+        with pytest.raises(ValueError, match="target dim 10 != params_fixed dim 2"):
+            fn(*args(target=wide))
+        if not name.startswith("bm."):
+            dim, K, _, spec = b["params_fixed"]
+            for mode in ("MCD_U_a-lp", "MCD_U_a-lp-sna"):
+                with pytest.raises(NotImplementedError, match="Mode not implemented."):   # before the TypeError / RuntimeError
+                    fn(*args(params_fixed=(dim, K, mode, spec), target=lambda z: z.sum()))
+    # each gradient keeps its own mode gate: the other gradient's mode is refused, on CPU tensors, as an unknown one is
+    (_, bptt, sn), (_, vargrad, var) = _entry_points()[2:4]
+    for fn, b in ((bptt, var), (vargrad, sn)):
+        with pytest.raises(NotImplementedError, match="Mode not implemented."):
+            fn(seeds, b["params_flat"], b["unflatten"], b["params_fixed"], b["target"])
+
+
+def test_plan_is_shared_and_follows_the_kernel_variant(monkeypatch):
+    """One plan per (tree, params_fixed, target, flags, KERNEL_VARIANT), KERNEL_VARIANT read at call time."""
+    b = synthetic.build("gmm_n300_k8", device="cpu")
+    plan = lambda **kw: mcdbm._plan(b["unflatten"], b["params_fixed"], b["target"], kw.get("eps"), kw.get("clip", False))
+    monkeypatch.setattr(mcdbm, "KERNEL_VARIANT", 0)
+    p0 = plan()
+    assert plan() is p0 and p0.desc.reserved == 0 and p0.desc.dim == 2 and p0.desc.nbridges == 8
+    monkeypatch.setattr(mcdbm, "KERNEL_VARIANT", 2)
+    p2 = plan()
+    assert p2 is not p0 and p2.desc.reserved == 2 and p0.desc.reserved == 0
+    assert p2.nbytes_of is not p0.nbytes_of                            # sizes are cached per descriptor
+    assert bytes(p2.desc) != bytes(p0.desc) and bytes(p2.lay) == bytes(p0.lay)
+    monkeypatch.setattr(mcdbm, "KERNEL_VARIANT", 0)
+    assert plan() is p0
+    assert plan(eps="cos_sq") is not p0 and plan(eps="cos_sq").desc.eps_schedule == 2 and plan(clip=True).desc.grad_clipping == 1
+
+
+def test_workspace_lru_rules(monkeypatch):
+    """_workspace, the only copy of the rules, on CPU buffers: (stream, tag) reuses its buffer; a larger request replaces it and
+    drops whatever claim the prepared table holds on the new buffer's slot; the 17th key of a device evicts the least recently
+    used; a capturing call gets a private buffer that the cache never sees."""
+    dropped = []
+
+    class Prepared(dict):
+        def pop(self, key, *default):
+            dropped.append(key)
+            return super().pop(key, *default)
+
+    monkeypatch.setattr(mcdbm, "_workspaces", {})
+    monkeypatch.setattr(mcdbm, "_prepared", Prepared())
+    cpu = torch.device("cpu")
+    ws = lambda stream, nbytes, tag="", capturing=False: mcdbm._workspace("cpu", cpu, stream, capturing, nbytes, tag)
+    a = ws(7, 100)
+    assert a.dtype == torch.uint8 and a.numel() == 1 << 20 and dropped == [("cpu", a.data_ptr())]
+    mcdbm._prepared[("cpu", a.data_ptr())] = "tables of an earlier call"
+    assert ws(7, 1 << 20) is a and len(dropped) == 1                   # same (stream, tag), large enough: reused, claim untouched
+    assert ws(7, 100, "grad") is not a and ws(8, 100) is not a         # another purpose / another stream: buffers of their own
+    dropped.clear()
+    big = ws(7, (1 << 20) + 1)
+    assert big is not a and big.numel() == (1 << 20) + 1 and dropped == [("cpu", big.data_ptr())]
+    assert ws(7, 100) is big and mcdbm._workspaces["cpu"][(7, "")] is big
+    # capture: private, never cached, and nothing in the cache moves
+    before = dict(mcdbm._workspaces["cpu"])
+    private = ws(7, 100, capturing=True)
+    assert private is not big and private.numel() == 1 << 20 and mcdbm._workspaces["cpu"] == before
+    assert ws(99, 100, capturing=True) is not None and (99, "") not in mcdbm._workspaces["cpu"]
+    # per-device LRU of 16: fill it, touch the oldest key, add one more
+    monkeypatch.setattr(mcdbm, "_workspaces", {})
+    first = [ws(s, 100) for s in range(mcdbm._WORKSPACE_CACHE)]
+    assert len(mcdbm._workspaces["cpu"]) == 16
+    assert ws(0, 100) is first[0]                                      # stream 0 is now the most recently used, stream 1 the least
+    ws(16, 100)                                                        # the 17th key
+    assert len(mcdbm._workspaces["cpu"]) == 16 and (1, "") not in mcdbm._workspaces["cpu"]
+    assert ws(0, 100) is first[0] and ws(2, 100) is first[2]
+    other = mcdbm._workspace("cpu:1", cpu, 0, False, 100, "")          # another device's LRU is its own
+    assert other is not first[0] and len(mcdbm._workspaces["cpu"]) == 16 and len(mcdbm._workspaces["cpu:1"]) == 1
+
+
+def test_non_trainable_tail_is_found_once_per_unflatten():
+    flat, un, _ = mcdbm.initialize(dim=2, nbridges=8, eps=0.01, trainable=("eps", "vd"), mode="MCD_CAIS_sn", emb_dim=20,
+                                   nn_arch="geffner", device="cpu")
+    n_train = un.offset("eta")                                         # keys sorted: eta is the first leaf of params_notrain
+    assert n_train == min(off for path, (off, _) in un.layout.items() if path[0] == 1)
+    g = torch.ones_like(flat)
+    mcdbm._zero_notrain(g, un)
+    assert un._n_train == n_train and bool((g[:n_train] == 1).all()) and bool((g[n_train:] == 0).all())
+    un.layout = None                                                   # a second call does not scan the layout again
+    g = torch.ones_like(flat)
+    mcdbm._zero_notrain(g, un)
+    assert float(g.sum()) == n_train
+    flat, un = mcdbm.ravel_pytree(({"a": torch.ones(3)},))              # no params_notrain at all: nothing to zero
+    g = torch.ones_like(flat)
+    mcdbm._zero_notrain(g, un)
+    assert un._n_train is None and float(g.sum()) == 3
+
+
+def test_stream_helper_answers_only_for_the_current_device(monkeypatch):
+    """_stream: (device index, raw stream of THAT device, capturing) when the tensor's device is current, None otherwise (the
+    entry point then re-enters itself under torch.cuda.device)."""
+    asked = []
+    monkeypatch.setattr(torch._C, "_cuda_getDevice", lambda: 1, raising=False)
+    monkeypatch.setattr(torch._C, "_cuda_getCurrentRawStream", lambda i: asked.append(i) or 0xABC0 + i, raising=False)
+    monkeypatch.setattr(torch._C, "_cuda_isCurrentStreamCapturing", lambda: False, raising=False)
+    assert mcdbm._stream(torch.device("cuda", 1)) == (1, 0xABC1, False)
+    assert mcdbm._stream(torch.device("cuda")) == (1, 0xABC1, False)           # "cuda" is the current device
+    assert mcdbm._stream(torch.device("cuda", 0)) is None and asked == [1, 1]
