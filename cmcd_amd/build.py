@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libcmcd_hip.so")
-SOURCES = ["cmcd_kernels.hip", "cmcd_uha.hip", "cmcd_coop.hip", "cmcd_coop_wide.hip", "cmcd_lgcp.hip", "cmcd_lgcp_wide.hip", "cmcd_grad.hip", "cmcd_bptt.hip", "cmcd_mfvi.hip", "cmcd_opt.hip"]
+SOURCES = ["cmcd_api.hip", "cmcd_kernels.hip", "cmcd_uha.hip", "cmcd_coop.hip", "cmcd_coop_wide.hip", "cmcd_lgcp.hip", "cmcd_lgcp_wide.hip", "cmcd_grad.hip", "cmcd_bptt.hip", "cmcd_mfvi.hip", "cmcd_opt.hip"]
 HEADERS = ["cmcd_device.h", os.path.join(ROOT, "include", "cmcd_hip.h"), os.path.join(ROOT, "include", "cmcd_hip_diag.h")]
 # Per-file flags.  cmcd_kernels.hip holds the wave-per-tile trajectory kernel, which is VALU-issue bound at 4 waves per
 # SIMD: there a packed fp32 instruction holds the pipe ~1.8x as long as a plain one and the SLP vectoriser pays v_mov
@@ -79,7 +79,7 @@ def build(force=False, verbose=False):
 
 
 BOUNDARY_LIB = os.path.join(HERE, "libcmcd_hip_boundary.so")
-HOOK_SOURCES = ("cmcd_kernels.hip", "cmcd_coop.hip", "cmcd_uha.hip")     # the translation units that define hooks of cmcd_hip_diag.h
+HOOK_SOURCES = ("cmcd_api.hip", "cmcd_coop.hip", "cmcd_uha.hip")     # the translation units that define hooks of cmcd_hip_diag.h
 
 
 def build_boundary_only(force=False):

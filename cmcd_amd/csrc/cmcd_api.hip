@@ -1,0 +1,677 @@
+// libcmcd_hip.so — the C ABI of include/cmcd_hip.h and the hooks of include/cmcd_hip_diag.h.  Host code only: every kernel is
+// launched through its own file's launcher (cmcd_host.h for cmcd_kernels.hip, cmcd_common.h for the others).
+//
+// One call = validate -> plan (CallPlan: effective descriptor + workspace carve-up) -> prep tables -> choose and launch the
+// trajectory kernel -> merge the statistics (-> reverse sweep, for the gradient entry points).  All on the caller's stream,
+// no host sync.  The size queries are the same plan, built for the largest target-constant block.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "cmcd_common.h"
+#include "cmcd_hip.h"
+#include "cmcd_hip_diag.h"
+#include "cmcd_host.h"
+
+namespace cmcd {
+
+static thread_local char g_err[512] = "";
+static thread_local char g_kernel_name[96] = "";   // cmcd_last_kernel_name
+
+// Optional in-library timing of the trajectory kernel: when enabled, every cmcd_bound_forward
+// brackets its traj_kernel launch with a hipEvent pair on the caller's stream (bench.py reads
+// the average kernel duration from them for the roofline figure).
+struct ProfileState {
+  static constexpr int kMax = 4096;
+  bool on = false;
+  bool open = false;   // profile_begin recorded the start event of pair `used`
+  int used = 0;
+  hipEvent_t ev[kMax][2];
+  int created = 0;
+};
+static thread_local ProfileState g_prof;
+// cmcd_debug_capture_noise: armed per host thread, consumed (and cleared) by the next forward call on that thread
+struct NoiseCapture { uint32_t* bits = nullptr; uint32_t* keys = nullptr; float* noise = nullptr; };
+static thread_local NoiseCapture g_capture;
+
+int fail(int code, const char* fmt, const char* a, long long b) {
+  snprintf(g_err, sizeof(g_err), fmt, a, b);
+  return code;
+}
+int fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
+
+// the profile's event pair around the trajectory launch (when cmcd_profile_enable is on): profile_begin right in front of the
+// launch, profile_end behind it; a launch that fails in between leaves no record
+static int profile_begin(hipStream_t stream) {
+  g_prof.open = g_prof.on && g_prof.used < ProfileState::kMax;
+  if (!g_prof.open) return CMCD_OK;
+  if (g_prof.used >= g_prof.created) {
+    CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][0]));
+    CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][1]));
+    ++g_prof.created;
+  }
+  CMCD_HIP_CHECK(hipEventRecord(g_prof.ev[g_prof.used][0], stream));
+  return CMCD_OK;
+}
+static int profile_end(hipStream_t stream) {
+  if (!g_prof.open) return CMCD_OK;
+  g_prof.open = false;
+  CMCD_HIP_CHECK(hipEventRecord(g_prof.ev[g_prof.used][1], stream));
+  ++g_prof.used;
+  return CMCD_OK;
+}
+// traj_launch calls this once its checks have passed, right in front of the kernel launch
+static int traj_before_launch(hipStream_t stream) {
+  const int rc = profile_begin(stream);
+  if (rc == CMCD_OK) snprintf(g_kernel_name, sizeof(g_kernel_name), "traj_kernel");
+  return rc;
+}
+
+// Tiles (16 particles each) up to which the CU-cooperative kernel is preferred; measured crossovers on
+// MI355X (tools/probes/variant_sweep.py, t9_variants.py): dds/geffner T<=4 between 512 and 1024 tiles; the 132-wide
+// net at ~600 (500 tiles: cooperative 1.85 ms against 2.27 ms one wave per tile; 1000 tiles: 3.69 against 2.28).
+// r02, after the cooperative kernel's per-bridge time dropped by a sixth (tools/probes/variant_crossover.py,
+// profiles/r02_s2e_variant_crossover.txt; the cooperative time is ceil(tiles / 256 CUs) rounds of one workgroup per CU):
+//   dds net, 40-mode mixture:     cooperative wins through 6 rounds (1536 tiles: 1.13 against 1.34 ms; 2048: 1.42 / 1.34)
+//   132-wide net, 40-mode mixture: through 3 rounds (768 tiles: 1.91 against 2.31 ms; 813: 2.53 / 2.29)
+//   funnel / gmm on the narrow geffner nets: 512 tiles still (768: 0.373 / 0.314 ms and 0.0257 / 0.0246 ms)
+static int coop_max_tiles(const cmcd_desc& d, int T) {
+  if (d.target == CMCD_TARGET_MANY_GMM && d.dim == 2) {
+    if (d.arch == CMCD_ARCH_DDS) return 1536;
+    if (T == 9) return 768;
+  }
+  return 512;
+}
+
+static inline int64_t align4(int64_t x) { return (x + 3) & ~int64_t(3); }
+
+static bool hidden_width(const cmcd_desc& d, int& HP) {
+  if (d.arch == CMCD_ARCH_DDS) { HP = 64; return true; }
+  if (d.arch == CMCD_ARCH_GEFFNER) {
+    if (d.emb_dim < 1) return false;
+    HP = ((net_in_dim(d) + d.emb_dim + 15) / 16) * 16;
+    if (d.mode == CMCD_MODE_CAIS_UHA_SN && d.target != CMCD_TARGET_LGCP) {
+      // 2nd-order CMCD has its own kernels (cmcd_uha.hip): instances of 2, 4, 5 and 9 neuron tiles (gmm 2*2+20 = 24,
+      // funnel 2*10+48 = 68, the 40-mode mixture 2*2+130 = 134), other widths zero-padded to the next one
+      const int T = HP / 16;
+      HP = 16 * (T <= 2 ? 2 : (T <= 4 ? 4 : (T <= 5 ? 5 : (T <= 9 ? 9 : T))));
+      return true;
+    }
+    // Kernel instances exist for 2, 4 and 9 neuron tiles (the BASELINE widths 22 / 58 / 132); any other width runs
+    // on the next larger instance with zero-padded weights: a padded unit has no outgoing weight, so it cannot
+    // reach the output, and its gradient entries are never copied out.  (lgcp has its own path: any width.)
+    if (d.target != CMCD_TARGET_LGCP) {
+      const int T = HP / 16;
+      // funnel (d = 10): its gradient kernels start at 4 tiles, and forward / gradient share one workspace layout
+      const int tmin = d.target == CMCD_TARGET_FUNNEL ? 4 : 2;
+      HP = 16 * (T <= tmin ? tmin : (T <= 4 ? 4 : (T <= 9 ? 9 : T)));
+    }
+    return true;
+  }
+  return false;
+}
+
+// width of the state part of the network input: z, or concat(z, rho) for the momentum mode (rho_dim = dim,
+// the reference's src/mcdboundingmachine.py:82-98)
+int net_in_dim(const cmcd_desc& d) { return d.mode == CMCD_MODE_CAIS_UHA_SN ? 2 * d.dim : d.dim; }
+
+// floats of the trajectory a gradient call keeps: z_0..z_K, plus rho_0..rho_K and rho'_0..rho'_{K-1} for the momentum mode
+static int64_t kept_traj_floats(const cmcd_desc& d, int64_t n) {
+  return (int64_t)(d.mode == CMCD_MODE_CAIS_UHA_SN ? 3 * d.nbridges + 2 : d.nbridges + 1) * n * d.dim;
+}
+
+// the schedule tables every layout starts with -> their floats
+static int64_t sched_tables(int64_t K, WsLayout& w) {
+  int64_t o = 0;
+  w.beta = o; o += align4(K);
+  w.eps = o; o += align4(K);
+  w.sig = o; o += align4(K);
+  w.logsig = o; o += align4(K);
+  w.sched = o; o += 8 * K;
+  return o;
+}
+
+// lgcp: only the schedule tables live in the common layout; the rest is carved by cmcd_lgcp.hip
+static void make_ws_lgcp(const cmcd_desc& d, int64_t n, WsLayout& w) {
+  memset(&w, 0, sizeof(w));
+  w.total_floats = sched_tables(d.nbridges, w);
+  w.n_waves = (int32_t)n;  // one statistics record per particle
+}
+
+static bool make_ws(const cmcd_desc& d, int64_t n, int64_t n_target, WsLayout& w) {
+  int HP;
+  if (!hidden_width(d, HP)) return false;
+  const int64_t K = d.nbridges, D = d.dim;
+  w.HP = HP;
+  w.T = HP / 16;
+  int64_t o = sched_tables(K, w);
+  w.bias1 = o; o += (K + 1) * HP;
+  if (d.arch == CMCD_ARCH_GEFFNER) { w.utab = o; o += (K + 1) * HP; } else { w.utab = w.bias1; }
+  w.w1z = o; o += int64_t(net_in_dim(d)) * HP;
+  w.w2 = o; o += int64_t(HP) * HP;
+  w.w2t = o; o += int64_t(HP) * HP;
+  w.w2q = o; o += 2 * int64_t(HP) * HP;
+  w.b2 = o; o += HP;
+  w.w3t = o; o += D * HP;
+  w.b3 = o; o += 16;
+  w.tgt_floats = d.target == CMCD_TARGET_MANY_GMM ? align4(4 + (n_target - 1)) : 0;   // staged for LDS: header + means
+  w.tgt = o; o += w.tgt_floats;
+  o = (o + 1) & ~int64_t(1);
+  w.n_waves = int32_t((n + 15) / 16);
+  // sized for the cooperative kernel's 8-particle tiles (twice the records of the 16-particle tiling)
+  w.partials = o; o += int64_t((n + 7) / 8) * CMCD_NSTATS * 2;
+  w.total_floats = o;
+  return true;
+}
+
+// What a set of prepared tables was formed from, as far as the library can know it without reading device memory: FNV-1a
+// over the descriptor (minus the kernel-variant field, which selects a kernel and not a table), the layout and the sizes.
+// The caller's descriptor, not the plan's effective one.
+static uint32_t tables_stamp(const cmcd_desc& d, const cmcd_layout& lay, int64_t n, int64_t n_params, int64_t n_target) {
+  uint32_t h = 2166136261u;
+  auto eat = [&](const void* p, size_t len) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < len; ++i) { h ^= b[i]; h *= 16777619u; }
+  };
+  cmcd_desc dd = d;
+  dd.reserved = 0;
+  eat(&dd, sizeof dd); eat(&lay, sizeof lay); eat(&n, sizeof n); eat(&n_params, sizeof n_params); eat(&n_target, sizeof n_target);
+  return h ? h : 1u;
+}
+
+static int check_desc(const cmcd_desc* d) {
+  if (!d) return fail(CMCD_ERR_BAD_ARG, "null desc%s");
+  if (d->mode < CMCD_MODE_CAIS_SN || d->mode > CMCD_MODE_CAIS_UHA_SN)
+    return fail(CMCD_ERR_UNSUPPORTED, "Mode not implemented.%s");
+  if (d->mode == CMCD_MODE_ULA && d->arch != CMCD_ARCH_DDS)
+    return fail(CMCD_ERR_BAD_ARG, "MCD_ULA has no network: pass arch = CMCD_ARCH_DDS as the placeholder%s");
+  if (d->arch != CMCD_ARCH_DDS && d->arch != CMCD_ARCH_GEFFNER)
+    return fail(CMCD_ERR_UNSUPPORTED, "nn_arch not implemented%s");
+  if (d->nbridges < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges must be >= 1%s");
+  if (d->ngrid < 1 || d->ngrid > 32) return fail(CMCD_ERR_BAD_ARG, "ngrid must be in [1, 32]%s");
+  if (d->eps_schedule == CMCD_EPS_LINEAR && d->nbridges < 2)
+    return fail(CMCD_ERR_BAD_ARG, "linear eps schedule needs nbridges >= 2%s");
+  int HP;
+  if (!hidden_width(*d, HP)) return fail(CMCD_ERR_BAD_ARG, "bad emb_dim%s");
+  if (d->target == CMCD_TARGET_LGCP) {
+    if ((d->arch != CMCD_ARCH_GEFFNER && d->mode != CMCD_MODE_ULA) || d->dim < 4 || d->dim > 4096)
+      return fail(CMCD_ERR_UNSUPPORTED, "lgcp runs with the geffner net only%s");
+    return CMCD_OK;
+  }
+  if (d->mode == CMCD_MODE_CAIS_UHA_SN) {
+    if (!uha_available(*d, HP / 16))
+      return fail(CMCD_ERR_UNSUPPORTED, "no MCD_CAIS_UHA_sn kernel instance for this (target, dim, arch, width=%s%lld)", "", HP);
+    return CMCD_OK;
+  }
+  if (!traj_available(*d, HP / 16))
+    return fail(CMCD_ERR_UNSUPPORTED, "no kernel instance for this (target, dim, arch, width=%s%lld)", "", HP);
+  return CMCD_OK;
+}
+
+static int check_workspace(const void* ptr, int64_t bytes, int64_t need) {
+  if (bytes < need || (reinterpret_cast<uintptr_t>(ptr) & 15))
+    return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
+  return CMCD_OK;
+}
+
+// many_gmm: target_consts = {scale, means[n_mixes][2]} (any other target: nothing to check here)
+static int check_many_gmm(const cmcd_desc& d, const float* target_consts, int64_t n_target) {
+  if (d.target == CMCD_TARGET_MANY_GMM &&
+      (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64))
+    return fail(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}%s");
+  return CMCD_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the plan of one call: what runs (effective descriptor) and where it lives in the caller's workspace
+//   forward:     [forward tables + statistics records]
+//   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
+//   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
+// ------------------------------------------------------------------------------------------
+enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD };
+
+struct CallPlan {
+  cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
+  WsLayout w;
+  int n_mix;
+  bool lgcp;
+  bool item;        // gradient on work items (small batches) instead of whole chains
+  bool keep;        // the forward pass leaves its trajectory at `traj`
+  int64_t fwd;      // floats of the forward part (what a forward-only call demands)
+  int64_t gfl, traj, scratch;   // float offsets of the gradient workspace, the kept trajectory and the work-item scratch
+  int64_t total;    // bytes of this layout = what the size query of `kind` answers
+  int64_t need;     // bytes the entry point demands: total, except that the VarGrad calls demand their size query's answer
+};
+
+// query: the plan of a size query — n_target is not read, the target block is the largest the target can stage (64 mixtures)
+static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKind kind, bool query, CallPlan& p) {
+  cmcd_desc& d = p.d = desc;
+  // the overdamped baselines: constant eps, no clipping (the reference's dispatcher passes neither, mcd_utils.py:35-58)
+  if (d.mode == CMCD_MODE_ULA || d.mode == CMCD_MODE_ULA_SN) { d.eps_schedule = CMCD_EPS_CONST; d.grad_clipping = 0; }
+  // MCD_CAIS_UHA_sn: the cos^2 schedule and the clip are fixed by the function body (mcd_under_lp_a_cais.py:23-48)
+  if (d.mode == CMCD_MODE_CAIS_UHA_SN) { d.eps_schedule = CMCD_EPS_COS_SQ; d.grad_clipping = 1; }
+  const bool many = d.target == CMCD_TARGET_MANY_GMM;
+  if (query) n_target = many ? 1 + 2 * 64 : 0;
+  p.n_mix = many ? int((n_target - 1) / 2) : 0;
+  p.lgcp = d.target == CMCD_TARGET_LGCP;
+  p.item = p.keep = false, p.gfl = p.traj = p.scratch = 0;
+  if (p.lgcp) {
+    make_ws_lgcp(d, n, p.w);
+    p.fwd = lgcp_workspace_floats(d, n, p.w.total_floats);
+  } else {
+    if (!make_ws(d, n, n_target, p.w)) return fail(CMCD_ERR_BAD_ARG, "bad descriptor%s");
+    p.fwd = p.w.total_floats;
+  }
+  p.total = p.need = p.fwd * 4;
+  if (kind == PLAN_FORWARD) return CMCD_OK;
+
+  const WsLayout& w = p.w;
+  int64_t gws, traj_fl = kept_traj_floats(d, n), scratch_fl = 0;
+  if (kind == PLAN_VAR_GRAD) {   // the local (stop_gradient) gradient: no mode check here, the size query answers for any mode
+    if (p.lgcp) {                // the reverse launch sequence with z detached, on the trajectory cmcd_bound_var_forward left
+      gws = lgcp_grad_workspace_floats(d, n);
+    } else {
+      const int64_t zs = (int64_t)(d.nbridges + 1) * n * d.dim;
+      if (!grad_available(d, w.T)) return fail(CMCD_ERR_UNSUPPORTED, "no gradient kernel instance for this (target, dim, arch, width)%s");
+      gws = grad_workspace_floats(d, w.HP, n);
+      p.item = grad_item_mode(d, w.T, n);
+      // only the work-item path reads the trajectory; without cmcd_bound_var_forward it runs the forward launch sequence
+      // once more, with its loss, z and statistics in the scratch
+      traj_fl = p.item ? align4(zs) : 0;
+      scratch_fl = p.item ? align4(n) + align4(n * d.dim) + 16 : 0;
+    }
+  } else if (p.lgcp) {           // launch-sequence forward (trajectory kept) + launch-sequence reverse sweep (cmcd_lgcp.hip)
+    if (d.mode == CMCD_MODE_CAIS_VAR_SN)
+      return fail(CMCD_ERR_UNSUPPORTED, "MCD_CAIS_var_sn: cmcd_grad_workspace_bytes / cmcd_bound_var_forward / cmcd_bound_var_grad_kept%s");
+    gws = lgcp_grad_workspace_floats(d, n);
+  } else if (d.mode == CMCD_MODE_ULA) {           // no network: the network-free reverse sweep
+    if (!ula_grad_available(d)) return fail(CMCD_ERR_UNSUPPORTED, "no MCD_ULA gradient instance for this target%s");
+    gws = ula_grad_workspace_floats(d, n);
+  } else if (d.mode == CMCD_MODE_CAIS_UHA_SN) {   // (z, rho, rho') kept + its reverse sweep (cmcd_uha.hip)
+    if (!uha_grad_available(d, w.T)) return fail(CMCD_ERR_UNSUPPORTED, "no MCD_CAIS_UHA_sn gradient instance for this (target, dim, arch, width)%s");
+    gws = uha_grad_workspace_floats(d, w.HP, n);
+  } else {
+    if ((d.mode != CMCD_MODE_CAIS_SN && d.mode != CMCD_MODE_ULA_SN) || !bptt_available(d, w.T))
+      return fail(CMCD_ERR_UNSUPPORTED, query ? "no reparameterised-gradient kernel instance for this (mode, target, dim, arch, width)%s"
+                                              : "no reparameterised-gradient kernel instance for this (target, dim, arch, width)%s");
+    gws = grad_workspace_floats(d, w.HP, n);
+    p.item = grad_item_mode(d, w.T, n);
+    traj_fl = align4(traj_fl);
+    scratch_fl = p.item ? bptt_item_floats(d, n) : 0;
+  }
+  p.keep = traj_fl > 0;
+  p.gfl = align4(p.fwd);
+  p.traj = p.gfl + align4(gws);
+  p.scratch = p.traj + traj_fl;
+  p.total = p.need = (p.scratch + scratch_fl) * 4;
+  if (kind == PLAN_VAR_GRAD && many && !query) {   // the layout is this call's, the demand is the size query's
+    CallPlan q;
+    make_plan(desc, n, 0, kind, true, q);
+    p.need = q.total;
+  }
+  return CMCD_OK;
+}
+
+static int64_t plan_bytes(const cmcd_desc* desc, int64_t n, PlanKind kind) {
+  CallPlan p;
+  if (check_desc(desc) != CMCD_OK || n < 1 || make_plan(*desc, n, 0, kind, true, p) != CMCD_OK) return 0;
+  return p.total;
+}
+
+// outer: the plan of the gradient entry point this forward pass belongs to (its trajectory is kept where that plan says)
+static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                        void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z, double* out_stats,
+                        void* stream_, bool tables_ready = false, const CallPlan* outer = nullptr) {
+  // 1. validate
+  const NoiseCapture cap = g_capture;   // armed by cmcd_debug_capture_noise: this call consumes it, whatever happens
+  g_capture = NoiseCapture{};
+  int rc = check_desc(desc);
+  if (rc != CMCD_OK) return rc;
+  if ((cap.bits || cap.keys) && desc->target == CMCD_TARGET_LGCP)
+    return fail(CMCD_ERR_UNSUPPORTED, "cmcd_debug_capture_noise: trajectory kernels only (not the lgcp launch sequence)%s");
+  if (!lay || !seeds || !params || !workspace || !out_loss || !out_z || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  const cmcd_desc& d = *desc;
+  const int64_t K = d.nbridges, D = d.dim, E = d.emb_dim, DIN = net_in_dim(d), IN = DIN + E;
+  const bool uha = d.mode == CMCD_MODE_CAIS_UHA_SN;
+
+  // every leaf this configuration reads must lie inside params_flat
+  auto need = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
+  bool ok = need(lay->vd_mean, D) && need(lay->vd_logdiag, D) && need(lay->eps, 1) &&
+            need(lay->mgridref_y, d.ngrid + 1) && (!uha || need(lay->gamma, 1));
+  if (d.mode == CMCD_MODE_ULA) {
+    // no network leaves
+  } else if (d.arch == CMCD_ARCH_GEFFNER)
+    ok = ok && need(lay->g_emb, K * E) && need(lay->g_factor, 1) && need(lay->g_w1, IN * IN) &&
+         need(lay->g_b1, IN) && need(lay->g_w2, IN * IN) && need(lay->g_b2, IN) && need(lay->g_w3, IN * D) &&
+         need(lay->g_b3, D);
+  else
+    ok = ok && need(lay->d_phase, 64) && need(lay->d_tw1, 128 * 64) && need(lay->d_tb1, 64) &&
+         need(lay->d_tw2, 64 * 64) && need(lay->d_tb2, 64) && need(lay->d_sw1, (DIN + 64) * 64) &&
+         need(lay->d_sb1, 64) && need(lay->d_sw2, 64 * 64) && need(lay->d_sb2, 64) &&
+         need(lay->d_sw3, 64 * D) && need(lay->d_sb3, D);
+  if (!ok) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if (d.target == CMCD_TARGET_LGCP && (!target_consts || n_target != D * D + D + 3))
+    return fail(CMCD_ERR_BAD_ARG, "lgcp needs target_consts = {Kinv[d,d], counts[d], mu0, a, lognorm}%s");
+
+  // 2. plan
+  CallPlan own;
+  if (!outer) {
+    if ((rc = make_plan(d, n, n_target, PLAN_FORWARD, false, own)) != CMCD_OK) return rc;
+    outer = &own;
+  }
+  const CallPlan& p = *outer;
+  const cmcd_desc& e = p.d;
+  const WsLayout& w = p.w;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.fwd * 4)) != CMCD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  float* traj = p.keep ? ws + p.traj : nullptr;
+
+  // 3. prep.  cmcd_bound_forward_prepared: the caller vouches that the workspace still holds the tables a previous call formed
+  // from the SAME (desc, layout, params, target constants, n): the prep launch (4.8 us + a kernel boundary per call) is
+  // skipped, and whoever writes the statistics compares the stamp the forming call left (b3[13]; lgcp: sched[0][7]) with
+  // this call's (finalize_kernel).  The 2nd-order lgcp sequence has no prepared form.
+  const bool ready = tables_ready && !(p.lgcp && uha);
+  const uint32_t stamp = tables_stamp(d, *lay, n, n_params, n_target);
+  if (!ready) {
+    if (p.lgcp) launch_prep_sched(e, *lay, w, params, ws, stream, stamp);   // the rest of lgcp's tables: lgcp_forward
+    else launch_prep(e, *lay, w, params, target_consts, p.n_mix, ws, stream, stamp);
+  }
+  const uint32_t* stamp_slot = ready ? reinterpret_cast<const uint32_t*>(ws + (p.lgcp ? w.sched + 7 : w.b3 + 13)) : nullptr;
+
+  // 4. choose and launch: every branch leaves `records` statistics records at `partials`, or has merged them itself
+  double* partials = reinterpret_cast<double*>(ws + w.partials);
+  int records = w.n_waves;
+  bool merged = false;
+  TrajArgs ta{seeds, params, ws, partials, out_loss, out_z, *lay, w, n, (int32_t)K, d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0,
+              e.grad_clipping, traj, d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
+  ta.dbg_bits = cap.bits; ta.dbg_keys = cap.keys; ta.dbg_noise = cap.noise;
+  if (p.lgcp) {
+    snprintf(g_kernel_name, sizeof(g_kernel_name), "%s", lgcp_use_wide(e, n, traj != nullptr)
+                 ? "lgcp wide-batch sequence (32x128-tile fp32 GEMM launches)"
+                 : "lgcp launch sequence (skinny GEMMs + state kernels)");
+    // gradient calls (traj set) hand over the gradient workspace: the forward's consumers keep their activations in its
+    // tables, so that the reverse sweep does not recompute them (cmcd_lgcp.hip: lgcp_keep)
+    rc = lgcp_forward(e, *lay, w, seeds, n, params, target_consts, ws, out_loss, out_z, &partials, traj, stream_, ready,
+                      traj ? ws + p.gfl : nullptr);
+    if (rc != CMCD_OK) return fail(rc, "lgcp launch sequence failed%s");
+    records = (int)n;
+  } else if (uha) {   // 2nd-order CMCD: its own trajectory kernel (cmcd_uha.hip), same prep tables and statistics merge
+    rc = uha_forward_launch(e, ta, stream, &records);
+    snprintf(g_kernel_name, sizeof(g_kernel_name), "%s", uha_last_kernel_name());
+    if (rc != CMCD_OK) return fail(rc, "MCD_CAIS_UHA_sn launch failed%s");
+  } else {
+    // Kernel variant (desc.reserved: 0 auto, 1 wave-per-tile, 2 CU-cooperative, 3 cooperative on 16-particle tiles,
+    // 4 cooperative on 8-particle tiles).  Auto: the cooperative kernel while the batch cannot fill the chip with one
+    // wave per tile, on 8-particle tiles while those still get a CU each (n <= 8 x 256).
+    const bool coop_ok = coop_available(d, w.T) && d.mode != CMCD_MODE_ULA;
+    const bool forced = d.reserved >= 2 && d.reserved <= 5;
+    const bool use_coop = forced ? coop_ok : (d.reserved == 1 ? false : (coop_ok && w.n_waves <= coop_max_tiles(d, w.T)));
+    if (forced && !coop_ok) return fail(CMCD_ERR_UNSUPPORTED, "no cooperative kernel instance%s");
+    const bool half_ok = coop_half_available(d, w.T);
+    if ((d.reserved == 4 || d.reserved == 5) && !half_ok) return fail(CMCD_ERR_UNSUPPORTED, "no 8-particle-tile cooperative instance%s");
+    const bool half = d.reserved == 4 || d.reserved == 5 || (d.reserved != 3 && half_ok && n <= 8 * 256);
+    const bool wide8 = half && d.reserved != 5 && coop_wide8_available(d, w.T);   // d = 10: the dealt-coordinates kernel (5 = the narrow form, A / B)
+    if (use_coop) {
+      // Small grids (<= 64 workgroups: the launch-bound configurations — gmm / funnel at N = 300 are 38 workgroups): the
+      // statistics are merged by the last workgroup to arrive (its counter: the free slot 14 of the b3 row, zeroed by the prep
+      // launch of this call) and the finalize launch is dropped: gmm N = 300, K = 8 0.0266 -> 0.0245 ms per call.  Larger
+      // grids keep the finalize launch: at the named batch's 250 workgroups the merge tail costs the trajectory kernel what
+      // the launch saves (per call 0.2026 vs 0.2024 ms).  Same five doubles bit for bit either way.
+      records = int(half ? (n + 7) / 8 : w.n_waves);
+      merged = records <= 64;
+      if ((rc = profile_begin(stream)) != CMCD_OK) return rc;
+      snprintf(g_kernel_name, sizeof(g_kernel_name), "%s<%d-particle tiles%s>", wide8 ? "coop_wide8_kernel" : "coop_kernel",
+               half ? 8 : 16, w.T == 9 ? ", 132-wide net" : "");
+      if (merged) {
+        ta.fin_out = out_stats;
+        ta.fin_counter = reinterpret_cast<int32_t*>(ws + w.b3 + 14);
+        ta.stamp_slot = stamp_slot;
+        ta.stamp_expect = stamp;
+      }
+      rc = coop_launch(e, ta, half, stream, !wide8);
+      if (rc != CMCD_OK) return fail(rc, "cooperative launch failed%s");
+    } else if ((rc = traj_launch(e, w, ta, stream, traj_before_launch)) != CMCD_OK) {
+      return rc;
+    }
+    if ((rc = profile_end(stream)) != CMCD_OK) return rc;
+  }
+
+  // 5. merge the statistics
+  if (!merged) launch_finalize(partials, records, out_stats, stream, stamp_slot, stamp);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+// the VarGrad gradient on the tables (and, for work items and lgcp, the trajectory) in the workspace; kept: left there by
+// cmcd_bound_var_forward, otherwise formed here
+static int var_grad_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                         const float* omega, void* workspace, int64_t workspace_bytes, float* grad, bool kept,
+                         void* stream_) {
+  int rc = check_desc(desc);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !seeds || !params || !omega || !workspace || !grad) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (desc->mode != CMCD_MODE_CAIS_VAR_SN)
+    return fail(CMCD_ERR_UNSUPPORTED, "the local (stop_gradient) gradient exists for MCD_CAIS_var_sn only%s");
+  const cmcd_desc& d = *desc;
+  if (d.target == CMCD_TARGET_LGCP && !kept)
+    return fail(CMCD_ERR_UNSUPPORTED, "lgcp: call cmcd_bound_var_forward, then cmcd_bound_var_grad_kept on the same workspace%s");
+  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  CallPlan p;
+  if ((rc = make_plan(d, n, n_target, PLAN_VAR_GRAD, false, p)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
+  float* ws = static_cast<float*>(workspace);
+  float* traj = p.keep ? ws + p.traj : nullptr;
+  if (p.lgcp) {
+    rc = lgcp_grad(d, *lay, p.w, n, params, n_params, target_consts, ws, traj, ws + p.gfl, 0.f, omega, false, grad, stream_);
+    return rc != CMCD_OK ? fail(rc, "lgcp gradient launch sequence failed%s") : CMCD_OK;
+  }
+  if (p.item && !kept) {   // the forward launch sequence once more, keeping z_0..z_K
+    float* sl = ws + p.scratch;
+    float* sz = sl + align4(n);
+    double* sst = reinterpret_cast<double*>(sz + align4(n * d.dim));
+    rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, sl, sz, sst,
+                      stream_, false, &p);
+    if (rc != CMCD_OK) return rc;
+  } else if (!kept) {
+    launch_prep(p.d, *lay, p.w, params, target_consts, p.n_mix, ws, static_cast<hipStream_t>(stream_),
+                tables_stamp(d, *lay, n, n_params, n_target));
+  }
+  rc = grad_launch(d, *lay, p.w, seeds, n, params, n_params, ws, omega, 0.f, false, p.item, traj, nullptr, ws + p.gfl, grad,
+                   stream_);
+  return rc != CMCD_OK ? fail(rc, "gradient launch failed%s") : CMCD_OK;
+}
+
+}  // namespace cmcd
+
+using namespace cmcd;
+
+extern "C" {
+
+int cmcd_version(void) { return CMCD_ABI_VERSION; }
+const char* cmcd_last_error(void) { return g_err; }
+
+int64_t cmcd_target_floats(const cmcd_desc* desc, int32_t n_mixes) {
+  if (!desc) return -1;
+  switch (desc->target) {
+    case CMCD_TARGET_GMM:
+    case CMCD_TARGET_FUNNEL: return 0;
+    case CMCD_TARGET_MANY_GMM: return 1 + 2 * (int64_t)n_mixes;
+    case CMCD_TARGET_LGCP: return (int64_t)desc->dim * desc->dim + desc->dim + 3;
+    default: return -1;
+  }
+}
+
+int64_t cmcd_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_FORWARD); }
+int64_t cmcd_grad_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_VAR_GRAD); }
+int64_t cmcd_bound_grad_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_BOUND_GRAD); }
+
+int cmcd_bound_forward(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                       const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                       void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
+                       double* out_stats, void* stream_) {
+  return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
+                      out_loss, out_z, out_stats, stream_);
+}
+
+int cmcd_bound_forward_prepared(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                                const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                                void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
+                                double* out_stats, void* stream_) {
+  return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
+                      out_loss, out_z, out_stats, stream_, true);
+}
+
+int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                    const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                    float omega, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
+                    double* out_stats, float* grad, void* stream_) {
+  int rc = check_desc(desc);
+  if (rc != CMCD_OK) return rc;
+  if (!grad) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (desc->mode != CMCD_MODE_CAIS_SN && desc->mode != CMCD_MODE_ULA_SN && desc->mode != CMCD_MODE_ULA &&
+      desc->mode != CMCD_MODE_CAIS_UHA_SN)
+    return fail(CMCD_ERR_UNSUPPORTED, "the reparameterised gradient exists for MCD_CAIS_sn, MCD_CAIS_UHA_sn and MCD_ULA[_sn] (MCD_CAIS_var_sn: cmcd_bound_var_grad)%s");
+  CallPlan p;
+  if ((rc = make_plan(*desc, n, n_target, PLAN_BOUND_GRAD, false, p)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
+  // forward with the trajectory kept, then the reverse sweep of the mode
+  rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_loss,
+                    out_z, out_stats, stream_, false, &p);
+  if (rc != CMCD_OK) return rc;
+  const cmcd_desc& d = p.d;
+  float* ws = static_cast<float*>(workspace);
+  float* traj = ws + p.traj;
+  float* gws = ws + p.gfl;
+  if (p.lgcp) {
+    rc = lgcp_grad(d, *lay, p.w, n, params, n_params, target_consts, ws, traj, gws, omega, nullptr, true, grad, stream_);
+    return rc != CMCD_OK ? fail(rc, "lgcp gradient launch sequence failed%s") : CMCD_OK;
+  }
+  if (d.mode == CMCD_MODE_ULA)
+    rc = ula_grad_launch(d, *lay, p.w, n, params, n_params, ws, traj, gws, omega, grad, stream_);
+  else if (d.mode == CMCD_MODE_CAIS_UHA_SN)
+    rc = uha_grad_launch(d, *lay, p.w, n, params, n_params, ws, traj, gws, omega, grad, stream_);
+  else
+    rc = grad_launch(d, *lay, p.w, seeds, n, params, n_params, ws, nullptr, omega, true, p.item, traj,
+                     p.item ? ws + p.scratch : nullptr, gws, grad, stream_);
+  return rc != CMCD_OK ? fail(rc, "gradient launch failed%s") : CMCD_OK;
+}
+
+int cmcd_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
+                         void* stream_) {
+  if (!loss || !stats || !omega || n < 1 || n_total < n) return fail(CMCD_ERR_BAD_ARG, "bad argument%s");
+  launch_vargrad_weights(loss, stats, n, n_total, omega, static_cast<hipStream_t>(stream_));
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+int cmcd_bound_var_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                        const float* omega, void* workspace, int64_t workspace_bytes, float* grad, void* stream_) {
+  return var_grad_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, omega, workspace,
+                       workspace_bytes, grad, false, stream_);
+}
+
+int cmcd_bound_var_forward(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                           const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                           void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
+                           double* out_stats, void* stream_) {
+  int rc = check_desc(desc);
+  if (rc != CMCD_OK) return rc;
+  if (desc->mode != CMCD_MODE_CAIS_VAR_SN)
+    return fail(CMCD_ERR_UNSUPPORTED, "the local (stop_gradient) gradient exists for MCD_CAIS_var_sn only%s");
+  CallPlan p;   // (no gradient instance, or no particles: the size query answers 0)
+  if (n < 1 || make_plan(*desc, n, n_target, PLAN_VAR_GRAD, false, p) != CMCD_OK) return CMCD_ERR_UNSUPPORTED;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
+  return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_loss,
+                      out_z, out_stats, stream_, false, &p);
+}
+
+int cmcd_bound_var_grad_kept(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
+                             const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                             const float* omega, void* workspace, int64_t workspace_bytes, float* grad,
+                             void* stream_) {
+  return var_grad_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, omega, workspace,
+                       workspace_bytes, grad, true, stream_);
+}
+
+int cmcd_stats_merge_device(const double* rows, int32_t count, double* out5, void* stream_) {
+  if (!rows || !out5 || count < 1) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  launch_finalize(rows, count, out5, static_cast<hipStream_t>(stream_), nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+int cmcd_stats_merge(const double* stats, const int64_t* n_per, int32_t count, double* merged5, double* out3) {
+  if (!stats || !n_per || count < 1 || !merged5 || !out3) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  double acc[CMCD_NSTATS] = {0, 0, 0, -INFINITY, 0};
+  int64_t n = 0;
+  for (int i = 0; i < count; ++i) {
+    const double* b = stats + (int64_t)i * CMCD_NSTATS;
+    acc[0] += b[0]; acc[1] += b[1]; acc[2] += b[2];
+    const double m = fmax(acc[3], b[3]);
+    const double sa = (acc[3] > -INFINITY && m < INFINITY) ? acc[4] * exp(acc[3] - m) : (acc[3] == m ? acc[4] : 0.0);
+    const double sb = (b[3] > -INFINITY && m < INFINITY) ? b[4] * exp(b[3] - m) : (b[3] == m ? b[4] : 0.0);
+    acc[3] = m; acc[4] = sa + sb;
+    n += n_per[i];
+  }
+  if (n < 1) return fail(CMCD_ERR_BAD_ARG, "no particles%s");
+  memcpy(merged5, acc, sizeof(acc));
+  const double mean = acc[1] / (double)n;
+  out3[0] = mean;
+  out3[1] = acc[2] / (double)n - mean * mean;        // var(ddof=0); inf - inf = NaN like the reference
+  out3[2] = acc[3] + log(acc[4]) - log((double)n);   // logsumexp(-l) - log n
+  return CMCD_OK;
+}
+
+#ifndef CMCD_NO_DIAG_HOOKS   // include/cmcd_hip_diag.h: compiled out of a boundary-only build
+const char* cmcd_last_kernel_name(void) { return g_kernel_name; }
+
+int cmcd_debug_capture_noise(uint32_t* bits, uint32_t* gen_keys, float* noise) {
+  if ((bits == nullptr) != (noise == nullptr)) return fail(CMCD_ERR_BAD_ARG, "bits and noise go together%s");
+  g_capture.bits = bits; g_capture.keys = gen_keys; g_capture.noise = noise;
+  return CMCD_OK;
+}
+
+int cmcd_debug_grad_item(int mode) {
+  if (mode < -1 || mode > 1) return fail(CMCD_ERR_BAD_ARG, "mode must be -1, 0 or 1%s");
+  set_grad_item_override(mode);
+  return CMCD_OK;
+}
+
+int cmcd_profile_enable(int on) {
+  g_prof.on = on != 0;
+  g_prof.used = 0;
+  // the first 512 event pairs are created here, outside any timed region (a 20-step measurement would otherwise pay two
+  // hipEventCreate calls inside every one of its steps)
+  for (; on && g_prof.created < 512; ++g_prof.created) {
+    CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][0]));
+    CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][1]));
+  }
+  return CMCD_OK;
+}
+
+int cmcd_profile_collect(double* total_ms, int64_t* launches) {
+  if (!total_ms || !launches) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  double tot = 0.0;
+  for (int i = 0; i < g_prof.used; ++i) {
+    float ms = 0.f;
+    CMCD_HIP_CHECK(hipEventSynchronize(g_prof.ev[i][1]));
+    CMCD_HIP_CHECK(hipEventElapsedTime(&ms, g_prof.ev[i][0], g_prof.ev[i][1]));
+    tot += ms;
+  }
+  *total_ms = tot;
+  *launches = g_prof.used;
+  g_prof.used = 0;
+  return CMCD_OK;
+}
+#endif   // CMCD_NO_DIAG_HOOKS
+
+}  // extern "C"

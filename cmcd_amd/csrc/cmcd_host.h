@@ -1,0 +1,39 @@
+// Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
+// trajectory and merge kernels with their launchers).  Not included by the other translation units: their seams are in
+// cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "cmcd_common.h"
+
+namespace cmcd {
+
+// cmcd_api.hip: sets this host thread's cmcd_last_error and returns `code`
+int fail(int code, const char* fmt, const char* a = "", long long b = 0);
+
+#define CMCD_HIP_CHECK(expr)                                                                   \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return fail(CMCD_ERR_HIP, "HIP error: %s (code %lld)", hipGetErrorString(e_), (long long)e_); \
+  } while (0)
+
+// cmcd_kernels.hip.  The launchers that return void leave their launch status to the caller's hipGetLastError.
+// `d` is the effective descriptor of the call (cmcd_api.hip: CallPlan).
+bool traj_available(const cmcd_desc& d, int T);   // a wave-per-tile traj_kernel instance exists for (target, dim, arch, T)
+// before_launch: called once the checks have passed, right in front of the kernel launch (the profile's start event); non-zero = give up
+int traj_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, hipStream_t stream,
+                int (*before_launch)(hipStream_t) = nullptr);
+// schedule tables + first-layer bias table + packed weights, one launch; stamp: tables_stamp() of the forming call
+void launch_prep(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, const float* params,
+                 const float* target_consts, int n_mix, float* ws, hipStream_t stream, uint32_t stamp);
+// the schedule tables alone (lgcp: the rest of its tables belongs to cmcd_lgcp.hip)
+void launch_prep_sched(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, const float* params, float* ws,
+                       hipStream_t stream, uint32_t stamp);
+// fixed-order merge of `count` statistics records -> out5; stamp_slot non-null: NaN unless *stamp_slot == stamp (prepared
+// form).  cmcd_common.h's four-argument launch_finalize (cmcd_mfvi.hip's call) is this one without a stamp.
+void launch_finalize(const double* partials, int32_t count, double* out5, hipStream_t stream, const uint32_t* stamp_slot,
+                     uint32_t stamp);
+void launch_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
+                            hipStream_t stream);
+
+}  // namespace cmcd

@@ -1,5 +1,5 @@
 // libcmcd_hip.so — hand-written gfx950 (CDNA4) kernels for CMCD's annealed-Langevin bound
-// (`MCD_CAIS_sn` / `MCD_CAIS_var_sn`) and the C ABI of include/cmcd_hip.h.
+// (`MCD_CAIS_sn` / `MCD_CAIS_var_sn`).  The C ABI of include/cmcd_hip.h that launches them is cmcd_api.hip (seams: cmcd_host.h).
 //
 // Launch sequence of one cmcd_bound_forward (all on the caller's stream, no host sync):
 //   1. prep_sched_kernel    betas / eps / sigma tables             (mcdboundingmachine.py:146-149,
@@ -26,139 +26,9 @@
 #include "cmcd_common.h"
 #include "cmcd_device.h"
 #include "cmcd_hip.h"
-#include "cmcd_hip_diag.h"
+#include "cmcd_host.h"
 
 namespace cmcd {
-
-static thread_local char g_err[512] = "";
-static thread_local char g_kernel_name[96] = "";   // cmcd_last_kernel_name
-
-// Optional in-library timing of the trajectory kernel: when enabled, every cmcd_bound_forward
-// brackets its traj_kernel launch with a hipEvent pair on the caller's stream (bench.py reads
-// the average kernel duration from them for the roofline figure).
-struct ProfileState {
-  static constexpr int kMax = 4096;
-  bool on = false;
-  int used = 0;
-  hipEvent_t ev[kMax][2];
-  int created = 0;
-};
-static thread_local ProfileState g_prof;
-// cmcd_debug_capture_noise: armed per host thread, consumed (and cleared) by the next forward call on that thread
-struct NoiseCapture { uint32_t* bits = nullptr; uint32_t* keys = nullptr; float* noise = nullptr; };
-static thread_local NoiseCapture g_capture;
-
-// Tiles (16 particles each) up to which the CU-cooperative kernel is preferred; measured crossovers on
-// MI355X (tools/probes/variant_sweep.py, t9_variants.py): dds/geffner T<=4 between 512 and 1024 tiles; the 132-wide
-// net at ~600 (500 tiles: cooperative 1.85 ms against 2.27 ms one wave per tile; 1000 tiles: 3.69 against 2.28).
-// r02, after the cooperative kernel's per-bridge time dropped by a sixth (tools/probes/variant_crossover.py,
-// profiles/r02_s2e_variant_crossover.txt; the cooperative time is ceil(tiles / 256 CUs) rounds of one workgroup per CU):
-//   dds net, 40-mode mixture:     cooperative wins through 6 rounds (1536 tiles: 1.13 against 1.34 ms; 2048: 1.42 / 1.34)
-//   132-wide net, 40-mode mixture: through 3 rounds (768 tiles: 1.91 against 2.31 ms; 813: 2.53 / 2.29)
-//   funnel / gmm on the narrow geffner nets: 512 tiles still (768: 0.373 / 0.314 ms and 0.0257 / 0.0246 ms)
-static int coop_max_tiles(const cmcd_desc& d, int T) {
-  if (d.target == CMCD_TARGET_MANY_GMM && d.dim == 2) {
-    if (d.arch == CMCD_ARCH_DDS) return 1536;
-    if (T == 9) return 768;
-  }
-  return 512;
-}
-static int fail(int code, const char* fmt, const char* a = "", long long b = 0) {
-  snprintf(g_err, sizeof(g_err), fmt, a, b);
-  return code;
-}
-
-static inline int64_t align4(int64_t x) { return (x + 3) & ~int64_t(3); }
-
-int net_in_dim(const cmcd_desc& d);
-static bool hidden_width(const cmcd_desc& d, int& HP) {
-  if (d.arch == CMCD_ARCH_DDS) {
-    HP = 64;
-    return true;
-  }
-  if (d.arch == CMCD_ARCH_GEFFNER) {
-    if (d.emb_dim < 1) return false;
-    HP = ((net_in_dim(d) + d.emb_dim + 15) / 16) * 16;
-    if (d.mode == CMCD_MODE_CAIS_UHA_SN && d.target != CMCD_TARGET_LGCP) {
-      // 2nd-order CMCD has its own kernels (cmcd_uha.hip): instances of 2, 4, 5 and 9 neuron tiles (gmm 2*2+20 = 24,
-      // funnel 2*10+48 = 68, the 40-mode mixture 2*2+130 = 134), other widths zero-padded to the next one
-      const int T = HP / 16;
-      HP = 16 * (T <= 2 ? 2 : (T <= 4 ? 4 : (T <= 5 ? 5 : (T <= 9 ? 9 : T))));
-      return true;
-    }
-    // Kernel instances exist for 2, 4 and 9 neuron tiles (the BASELINE widths 22 / 58 / 132); any other width runs
-    // on the next larger instance with zero-padded weights: a padded unit has no outgoing weight, so it cannot
-    // reach the output, and its gradient entries are never copied out.  (lgcp has its own path: any width.)
-    if (d.target != CMCD_TARGET_LGCP) {
-      const int T = HP / 16;
-      // funnel (d = 10): its gradient kernels start at 4 tiles, and forward / gradient share one workspace layout
-      const int tmin = d.target == CMCD_TARGET_FUNNEL ? 4 : 2;
-      HP = 16 * (T <= tmin ? tmin : (T <= 4 ? 4 : (T <= 9 ? 9 : T)));
-    }
-    return true;
-  }
-  return false;
-}
-
-// width of the state part of the network input: z, or concat(z, rho) for the momentum mode (rho_dim = dim,
-// /root/reference/src/mcdboundingmachine.py:82-98)
-int net_in_dim(const cmcd_desc& d) { return d.mode == CMCD_MODE_CAIS_UHA_SN ? 2 * d.dim : d.dim; }
-
-// floats of the trajectory a gradient call keeps: z_0..z_K, plus rho_0..rho_K and rho'_0..rho'_{K-1} for the momentum mode
-static int64_t kept_traj_floats(const cmcd_desc& d, int64_t n) {
-  return (int64_t)(d.mode == CMCD_MODE_CAIS_UHA_SN ? 3 * d.nbridges + 2 : d.nbridges + 1) * n * d.dim;
-}
-
-static int64_t target_lds_floats(const cmcd_desc& d, int64_t n_target) {
-  if (d.target == CMCD_TARGET_MANY_GMM) return 4 + (n_target - 1);  // header + means
-  return 0;
-}
-
-// lgcp: only the schedule tables live in the common layout; the rest is carved by cmcd_lgcp.hip
-static bool make_ws_lgcp(const cmcd_desc& d, int64_t n, WsLayout& w) {
-  const int64_t K = d.nbridges;
-  memset(&w, 0, sizeof(w));
-  int64_t o = 0;
-  w.beta = o; o += align4(K);
-  w.eps = o; o += align4(K);
-  w.sig = o; o += align4(K);
-  w.logsig = o; o += align4(K);
-  w.sched = o; o += 8 * K;
-  w.n_waves = (int32_t)n;  // one statistics record per particle
-  w.total_floats = o;
-  return true;
-}
-
-static bool make_ws(const cmcd_desc& d, int64_t n, int64_t n_target, WsLayout& w) {
-  int HP;
-  if (!hidden_width(d, HP)) return false;
-  const int64_t K = d.nbridges, D = d.dim;
-  w.HP = HP;
-  w.T = HP / 16;
-  int64_t o = 0;
-  w.beta = o; o += align4(K);
-  w.eps = o; o += align4(K);
-  w.sig = o; o += align4(K);
-  w.logsig = o; o += align4(K);
-  w.sched = o; o += 8 * K;
-  w.bias1 = o; o += (K + 1) * HP;
-  if (d.arch == CMCD_ARCH_GEFFNER) { w.utab = o; o += (K + 1) * HP; } else { w.utab = w.bias1; }
-  w.w1z = o; o += int64_t(net_in_dim(d)) * HP;
-  w.w2 = o; o += int64_t(HP) * HP;
-  w.w2t = o; o += int64_t(HP) * HP;
-  w.w2q = o; o += 2 * int64_t(HP) * HP;
-  w.b2 = o; o += HP;
-  w.w3t = o; o += D * HP;
-  w.b3 = o; o += 16;
-  w.tgt_floats = align4(target_lds_floats(d, n_target));
-  w.tgt = o; o += w.tgt_floats;
-  o = (o + 1) & ~int64_t(1);
-  w.n_waves = int32_t((n + 15) / 16);
-  // sized for the cooperative kernel's 8-particle tiles (twice the records of the 16-particle tiling)
-  w.partials = o; o += int64_t((n + 7) / 8) * CMCD_NSTATS * 2;
-  w.total_floats = o;
-  return true;
-}
 
 // ------------------------------------------------------------------------------------------
 // 1. schedules
@@ -1106,7 +976,7 @@ __global__ void vargrad_weights_kernel(const float* loss, const double* stats, i
 }
 
 // ------------------------------------------------------------------------------------------
-// host side
+// launchers (cmcd_host.h): everything cmcd_api.hip needs from this file
 // ------------------------------------------------------------------------------------------
 typedef void (*traj_fn)(TrajArgs);
 
@@ -1146,30 +1016,44 @@ static traj_fn pick_kernel(const cmcd_desc& d, int T) {
   return nullptr;
 }
 
-// What a set of prepared tables was formed from, as far as the library can know it without reading device memory: FNV-1a
-// over the descriptor (minus the kernel-variant field, which selects a kernel and not a table), the layout and the sizes.
-static uint32_t tables_stamp(const cmcd_desc& d, const cmcd_layout& lay, int64_t n, int64_t n_params, int64_t n_target) {
-  uint32_t h = 2166136261u;
-  auto eat = [&](const void* p, size_t len) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t i = 0; i < len; ++i) { h ^= b[i]; h *= 16777619u; }
-  };
-  cmcd_desc dd = d;
-  dd.reserved = 0;
-  eat(&dd, sizeof dd); eat(&lay, sizeof lay); eat(&n, sizeof n); eat(&n_params, sizeof n_params); eat(&n_target, sizeof n_target);
-  return h ? h : 1u;
+bool traj_available(const cmcd_desc& d, int T) { return pick_kernel(d, T) != nullptr; }
+
+int traj_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, hipStream_t stream,
+                int (*before_launch)(hipStream_t)) {
+  traj_fn fn = pick_kernel(d, w.T);
+  const int64_t tiles = w.n_waves, D = d.dim;
+  const size_t lds_bytes = size_t(w.HP * w.HP + 2 * D * w.HP + w.HP + 16 + w.tgt_floats) * 4;
+  if (lds_bytes > 160 * 1024) return fail(CMCD_ERR_UNSUPPORTED, "network too wide for LDS%s");
+  // Waves per workgroup.  Up to 1024 tiles: one wave per workgroup spreads over all SIMDs.  Beyond
+  // that single-wave workgroups pile onto the same SIMD of a CU (measured: 2048 x 1 wave ran 2.4x
+  // longer than 1024 x 1), so use 4-wave workgroups (one wave per SIMD), 8 for very large batches
+  // or when LDS limits the CU to one resident workgroup.
+  int64_t per_cu = (160 * 1024) / (int64_t)lds_bytes;
+  int nw = tiles <= 1024 ? 1 : (tiles <= 8192 ? 4 : 8);
+  if (per_cu < 2 && tiles > 256) nw = tiles <= 1024 ? 4 : 8;
+  CMCD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  const unsigned blocks = unsigned((tiles + nw - 1) / nw);
+  const int rc = before_launch ? before_launch(stream) : CMCD_OK;
+  if (rc != CMCD_OK) return rc;
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * nw), lds_bytes, stream, ta);
+  return CMCD_OK;
 }
 
-static void launch_prep(const cmcd_desc& d, const cmcd_layout& layr, const WsLayout& w, const float* params,
-                        const float* target_consts, int n_mix, float* ws, hipStream_t stream, uint32_t stamp) {
+void launch_prep_sched(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, const float* params, float* ws,
+                       hipStream_t stream, uint32_t stamp) {
+  SchedArgs sa{params, ws, lay, w, d.nbridges, d.ngrid, d.eps_schedule, -1, -1};
+  sa.stamp = stamp;
+  hipLaunchKernelGGL(prep_sched_kernel, dim3(1), dim3(256), 0, stream, sa);
+}
+
+void launch_prep(const cmcd_desc& d, const cmcd_layout& layr, const WsLayout& w, const float* params,
+                 const float* target_consts, int n_mix, float* ws, hipStream_t stream, uint32_t stamp) {
   const cmcd_layout* lay = &layr;
   // D here = the state inputs of the network: z, or concat(z, rho) for the momentum mode
   const int64_t K = d.nbridges, D = net_in_dim(d), E = d.emb_dim, IN = D + E;
   PrepArgs pa{};
-  const bool ula_mode = d.mode == CMCD_MODE_ULA || d.mode == CMCD_MODE_ULA_SN;
-  // MCD_CAIS_UHA_sn: the cos^2 schedule is part of the function body (mcd_under_lp_a_cais.py:33-40,48)
-  const int sched = ula_mode ? CMCD_EPS_CONST : (d.mode == CMCD_MODE_CAIS_UHA_SN ? CMCD_EPS_COS_SQ : d.eps_schedule);
-  pa.sched = SchedArgs{params, ws, *lay, w, (int32_t)K, d.ngrid, sched, -1, -1};
+  pa.sched = SchedArgs{params, ws, *lay, w, (int32_t)K, d.ngrid, d.eps_schedule, -1, -1};
   PackArgs& pk = pa.pack;
   pk.stamp = stamp;
   pa.sched.stamp = stamp;
@@ -1190,625 +1074,22 @@ static void launch_prep(const cmcd_desc& d, const cmcd_layout& layr, const WsLay
   pa.npack = (w.HP * w.HP + 255) / 256;
   if (pa.npack > 64) pa.npack = 64;
   hipLaunchKernelGGL(prep_fused_kernel, dim3((unsigned)(K + 2 + pa.npack)), dim3(256), 0, stream, pa);
-
-
 }
 
-int fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
+void launch_finalize(const double* partials, int32_t count, double* out5, hipStream_t stream, const uint32_t* stamp_slot,
+                     uint32_t stamp) {
+  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, stream, partials, count, out5, stamp_slot, stamp);
+}
 
 int launch_finalize(const double* partials, int32_t count, double* out5, void* stream) {
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), partials, count, out5,
-                     (const uint32_t*)nullptr, 0u);
+  launch_finalize(partials, count, out5, static_cast<hipStream_t>(stream), nullptr, 0u);
   return hipGetLastError() == hipSuccess ? CMCD_OK : fail(CMCD_ERR_HIP, "finalize launch failed%s");
 }
 
-static int check_desc(const cmcd_desc* d) {
-  if (!d) return fail(CMCD_ERR_BAD_ARG, "null desc%s");
-  if (d->mode < CMCD_MODE_CAIS_SN || d->mode > CMCD_MODE_CAIS_UHA_SN)
-    return fail(CMCD_ERR_UNSUPPORTED, "Mode not implemented.%s");
-  if (d->mode == CMCD_MODE_ULA && d->arch != CMCD_ARCH_DDS)
-    return fail(CMCD_ERR_BAD_ARG, "MCD_ULA has no network: pass arch = CMCD_ARCH_DDS as the placeholder%s");
-  if (d->arch != CMCD_ARCH_DDS && d->arch != CMCD_ARCH_GEFFNER)
-    return fail(CMCD_ERR_UNSUPPORTED, "nn_arch not implemented%s");
-  if (d->nbridges < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges must be >= 1%s");
-  if (d->ngrid < 1 || d->ngrid > 32) return fail(CMCD_ERR_BAD_ARG, "ngrid must be in [1, 32]%s");
-  if (d->eps_schedule == CMCD_EPS_LINEAR && d->nbridges < 2)
-    return fail(CMCD_ERR_BAD_ARG, "linear eps schedule needs nbridges >= 2%s");
-  int HP;
-  if (!hidden_width(*d, HP)) return fail(CMCD_ERR_BAD_ARG, "bad emb_dim%s");
-  if (d->target == CMCD_TARGET_LGCP) {
-    if ((d->arch != CMCD_ARCH_GEFFNER && d->mode != CMCD_MODE_ULA) || d->dim < 4 || d->dim > 4096)
-      return fail(CMCD_ERR_UNSUPPORTED, "lgcp runs with the geffner net only%s");
-    return CMCD_OK;
-  }
-  if (d->mode == CMCD_MODE_CAIS_UHA_SN) {
-    if (!uha_available(*d, HP / 16))
-      return fail(CMCD_ERR_UNSUPPORTED, "no MCD_CAIS_UHA_sn kernel instance for this (target, dim, arch, width=%s%lld)", "", HP);
-    return CMCD_OK;
-  }
-  if (!pick_kernel(*d, HP / 16))
-    return fail(CMCD_ERR_UNSUPPORTED, "no kernel instance for this (target, dim, arch, width=%s%lld)", "", HP);
-  return CMCD_OK;
+void launch_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(vargrad_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, loss, stats, n, n_total,
+                     omega);
 }
 
 }  // namespace cmcd
-
-using namespace cmcd;
-
-extern "C" {
-
-int cmcd_version(void) { return CMCD_ABI_VERSION; }
-const char* cmcd_last_error(void) { return g_err; }
-#ifndef CMCD_NO_DIAG_HOOKS   // include/cmcd_hip_diag.h: compiled out of a boundary-only build
-const char* cmcd_last_kernel_name(void) { return g_kernel_name; }
-#endif
-
-int64_t cmcd_target_floats(const cmcd_desc* desc, int32_t n_mixes) {
-  if (!desc) return -1;
-  switch (desc->target) {
-    case CMCD_TARGET_GMM:
-    case CMCD_TARGET_FUNNEL: return 0;
-    case CMCD_TARGET_MANY_GMM: return 1 + 2 * (int64_t)n_mixes;
-    case CMCD_TARGET_LGCP: return (int64_t)desc->dim * desc->dim + desc->dim + 3;
-    default: return -1;
-  }
-}
-
-int64_t cmcd_workspace_bytes(const cmcd_desc* desc, int64_t n) {
-  if (check_desc(desc) != CMCD_OK || n < 1) return 0;
-  WsLayout w;
-  if (desc->target == CMCD_TARGET_LGCP) {
-    make_ws_lgcp(*desc, n, w);
-    return lgcp_workspace_floats(*desc, n, w.total_floats) * 4;
-  }
-  // size for the largest target-constant block this target can stage (64 mixtures)
-  const int64_t nt = desc->target == CMCD_TARGET_MANY_GMM ? 1 + 2 * 64 : 0;
-  if (!make_ws(*desc, n, nt, w)) return 0;
-  return w.total_floats * 4;
-}
-
-#define CMCD_HIP_CHECK(expr)                                                                   \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(CMCD_ERR_HIP, "HIP error: %s (code %lld)", hipGetErrorString(e_), (long long)e_); \
-  } while (0)
-
-static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                        void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
-                        double* out_stats, float* traj, void* stream_, bool tables_ready = false) {
-  const NoiseCapture cap = g_capture;   // armed by cmcd_debug_capture_noise: this call consumes it, whatever happens
-  g_capture = NoiseCapture{};
-  int rc = check_desc(desc);
-  if (rc != CMCD_OK) return rc;
-  if ((cap.bits || cap.keys) && desc->target == CMCD_TARGET_LGCP)
-    return fail(CMCD_ERR_UNSUPPORTED, "cmcd_debug_capture_noise: trajectory kernels only (not the lgcp launch sequence)%s");
-  if (!lay || !seeds || !params || !workspace || !out_loss || !out_z || !out_stats)
-    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  const cmcd_desc& d = *desc;
-  const int64_t K = d.nbridges, D = d.dim, E = d.emb_dim, DIN = net_in_dim(d), IN = DIN + E;
-  const bool uha = d.mode == CMCD_MODE_CAIS_UHA_SN;
-
-  // every leaf this configuration reads must lie inside params_flat
-  auto need = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
-  bool ok = need(lay->vd_mean, D) && need(lay->vd_logdiag, D) && need(lay->eps, 1) &&
-            need(lay->mgridref_y, d.ngrid + 1) && (!uha || need(lay->gamma, 1));
-  if (d.mode == CMCD_MODE_ULA) {
-    // no network leaves
-  } else if (d.arch == CMCD_ARCH_GEFFNER)
-    ok = ok && need(lay->g_emb, K * E) && need(lay->g_factor, 1) && need(lay->g_w1, IN * IN) &&
-         need(lay->g_b1, IN) && need(lay->g_w2, IN * IN) && need(lay->g_b2, IN) && need(lay->g_w3, IN * D) &&
-         need(lay->g_b3, D);
-  else
-    ok = ok && need(lay->d_phase, 64) && need(lay->d_tw1, 128 * 64) && need(lay->d_tb1, 64) &&
-         need(lay->d_tw2, 64 * 64) && need(lay->d_tb2, 64) && need(lay->d_sw1, (DIN + 64) * 64) &&
-         need(lay->d_sb1, 64) && need(lay->d_sw2, 64 * 64) && need(lay->d_sb2, 64) &&
-         need(lay->d_sw3, 64 * D) && need(lay->d_sb3, D);
-  if (!ok) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-
-  int n_mix = 0;
-  if (d.target == CMCD_TARGET_MANY_GMM) {
-    if (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64)
-      return fail(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}%s");
-    n_mix = int((n_target - 1) / 2);
-  } else if (d.target == CMCD_TARGET_LGCP) {
-    if (!target_consts || n_target != D * D + D + 3)
-      return fail(CMCD_ERR_BAD_ARG, "lgcp needs target_consts = {Kinv[d,d], counts[d], mu0, a, lognorm}%s");
-    WsLayout lw;
-    make_ws_lgcp(d, n, lw);
-    const int64_t need = lgcp_workspace_floats(d, n, lw.total_floats) * 4;
-    if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-      return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-    hipStream_t st = static_cast<hipStream_t>(stream_);
-    float* wsf = static_cast<float*>(workspace);
-    // the overdamped baselines: constant eps, no clipping (the reference's dispatcher passes neither, mcd_utils.py:35-58)
-    cmcd_desc dl = d;
-    if (d.mode == CMCD_MODE_ULA || d.mode == CMCD_MODE_ULA_SN) { dl.eps_schedule = CMCD_EPS_CONST; dl.grad_clipping = 0; }
-    if (uha) { dl.eps_schedule = CMCD_EPS_COS_SQ; dl.grad_clipping = 1; }   // fixed by the function body (mcd_under_lp_a_cais.py:23-48)
-    // (cmcd_bound_forward_prepared: the schedule table, the first-layer bias table and the packed weights are still in the
-    // workspace; the 2nd-order sequence has no prepared form)
-    const bool lgcp_ready = tables_ready && !uha;
-    SchedArgs sa{params, wsf, *lay, lw, (int32_t)K, d.ngrid, dl.eps_schedule, -1, -1};
-    const uint32_t lstamp = tables_stamp(d, *lay, n, n_params, n_target);
-    sa.stamp = lstamp;
-    if (!lgcp_ready) hipLaunchKernelGGL(prep_sched_kernel, dim3(1), dim3(256), 0, st, sa);
-    double* partials = nullptr;
-    snprintf(g_kernel_name, sizeof(g_kernel_name), "%s", lgcp_use_wide(dl, n, traj != nullptr)
-                 ? "lgcp wide-batch sequence (32x128-tile fp32 GEMM launches)"
-                 : "lgcp launch sequence (skinny GEMMs + state kernels)");
-    // gradient calls (traj set) place the gradient workspace right in front of the kept trajectory: the forward's consumers
-    // keep their activations in its tables, so that the reverse sweep does not recompute them (cmcd_lgcp.hip: lgcp_keep)
-    float* keep_gws = traj ? traj - align4(lgcp_grad_workspace_floats(dl, n)) : nullptr;
-    rc = lgcp_forward(dl, *lay, lw, seeds, n, params, target_consts, wsf, out_loss, out_z, &partials, traj, stream_, lgcp_ready,
-                      keep_gws);
-    if (rc != CMCD_OK) return fail(rc, "lgcp launch sequence failed%s");
-    // (prepared form: the stamp the forming call's schedule launch left in sched[0][7] must be this call's)
-    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, partials, (int32_t)n, out_stats,
-                       lgcp_ready ? reinterpret_cast<const uint32_t*>(wsf + lw.sched + 7) : nullptr, lstamp);
-    CMCD_HIP_CHECK(hipGetLastError());
-    return CMCD_OK;
-  }
-
-  WsLayout w;
-  if (!make_ws(d, n, n_target, w)) return fail(CMCD_ERR_BAD_ARG, "bad descriptor%s");
-  if (workspace_bytes < w.total_floats * 4 || (reinterpret_cast<uintptr_t>(workspace) & 15))
-    return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "",
-                w.total_floats * 4);
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-
-  // cmcd_bound_forward_prepared: the caller vouches that the workspace still holds the tables a previous call formed from the
-  // SAME (desc, layout, params, target constants, n): the prep launch (4.8 us + a kernel boundary per call) is skipped
-  const uint32_t stamp = tables_stamp(d, *lay, n, n_params, n_target);
-  if (!tables_ready) launch_prep(d, *lay, w, params, target_consts, n_mix, ws, stream, stamp);
-  // prepared form: whoever writes the statistics compares the stamp left in b3[13] with this call's (finalize_kernel)
-  const uint32_t* stamp_slot = tables_ready ? reinterpret_cast<const uint32_t*>(ws + w.b3 + 13) : nullptr;
-
-  if (uha) {   // 2nd-order CMCD: its own trajectory kernel (cmcd_uha.hip), same prep tables and statistics merge
-    TrajArgs tu{seeds, params, ws, reinterpret_cast<double*>(ws + w.partials), out_loss, out_z, *lay, w, n,
-                (int32_t)K, 0, 1, traj, 0};
-    tu.dbg_bits = cap.bits; tu.dbg_keys = cap.keys; tu.dbg_noise = cap.noise;
-    int n_records = w.n_waves;
-    rc = uha_forward_launch(d, tu, stream, &n_records);
-    snprintf(g_kernel_name, sizeof(g_kernel_name), "%s", uha_last_kernel_name());
-    if (rc != CMCD_OK) return fail(rc, "MCD_CAIS_UHA_sn launch failed%s");
-    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, stream,
-                       reinterpret_cast<const double*>(ws + w.partials), (int32_t)n_records, out_stats, stamp_slot, stamp);
-    CMCD_HIP_CHECK(hipGetLastError());
-    return CMCD_OK;
-  }
-
-  TrajArgs ta{seeds, params, ws, reinterpret_cast<double*>(ws + w.partials), out_loss, out_z, *lay, w, n,
-              (int32_t)K, d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0,
-              (d.mode == CMCD_MODE_ULA || d.mode == CMCD_MODE_ULA_SN) ? 0 : d.grad_clipping, traj,
-              d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
-  ta.dbg_bits = cap.bits; ta.dbg_keys = cap.keys; ta.dbg_noise = cap.noise;
-  // Kernel variant (desc.reserved: 0 auto, 1 wave-per-tile, 2 CU-cooperative, 3 cooperative on 16-particle tiles,
-  // 4 cooperative on 8-particle tiles).  Auto: the cooperative kernel while the batch cannot fill the chip with one
-  // wave per tile, on 8-particle tiles while those still get a CU each (n <= 8 x 256).
-  const bool coop_ok = coop_available(d, w.T) && d.mode != CMCD_MODE_ULA;
-  const bool forced = d.reserved >= 2 && d.reserved <= 5;
-  bool use_coop = forced ? coop_ok : (d.reserved == 1 ? false : (coop_ok && w.n_waves <= coop_max_tiles(d, w.T)));
-  if (forced && !coop_ok) return fail(CMCD_ERR_UNSUPPORTED, "no cooperative kernel instance%s");
-  const bool half_ok = coop_half_available(d, w.T);
-  if ((d.reserved == 4 || d.reserved == 5) && !half_ok) return fail(CMCD_ERR_UNSUPPORTED, "no 8-particle-tile cooperative instance%s");
-  const bool half = d.reserved == 4 || d.reserved == 5 || (d.reserved != 3 && half_ok && n <= 8 * 256);
-  const bool wide8 = half && d.reserved != 5 && coop_wide8_available(d, w.T);   // d = 10: the dealt-coordinates kernel (5 = the narrow form, A / B)
-  if (use_coop) {
-    const bool prof = g_prof.on && g_prof.used < ProfileState::kMax;
-    if (prof) {
-      if (g_prof.used >= g_prof.created) {
-        CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][0]));
-        CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][1]));
-        ++g_prof.created;
-      }
-      CMCD_HIP_CHECK(hipEventRecord(g_prof.ev[g_prof.used][0], stream));
-    }
-    snprintf(g_kernel_name, sizeof(g_kernel_name), "%s<%d-particle tiles%s>", wide8 ? "coop_wide8_kernel" : "coop_kernel",
-             half ? 8 : 16, w.T == 9 ? ", 132-wide net" : "");
-    // Small grids (<= 64 workgroups: the launch-bound configurations — gmm / funnel at N = 300 are 38 workgroups): the
-    // statistics are merged by the last workgroup to arrive (its counter: the free slot 14 of the b3 row, zeroed by the prep
-    // launch of this call) and the finalize launch is dropped: gmm N = 300, K = 8 0.0266 -> 0.0245 ms per call.  Larger
-    // grids keep the finalize launch: at the named batch's 250 workgroups the merge tail costs the trajectory kernel what
-    // the launch saves (per call 0.2026 vs 0.2024 ms).  Same five doubles bit for bit either way.
-    const int64_t coop_wgs = half ? (n + 7) / 8 : w.n_waves;
-    const bool fused_merge = coop_wgs <= 64;
-    if (fused_merge) {
-      ta.fin_out = out_stats;
-      ta.fin_counter = reinterpret_cast<int32_t*>(ws + w.b3 + 14);
-      ta.stamp_slot = stamp_slot;
-      ta.stamp_expect = stamp;
-    }
-    rc = coop_launch(d, ta, half, stream, !wide8);
-    if (rc != CMCD_OK) return fail(rc, "cooperative launch failed%s");
-    if (prof) {
-      CMCD_HIP_CHECK(hipEventRecord(g_prof.ev[g_prof.used][1], stream));
-      ++g_prof.used;
-    }
-    if (!fused_merge)
-      hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, stream,
-                         reinterpret_cast<const double*>(ws + w.partials), (int32_t)coop_wgs, out_stats, stamp_slot, stamp);
-    CMCD_HIP_CHECK(hipGetLastError());
-    return CMCD_OK;
-  }
-  traj_fn fn = pick_kernel(d, w.T);
-  // waves per workgroup: one wave per CU until every CU has one, then grow (weights are
-  // staged once per workgroup, so bigger groups amortise the LDS fill).
-  const int64_t tiles = w.n_waves;
-  const size_t lds_bytes = size_t(w.HP * w.HP + 2 * D * w.HP + w.HP + 16 + w.tgt_floats) * 4;
-  if (lds_bytes > 160 * 1024) return fail(CMCD_ERR_UNSUPPORTED, "network too wide for LDS%s");
-  // Waves per workgroup.  Up to 1024 tiles: one wave per workgroup spreads over all SIMDs.  Beyond
-  // that single-wave workgroups pile onto the same SIMD of a CU (measured: 2048 x 1 wave ran 2.4x
-  // longer than 1024 x 1), so use 4-wave workgroups (one wave per SIMD), 8 for very large batches
-  // or when LDS limits the CU to one resident workgroup.
-  int64_t per_cu = (160 * 1024) / (int64_t)lds_bytes;
-  int nw = tiles <= 1024 ? 1 : (tiles <= 8192 ? 4 : 8);
-  if (per_cu < 2 && tiles > 256) nw = tiles <= 1024 ? 4 : 8;
-  CMCD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  const unsigned blocks = unsigned((tiles + nw - 1) / nw);
-  const bool prof = g_prof.on && g_prof.used < ProfileState::kMax;
-  if (prof) {
-    if (g_prof.used >= g_prof.created) {
-      CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][0]));
-      CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][1]));
-      ++g_prof.created;
-    }
-    CMCD_HIP_CHECK(hipEventRecord(g_prof.ev[g_prof.used][0], stream));
-  }
-  snprintf(g_kernel_name, sizeof(g_kernel_name), "traj_kernel");
-  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * nw), lds_bytes, stream, ta);
-  if (prof) {
-    CMCD_HIP_CHECK(hipEventRecord(g_prof.ev[g_prof.used][1], stream));
-    ++g_prof.used;
-  }
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, stream,
-                     reinterpret_cast<const double*>(ws + w.partials), w.n_waves, out_stats, stamp_slot, stamp);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
-}
-
-#ifndef CMCD_NO_DIAG_HOOKS
-int cmcd_debug_capture_noise(uint32_t* bits, uint32_t* gen_keys, float* noise) {
-  if ((bits == nullptr) != (noise == nullptr)) return fail(CMCD_ERR_BAD_ARG, "bits and noise go together%s");
-  g_capture.bits = bits; g_capture.keys = gen_keys; g_capture.noise = noise;
-  return CMCD_OK;
-}
-#endif
-
-int cmcd_bound_forward(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                       const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                       void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
-                       double* out_stats, void* stream_) {
-  return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
-                      out_loss, out_z, out_stats, nullptr, stream_);
-}
-
-int cmcd_bound_forward_prepared(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                                const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                                void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
-                                double* out_stats, void* stream_) {
-  const bool ready = desc != nullptr;
-  return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
-                      out_loss, out_z, out_stats, nullptr, stream_, ready);
-}
-
-int64_t cmcd_bound_grad_workspace_bytes(const cmcd_desc* desc, int64_t n) {
-  if (check_desc(desc) != CMCD_OK || n < 1) return 0;
-  if (desc->target == CMCD_TARGET_LGCP) {
-    if (desc->mode == CMCD_MODE_CAIS_VAR_SN) {
-      fail(CMCD_ERR_UNSUPPORTED, "MCD_CAIS_var_sn: cmcd_grad_workspace_bytes / cmcd_bound_var_forward / cmcd_bound_var_grad_kept%s");
-      return 0;
-    }
-    WsLayout lw;
-    make_ws_lgcp(*desc, n, lw);
-    return (align4(lgcp_workspace_floats(*desc, n, lw.total_floats)) + align4(lgcp_grad_workspace_floats(*desc, n)) +
-            kept_traj_floats(*desc, n)) * 4;
-  }
-  WsLayout w;
-  const int64_t nt = desc->target == CMCD_TARGET_MANY_GMM ? 1 + 2 * 64 : 0;
-  if (!make_ws(*desc, n, nt, w)) return 0;
-  if (desc->mode == CMCD_MODE_ULA) {
-    if (!ula_grad_available(*desc)) { fail(CMCD_ERR_UNSUPPORTED, "no MCD_ULA gradient instance for this target%s"); return 0; }
-    return (align4(w.total_floats) + align4(ula_grad_workspace_floats(*desc, n)) +
-            (int64_t)(desc->nbridges + 1) * n * desc->dim) * 4;
-  }
-  if (desc->mode == CMCD_MODE_CAIS_UHA_SN) {
-    if (!uha_grad_available(*desc, w.T)) { fail(CMCD_ERR_UNSUPPORTED, "no MCD_CAIS_UHA_sn gradient instance for this (target, dim, arch, width)%s"); return 0; }
-    return (align4(w.total_floats) + align4(uha_grad_workspace_floats(*desc, w.HP, n)) + uha_traj_floats(*desc, n)) * 4;
-  }
-  if ((desc->mode != CMCD_MODE_CAIS_SN && desc->mode != CMCD_MODE_ULA_SN) || !bptt_available(*desc, w.T)) {
-    fail(CMCD_ERR_UNSUPPORTED, "no reparameterised-gradient kernel instance for this (mode, target, dim, arch, width)%s");
-    return 0;
-  }
-  return (align4(w.total_floats) + align4(grad_workspace_floats(*desc, w.HP, n)) +
-          align4((int64_t)(desc->nbridges + 1) * n * desc->dim) +
-          (grad_item_mode(*desc, w.T, n) ? bptt_item_floats(*desc, n) : 0)) * 4;
-}
-
-int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                    const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                    float omega, void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
-                    double* out_stats, float* grad, void* stream_) {
-  int rc = check_desc(desc);
-  if (rc != CMCD_OK) return rc;
-  if (!grad) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (desc->mode != CMCD_MODE_CAIS_SN && desc->mode != CMCD_MODE_ULA_SN && desc->mode != CMCD_MODE_ULA &&
-      desc->mode != CMCD_MODE_CAIS_UHA_SN)
-    return fail(CMCD_ERR_UNSUPPORTED, "the reparameterised gradient exists for MCD_CAIS_sn, MCD_CAIS_UHA_sn and MCD_ULA[_sn] (MCD_CAIS_var_sn: cmcd_bound_var_grad)%s");
-  // MCD_ULA_sn: the reference's dispatcher passes neither eps_schedule nor grad_clipping (mcd_utils.py:35-58)
-  cmcd_desc dd = *desc;
-  if (dd.mode == CMCD_MODE_ULA_SN || dd.mode == CMCD_MODE_ULA) { dd.eps_schedule = CMCD_EPS_CONST; dd.grad_clipping = 0; }
-  const cmcd_desc& d = dd;
-  if (d.target == CMCD_TARGET_LGCP) {
-    // d = 1600: launch-sequence forward (trajectory kept) + launch-sequence reverse sweep (cmcd_lgcp.hip)
-    WsLayout lw;
-    make_ws_lgcp(d, n, lw);
-    const int64_t fwd = align4(lgcp_workspace_floats(d, n, lw.total_floats));
-    const int64_t gfl = align4(lgcp_grad_workspace_floats(d, n));
-    const int64_t need = (fwd + gfl + kept_traj_floats(d, n)) * 4;
-    if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-      return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-    float* ws = static_cast<float*>(workspace);
-    float* traj = ws + fwd + gfl;
-    rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, out_loss,
-                      out_z, out_stats, traj, stream_);
-    if (rc != CMCD_OK) return rc;
-    rc = lgcp_grad(d, *lay, lw, n, params, n_params, target_consts, ws, traj, ws + fwd, omega, nullptr, true, grad, stream_);
-    if (rc != CMCD_OK) return fail(rc, "lgcp gradient launch sequence failed%s");
-    return CMCD_OK;
-  }
-  WsLayout w;
-  if (!make_ws(d, n, n_target, w)) return fail(CMCD_ERR_BAD_ARG, "bad descriptor%s");
-  if (d.mode == CMCD_MODE_ULA) {   // no network: forward with the trajectory kept + the network-free reverse sweep
-    if (!ula_grad_available(d)) return fail(CMCD_ERR_UNSUPPORTED, "no MCD_ULA gradient instance for this target%s");
-    const int64_t fwd = align4(w.total_floats), gfl = align4(ula_grad_workspace_floats(d, n));
-    const int64_t need = (fwd + gfl + (int64_t)(d.nbridges + 1) * n * d.dim) * 4;
-    if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-      return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-    float* ws = static_cast<float*>(workspace);
-    float* traj = ws + fwd + gfl;
-    rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, out_loss,
-                      out_z, out_stats, traj, stream_);
-    if (rc != CMCD_OK) return rc;
-    rc = ula_grad_launch(d, *lay, w, n, params, n_params, ws, traj, ws + fwd, omega, grad, stream_);
-    if (rc != CMCD_OK) return fail(rc, "gradient launch failed%s");
-    return CMCD_OK;
-  }
-  if (d.mode == CMCD_MODE_CAIS_UHA_SN) {   // 2nd-order CMCD: forward with (z, rho, rho') kept + its reverse sweep (cmcd_uha.hip)
-    if (!uha_grad_available(d, w.T)) return fail(CMCD_ERR_UNSUPPORTED, "no MCD_CAIS_UHA_sn gradient instance for this (target, dim, arch, width)%s");
-    const int64_t fwd = align4(w.total_floats), gfl = align4(uha_grad_workspace_floats(d, w.HP, n));
-    const int64_t need = (fwd + gfl + uha_traj_floats(d, n)) * 4;
-    if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-      return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-    float* ws = static_cast<float*>(workspace);
-    float* traj = ws + fwd + gfl;
-    rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, out_loss,
-                      out_z, out_stats, traj, stream_);
-    if (rc != CMCD_OK) return rc;
-    rc = uha_grad_launch(d, *lay, w, n, params, n_params, ws, traj, ws + fwd, omega, grad, stream_);
-    if (rc != CMCD_OK) return fail(rc, "gradient launch failed%s");
-    return CMCD_OK;
-  }
-  if (!bptt_available(d, w.T)) return fail(CMCD_ERR_UNSUPPORTED, "no reparameterised-gradient kernel instance for this (target, dim, arch, width)%s");
-  const int64_t fwd = align4(w.total_floats), gfl = align4(grad_workspace_floats(d, w.HP, n));
-  const int64_t tfl = align4((int64_t)(d.nbridges + 1) * n * d.dim);
-  const bool item = grad_item_mode(d, w.T, n);
-  const int64_t need = (fwd + gfl + tfl + (item ? bptt_item_floats(d, n) : 0)) * 4;
-  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-    return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-  float* ws = static_cast<float*>(workspace);
-  float* traj = ws + fwd + gfl;
-  rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, out_loss,
-                    out_z, out_stats, traj, stream_);
-  if (rc != CMCD_OK) return rc;
-  rc = grad_launch(d, *lay, w, seeds, n, params, n_params, ws, nullptr, omega, true, item, traj,
-                   item ? traj + tfl : nullptr, ws + fwd, grad, stream_);
-  if (rc != CMCD_OK) return fail(rc, "gradient launch failed%s");
-  return CMCD_OK;
-}
-
-int64_t cmcd_grad_workspace_bytes(const cmcd_desc* desc, int64_t n) {
-  if (check_desc(desc) != CMCD_OK || n < 1) return 0;
-  if (desc->target == CMCD_TARGET_LGCP) {   // launch-sequence forward + reverse sweep + the kept trajectory
-    WsLayout lw;
-    make_ws_lgcp(*desc, n, lw);
-    return (align4(lgcp_workspace_floats(*desc, n, lw.total_floats)) + align4(lgcp_grad_workspace_floats(*desc, n)) +
-            kept_traj_floats(*desc, n)) * 4;
-  }
-  WsLayout w;
-  const int64_t nt = desc->target == CMCD_TARGET_MANY_GMM ? 1 + 2 * 64 : 0;
-  if (!make_ws(*desc, n, nt, w)) return 0;
-  if (!grad_available(*desc, w.T)) {
-    fail(CMCD_ERR_UNSUPPORTED, "no gradient kernel instance for this (target, dim, arch, width)%s");
-    return 0;
-  }
-  int64_t fl = align4(w.total_floats) + align4(grad_workspace_floats(*desc, w.HP, n));
-  if (grad_item_mode(*desc, w.T, n))   // trajectory + scratch outputs of the internal forward pass
-    fl += align4((int64_t)(desc->nbridges + 1) * n * desc->dim) + align4(n) + align4(n * desc->dim) + 16;
-  return fl * 4;
-}
-
-int cmcd_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
-                         void* stream_) {
-  if (!loss || !stats || !omega || n < 1 || n_total < n) return fail(CMCD_ERR_BAD_ARG, "bad argument%s");
-  hipLaunchKernelGGL(vargrad_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), loss, stats, n, n_total, omega);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
-}
-
-static int var_grad_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                         const float* omega, void* workspace, int64_t workspace_bytes, float* grad, bool kept,
-                         void* stream_) {
-  int rc = check_desc(desc);
-  if (rc != CMCD_OK) return rc;
-  if (!lay || !seeds || !params || !omega || !workspace || !grad) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (desc->mode != CMCD_MODE_CAIS_VAR_SN)
-    return fail(CMCD_ERR_UNSUPPORTED, "the local (stop_gradient) gradient exists for MCD_CAIS_var_sn only%s");
-  const cmcd_desc& d = *desc;
-  if (d.target == CMCD_TARGET_LGCP) {
-    // d = 1600: the reverse launch sequence of cmcd_lgcp.hip with z detached, on the trajectory cmcd_bound_var_forward left
-    if (!kept)
-      return fail(CMCD_ERR_UNSUPPORTED, "lgcp: call cmcd_bound_var_forward, then cmcd_bound_var_grad_kept on the same workspace%s");
-    WsLayout lw;
-    make_ws_lgcp(d, n, lw);
-    const int64_t fwd = align4(lgcp_workspace_floats(d, n, lw.total_floats));
-    const int64_t gfl = align4(lgcp_grad_workspace_floats(d, n));
-    const int64_t need = (fwd + gfl + (int64_t)(d.nbridges + 1) * n * d.dim) * 4;
-    if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-      return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-    float* ws = static_cast<float*>(workspace);
-    rc = lgcp_grad(d, *lay, lw, n, params, n_params, target_consts, ws, ws + fwd + gfl, ws + fwd, 0.f, omega, false, grad,
-                   stream_);
-    if (rc != CMCD_OK) return fail(rc, "lgcp gradient launch sequence failed%s");
-    return CMCD_OK;
-  }
-  int n_mix = 0;
-  if (d.target == CMCD_TARGET_MANY_GMM) {
-    if (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64)
-      return fail(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}%s");
-    n_mix = int((n_target - 1) / 2);
-  }
-  WsLayout w;
-  if (!make_ws(d, n, n_target, w)) return fail(CMCD_ERR_BAD_ARG, "bad descriptor%s");
-  if (!grad_available(d, w.T)) return fail(CMCD_ERR_UNSUPPORTED, "no gradient kernel instance for this (target, dim, arch, width)%s");
-  const int64_t need = cmcd_grad_workspace_bytes(desc, n);
-  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-    return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  const int64_t fwd = align4(w.total_floats), gfl = align4(grad_workspace_floats(d, w.HP, n));
-  const bool item = grad_item_mode(d, w.T, n);
-  float* traj = nullptr;
-  if (item && kept) {
-    traj = ws + fwd + gfl;   // left there, with the prep tables, by cmcd_bound_var_forward
-  } else if (item) {
-    // the work-item path reads the trajectory: run the forward launch sequence once more, keeping z_0..z_K
-    traj = ws + fwd + gfl;
-    float* sl = traj + align4((int64_t)(d.nbridges + 1) * n * d.dim);
-    float* sz = sl + align4(n);
-    double* sst = reinterpret_cast<double*>(sz + align4(n * d.dim));
-    rc = forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, sl, sz, sst,
-                      traj, stream_);
-    if (rc != CMCD_OK) return rc;
-  } else if (!kept) {
-    launch_prep(d, *lay, w, params, target_consts, n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
-  }
-  rc = grad_launch(d, *lay, w, seeds, n, params, n_params, ws, omega, 0.f, false, item, traj, nullptr, ws + fwd, grad,
-                   stream_);
-  if (rc != CMCD_OK) return fail(rc, "gradient launch failed%s");
-  return CMCD_OK;
-}
-
-int cmcd_bound_var_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                        const float* omega, void* workspace, int64_t workspace_bytes, float* grad, void* stream_) {
-  return var_grad_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, omega, workspace,
-                       workspace_bytes, grad, false, stream_);
-}
-
-int cmcd_bound_var_forward(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                           const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                           void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z,
-                           double* out_stats, void* stream_) {
-  int rc = check_desc(desc);
-  if (rc != CMCD_OK) return rc;
-  if (desc->mode != CMCD_MODE_CAIS_VAR_SN)
-    return fail(CMCD_ERR_UNSUPPORTED, "the local (stop_gradient) gradient exists for MCD_CAIS_var_sn only%s");
-  const int64_t need = cmcd_grad_workspace_bytes(desc, n);
-  if (need <= 0) return CMCD_ERR_UNSUPPORTED;
-  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-    return fail(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned (need %s%lld bytes)", "", need);
-  if (desc->target == CMCD_TARGET_LGCP) {
-    WsLayout lw;
-    make_ws_lgcp(*desc, n, lw);
-    const int64_t fwd = align4(lgcp_workspace_floats(*desc, n, lw.total_floats));
-    const int64_t gfl = align4(lgcp_grad_workspace_floats(*desc, n));
-    return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, out_loss,
-                        out_z, out_stats, static_cast<float*>(workspace) + fwd + gfl, stream_);
-  }
-  WsLayout w;
-  if (!make_ws(*desc, n, n_target, w)) return fail(CMCD_ERR_BAD_ARG, "bad descriptor%s");
-  const int64_t fwd = align4(w.total_floats), gfl = align4(grad_workspace_floats(*desc, w.HP, n));
-  float* traj = grad_item_mode(*desc, w.T, n) ? static_cast<float*>(workspace) + fwd + gfl : nullptr;
-  return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, fwd * 4, out_loss,
-                      out_z, out_stats, traj, stream_);
-}
-
-int cmcd_bound_var_grad_kept(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
-                             const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
-                             const float* omega, void* workspace, int64_t workspace_bytes, float* grad,
-                             void* stream_) {
-  return var_grad_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, omega, workspace,
-                       workspace_bytes, grad, true, stream_);
-}
-
-int cmcd_stats_merge_device(const double* rows, int32_t count, double* out5, void* stream_) {
-  if (!rows || !out5 || count < 1) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream_), rows, count, out5,
-                     (const uint32_t*)nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
-}
-
-#ifndef CMCD_NO_DIAG_HOOKS
-int cmcd_debug_grad_item(int mode) {
-  if (mode < -1 || mode > 1) return fail(CMCD_ERR_BAD_ARG, "mode must be -1, 0 or 1%s");
-  set_grad_item_override(mode);
-  return CMCD_OK;
-}
-
-int cmcd_profile_enable(int on) {
-  g_prof.on = on != 0;
-  g_prof.used = 0;
-  // the first 512 event pairs are created here, outside any timed region (a 20-step measurement would otherwise pay two
-  // hipEventCreate calls inside every one of its steps)
-  for (; on && g_prof.created < 512; ++g_prof.created) {
-    CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][0]));
-    CMCD_HIP_CHECK(hipEventCreate(&g_prof.ev[g_prof.created][1]));
-  }
-  return CMCD_OK;
-}
-
-int cmcd_profile_collect(double* total_ms, int64_t* launches) {
-  if (!total_ms || !launches) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  double tot = 0.0;
-  for (int i = 0; i < g_prof.used; ++i) {
-    float ms = 0.f;
-    CMCD_HIP_CHECK(hipEventSynchronize(g_prof.ev[i][1]));
-    CMCD_HIP_CHECK(hipEventElapsedTime(&ms, g_prof.ev[i][0], g_prof.ev[i][1]));
-    tot += ms;
-  }
-  *total_ms = tot;
-  *launches = g_prof.used;
-  g_prof.used = 0;
-  return CMCD_OK;
-}
-#endif   // CMCD_NO_DIAG_HOOKS
-
-int cmcd_stats_merge(const double* stats, const int64_t* n_per, int32_t count, double* merged5, double* out3) {
-  if (!stats || !n_per || count < 1 || !merged5 || !out3) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  double acc[CMCD_NSTATS] = {0, 0, 0, -INFINITY, 0};
-  int64_t n = 0;
-  for (int i = 0; i < count; ++i) {
-    const double* b = stats + (int64_t)i * CMCD_NSTATS;
-    acc[0] += b[0]; acc[1] += b[1]; acc[2] += b[2];
-    const double m = fmax(acc[3], b[3]);
-    const double sa = (acc[3] > -INFINITY && m < INFINITY) ? acc[4] * exp(acc[3] - m) : (acc[3] == m ? acc[4] : 0.0);
-    const double sb = (b[3] > -INFINITY && m < INFINITY) ? b[4] * exp(b[3] - m) : (b[3] == m ? b[4] : 0.0);
-    acc[3] = m; acc[4] = sa + sb;
-    n += n_per[i];
-  }
-  if (n < 1) return fail(CMCD_ERR_BAD_ARG, "no particles%s");
-  memcpy(merged5, acc, sizeof(acc));
-  const double mean = acc[1] / (double)n;
-  out3[0] = mean;
-  out3[1] = acc[2] / (double)n - mean * mean;        // var(ddof=0); inf - inf = NaN like the reference
-  out3[2] = acc[3] + log(acc[4]) - log((double)n);   // logsumexp(-l) - log n
-  return CMCD_OK;
-}
-
-}  // extern "C"

@@ -50,7 +50,8 @@ def test_boundary_library_exports_exactly_the_boundary_header():
 
 def test_boundary_only_build_exports_no_hooks(tmp_path):
     """-DCMCD_NO_DIAG_HOOKS (CMCD_DIAG_HOOKS=0 python -m cmcd_amd.build): every symbol of the hooks' header is gone from the three
-    translation units that define them, every boundary symbol they define is still there (checked on the objects: no link, no GPU)."""
+    translation units that define them (cmcd_api.hip, which holds the entry points, cmcd_coop.hip and cmcd_uha.hip),
+    every boundary symbol they define is still there (checked on the objects: no link, no GPU)."""
     import subprocess
     from cmcd_amd import build
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -58,7 +59,7 @@ def test_boundary_only_build_exports_no_hooks(tmp_path):
         pytest.skip("hipcc not installed")
     diag = set(declared_functions("cmcd_hip_diag.h"))
     seen = set()
-    for src in ("cmcd_kernels.hip", "cmcd_coop.hip"):       # (cmcd_uha.hip holds one more hook behind the same guard)
+    for src in ("cmcd_api.hip", "cmcd_coop.hip"):       # (cmcd_uha.hip holds one more hook behind the same guard)
         obj = tmp_path / (src + ".o")
         subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-DCMCD_NO_DIAG_HOOKS", "-I",
                         os.path.join(ROOT, "include"), "-I", build.CSRC, "-Wno-format-security"] + build.EXTRA_FLAGS.get(src, []) +
