@@ -101,6 +101,11 @@ def lib():
                                          C.c_void_p]
         L.cmcd_stats_merge_device.restype = C.c_int
         L.cmcd_stats_merge_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.cmcd_resample_workspace_bytes.restype = C.c_int64
+        L.cmcd_resample_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        L.cmcd_resample_systematic.restype = C.c_int
+        L.cmcd_resample_systematic.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # measurement / diagnostic hooks (include/cmcd_hip_diag.h): absent from a boundary-only build (-DCMCD_NO_DIAG_HOOKS)
         global HAS_DIAG
         HAS_DIAG = hasattr(L, "cmcd_profile_enable")

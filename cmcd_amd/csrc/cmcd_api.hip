@@ -631,6 +631,28 @@ int cmcd_stats_merge(const double* stats, const int64_t* n_per, int32_t count, d
   return CMCD_OK;
 }
 
+int64_t cmcd_resample_workspace_bytes(int64_t n, int32_t groups) {
+  if (n < 1 || n > INT32_MAX || groups < 1 || n % groups != 0 || n / groups > kResampleMaxGroup) return 0;
+  return resample_workspace_bytes(n);
+}
+
+int cmcd_resample_systematic(const float* loss, const float* z, int64_t n, int32_t dim, int32_t groups, uint32_t seed,
+                             void* workspace, int64_t workspace_bytes, int32_t* out_index, float* out_z, double* out_stats,
+                             void* stream_) {
+  if (!loss || !out_stats) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > INT32_MAX) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");   // out_index holds int32 row numbers
+  if (groups < 1) return fail(CMCD_ERR_BAD_ARG, "groups must be >= 1%s");
+  if (n % groups != 0) return fail(CMCD_ERR_BAD_ARG, "n must be a multiple of groups%s");
+  if (out_z && !z) return fail(CMCD_ERR_BAD_ARG, "out_z needs z%s");
+  if (z && dim < 1) return fail(CMCD_ERR_BAD_ARG, "dim must be >= 1%s");
+  if (n / groups > kResampleMaxGroup)
+    return fail(CMCD_ERR_UNSUPPORTED, "groups of more than 2^20 particles are not resampled (got %s%lld)", "", n / groups);
+  int rc = check_workspace(workspace, workspace_bytes, resample_workspace_bytes(n));
+  if (rc != CMCD_OK) return rc;
+  return resample_launch(loss, z, n, dim, groups, seed, workspace, out_index, out_z, out_stats,
+                         static_cast<hipStream_t>(stream_));
+}
+
 #ifndef CMCD_NO_DIAG_HOOKS   // include/cmcd_hip_diag.h: compiled out of a boundary-only build
 const char* cmcd_last_kernel_name(void) { return g_kernel_name; }
 

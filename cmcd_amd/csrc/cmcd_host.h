@@ -1,5 +1,5 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers).  Not included by the other translation units: their seams are in
+// trajectory and merge kernels with their launchers) and cmcd_resample.hip.  Not included by the other translation units: their seams are in
 // cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,5 +35,14 @@ void launch_finalize(const double* partials, int32_t count, double* out5, hipStr
                      uint32_t stamp);
 void launch_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
                             hipStream_t stream);
+
+// cmcd_resample.hip: importance statistics + systematic resampling, one workgroup per group of n / groups rows, one launch.
+// The group is walked in chunks of kResampleChunk rows with a float64 running sum carried between them.
+constexpr int kResampleChunk = 1024;
+constexpr int64_t kResampleMaxGroup = int64_t(1) << 20;   // rows per group the entry point accepts
+int64_t resample_workspace_bytes(int64_t n);
+// the arguments are cmcd_resample_systematic's, already checked; out_index / out_z / z nullable
+int resample_launch(const float* loss, const float* z, int64_t n, int32_t dim, int32_t groups, uint32_t seed, void* workspace,
+                    int32_t* out_index, float* out_z, double* out_stats, hipStream_t stream);
 
 }  // namespace cmcd

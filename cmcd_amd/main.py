@@ -157,7 +157,7 @@ def main(config):
     import torch.distributed as dist
     from . import boundingmachine as bm
     from . import mcdboundingmachine as mcdbm
-    from . import opt, parallel, utils
+    from . import opt, parallel, resample, utils
     from .model_handler import load_model
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -232,6 +232,9 @@ def main(config):
     final_elbo, final_ln_Z = utils.log_final_losses(eval_losses.cpu())
     say("Done training, got ELBO %.2f." % final_elbo)
     say("Done training, got ln Z %.2f." % final_ln_Z)
+    ess = utils.log_importance_diagnostics(eval_losses)
+    say("Importance weights behind ln Z: ESS %.1f (+- %.1f) of %d samples per group (%.1f %%)." % (
+        ess["ess"], ess["ess_std"], config.n_samples, 100.0 * ess["ess_frac"]))
     if config.use_ema:
         eval_losses_ema, samples_ema = utils.sample(config, config.n_samples, config.n_input_dist_seeds, ema_params, unflatten,
                                           params_fixed, log_prob_model, loss_fn, eval_seeds, log_prefix="eval")
@@ -248,6 +251,13 @@ def main(config):
             say("W2%s to the target %.4f (+- %.4f); between two target draws %.4f (+- %.4f)" % (
                 prefix, w2["w2_dist" + prefix], w2["w2_dist_std" + prefix], w2["self_w2_dist" + prefix],
                 w2["self_w2_dist_std" + prefix]))
+            # the same cloud importance-resampled within each seed group (weights exp(-loss), systematic scheme)
+            resampled, _, _ = resample.resample(eval_losses_ema if prefix else eval_losses, cloud,
+                                                groups=config.n_input_dist_seeds, seed=config.seed)
+            w2 = utils.calculate_W2_distances(resampled, tgt, other, config.n_samples, config.n_input_dist_seeds,
+                                              config.n_samples, log_prefix=prefix)
+            say("W2%s of the resampled cloud to the target %.4f (+- %.4f)" % (
+                prefix, w2["w2_dist" + prefix], w2["w2_dist_std" + prefix]))
     if config.save_params and rank == 0:
         utils.save_params(config.save_params, params_flat, unflatten)
     if dist.is_initialized():

@@ -32,6 +32,26 @@ def log_final_losses(eval_losses, log_prefix=""):
 log_final_losses.last = {}
 
 
+def log_importance_diagnostics(eval_losses, log_prefix=""):
+    """eval_losses: [n_input_dist_seeds, n_samples] DEVICE tensor -> the effective sample size of the importance weights
+    exp(-loss) behind each group's ln Z, as mean and standard deviation (ddof = 0) over the groups, absolute and as a
+    fraction of n_samples.  One launch (cmcd_amd.resample.importance_stats); the reference reports no such figure."""
+    from . import resample
+    n_groups, n_samples = eval_losses.shape
+    ess = resample.importance_stats(eval_losses, groups=n_groups)["ess"]
+    out = {
+        f"ess{log_prefix}": float(ess.mean()),
+        f"ess_std{log_prefix}": float(ess.std(unbiased=False)),
+        f"ess_frac{log_prefix}": float(ess.mean()) / n_samples,
+        f"ess_frac_std{log_prefix}": float(ess.std(unbiased=False)) / n_samples,
+    }
+    log_importance_diagnostics.last = out
+    return out
+
+
+log_importance_diagnostics.last = {}
+
+
 def sample(info, n_samples, n_input_dist_seeds, params_flat, unflatten, params_fixed, log_prob_model, loss_fn,
            eval_seeds, log_prefix=""):
     """/root/reference/src/opt.py:167-197 -> (elbos [n_input_dist_seeds][n_samples], zs [n*m, dim]).

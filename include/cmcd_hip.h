@@ -281,6 +281,26 @@ int cmcd_stats_merge_device(const double* rows, int32_t count, double* out5, voi
 int cmcd_stats_merge(const double* stats, const int64_t* n_per, int32_t count,
                      double* merged5, double* out3);
 
+/* ---- Importance diagnostics and systematic resampling of the weighted particle system an entry point returned:
+ * loss[n] and z[n, dim] with weights w_j = exp(-loss_j).  No analogue in the reference, which stops at the unweighted z and
+ * logsumexp(-loss); the arithmetic is restated in float64 NumPy in tests/test_gpu_resample.py.
+ * The n rows are `groups` consecutive groups of m = n / groups rows (the n_input_dist_seeds x n_samples layout of the
+ * evaluation); each group is treated on its own, all sums in float64 and in a fixed order (same arguments, same bits):
+ *   M = max(-loss) over the finite entries, w_j = exp(-loss_j - M) (a loss of +inf weighs 0), S1 = sum w, S2 = sum w^2
+ *   out_stats[g] = {number of finite losses, ln Z = M + log S1 - log m, ESS = S1^2 / S2, max_j w_j / S1, diverged}
+ *   a group holding a NaN or -inf loss is diverged: {NaN, NaN, NaN, NaN, 1} and the identity as ancestors;
+ *   a group without a finite loss: {0, -inf, 0, 0, 0} and the identity as ancestors.
+ * Systematic resampling: u_g = word g of jax.random.uniform(PRNGKey(seed), (groups,)) (Threefry, as everywhere in this
+ * library), thresholds t_k = (k + u_g) / m, ancestor a_k = min{ j : C_j > t_k } with C the inclusive cumulative sum of w / S1,
+ * never past the last row of positive weight.  out_index[n] (int32, nullable) receives the ancestors as global row numbers,
+ * out_z[n, dim] (nullable; needs z, must not overlap it) the rows z[a_k, :].  With both null only out_stats is written.
+ * m <= 2^20 (CMCD_ERR_UNSUPPORTED above), n < 2^31.  One launch on `stream`, no host synchronisation, no allocation: it can be
+ * captured into a hipGraph behind the forward call that produced loss and z.  All pointers [device]. */
+int64_t cmcd_resample_workspace_bytes(int64_t n, int32_t groups);   /* 0 on bad arguments */
+int cmcd_resample_systematic(const float* loss, const float* z, int64_t n, int32_t dim, int32_t groups, uint32_t seed,
+                             void* workspace, int64_t workspace_bytes, int32_t* out_index, float* out_z,
+                             double* out_stats /*[groups][5]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,9 @@ def evaluate(p, tag):
     e, z = utils.log_final_losses(elbos.cpu())
     d = utils.log_final_losses.last
     print("%s: ELBO %.4f (+- %.4f)   ln Z %.4f (+- %.4f)" % (tag, e, d["elbo_final_std"], z, d["final_ln_Z_std"]))
+    ess = utils.log_importance_diagnostics(elbos)
+    print("%s: ESS %.1f (+- %.1f) of %d samples per group (%.1f %%)" % (tag, ess["ess"], ess["ess_std"], cfg.n_samples,
+                                                                     100.0 * ess["ess_frac"]))
 
 
 evaluate(flat, "before")
