@@ -91,3 +91,79 @@ def lgcp_counts_fixture():
     """The 40x40 bin counts of the Finnish pines point set (tests/golden/lgcp_bin_counts.npy: data)."""
     import os
     return np.load(os.path.join(os.path.dirname(__file__), "golden", "lgcp_bin_counts.npy"))
+
+
+def check_stats(stats, losses, tag=""):
+    """The five on-device statistics `{n_finite, sum l, sum l^2, max(-l), sum exp(-l - max)}` against oracle.cmcd_oracle.stats5
+    semantics on the losses the device returned, cast to float64 (what the kernels reduce: the check isolates the reduction
+    from the chain's round-off), with the three sums taken by math.fsum so that the reference carries no order error.
+      * n_finite and the maximum: exactly equal;
+      * sum l, sum l^2: exactly equal when not finite (a +inf loss gives +inf, never NaN); finite: within
+        (n + 1024) 2^-53 sum |term|, the worst case of ANY float64 summation order (Higham, Accuracy and Stability, 4.2:
+        (n - 1) u sum |x_i| to first order; the 1024 absorbs the higher-order terms);
+      * sum exp: within (5 n + 1024) 2^-53 max(1, want) — each exp(x), x <= 0, carries at most (|x| e^x + 3 e^x) 2^-53
+        < 4 2^-53 absolute, the per-record rescale the same again (together < 5 n 2^-53 after the common factor), the
+        summation order n 2^-53 sum; exactly 0.0 for a batch of +inf losses only;
+      * what callers derive: ln Z through mcdboundingmachine.ln_z_from_stats and parallel.finalize within 1e-9 absolute of
+        oracle.ln_z (exactly -inf for an all-+inf batch), finalize's mean / variance / n_finite from the same bounds.
+    The bounds are derived, not measured: a case beyond them is a finding about a record writer or a merge.
+    -> dict of the observed errors relative to their scale (rel_sum, rel_sumsq, rel_exp, lnz_err)."""
+    import math
+
+    import torch
+
+    from cmcd_amd import mcdboundingmachine as mcdbm
+    from cmcd_amd import parallel
+    u = 2.0 ** -53
+    st = torch.as_tensor(stats).detach().to("cpu", torch.float64).reshape(5)
+    got = st.numpy()
+    l = np.asarray(torch.as_tensor(losses).detach().cpu().numpy() if hasattr(losses, "detach") else losses, np.float64).ravel()
+    n = l.size
+    assert n >= 1 and not np.isnan(l).any() and not (l == -np.inf).any(), f"{tag}: stats5 reference needs losses in (-inf, +inf]"
+    fin = np.isfinite(l)
+    want0, want3 = float(fin.sum()), float(np.max(-l))
+    assert got[0] == want0, f"{tag}: n_finite {got[0]} != {want0}"
+    assert got[3] == want3, f"{tag}: max(-loss) {got[3]!r} != {want3!r}"
+    rep = dict(n=n, n_inf=int(n - want0), rel_sum=0.0, rel_sumsq=0.0, rel_exp=0.0, lnz_err=0.0)
+    terms = {1: l[fin], 2: l[fin] * l[fin]}
+    for k, name in ((1, "rel_sum"), (2, "rel_sumsq")):
+        if not fin.all():
+            assert got[k] == np.inf, f"{tag}: stats[{k}] = {got[k]!r} with a +inf loss in the batch, want +inf"
+            continue
+        want, mag = math.fsum(terms[k]), math.fsum(np.abs(terms[k]))
+        bound = (n + 1024) * u * mag
+        assert abs(got[k] - want) <= bound, f"{tag}: stats[{k}] = {got[k]!r}, want {want!r}: off by {abs(got[k] - want):.3e} > {bound:.3e}"
+        rep[name] = abs(got[k] - want) / mag if mag > 0 else 0.0
+    if want0 == 0:
+        want4 = 0.0
+        assert got[4] == 0.0, f"{tag}: stats[4] = {got[4]!r} for a batch of +inf losses, want 0.0"
+    else:
+        want4 = math.fsum(np.exp(-l[fin] - want3))
+        bound = (5 * n + 1024) * u * max(1.0, want4)
+        assert abs(got[4] - want4) <= bound, f"{tag}: stats[4] = {got[4]!r}, want {want4!r}: off by {abs(got[4] - want4):.3e} > {bound:.3e}"
+        rep["rel_exp"] = abs(got[4] - want4) / max(1.0, want4)
+    # what the callers derive from the five numbers
+    lnz_ref = orc.ln_z(l)
+    fz = parallel.finalize(st, n)
+    for name, lnz in (("ln_z_from_stats", float(mcdbm.ln_z_from_stats(st, n))), ("parallel.finalize", float(fz["ln_z"]))):
+        if want0 == 0:
+            assert lnz == -np.inf, f"{tag}: {name} = {lnz!r} for a batch of +inf losses, want -inf"
+        else:
+            assert abs(lnz - lnz_ref) <= 1e-9, f"{tag}: {name} = {lnz!r}, want {lnz_ref!r}"
+            rep["lnz_err"] = max(rep["lnz_err"], abs(lnz - lnz_ref))
+    assert float(fz["n_finite"]) == want0, f"{tag}: finalize n_finite"
+    mean, var = float(fz["mean"]), float(fz["var"])
+    if not fin.all():
+        assert mean == np.inf and math.isnan(var), f"{tag}: finalize mean / var = {mean!r} / {var!r} with a +inf loss, want inf / nan"
+    else:
+        s1, a1, s2 = math.fsum(l), math.fsum(np.abs(l)), math.fsum(l * l)
+        m_ref = s1 / n
+        assert abs(mean - m_ref) <= ((n + 1024) * u * a1 + 2 * u * abs(s1)) / n, f"{tag}: finalize mean {mean!r}, want {m_ref!r}"
+        # var = s2 / n - mean^2 in float64: the two sums' bounds, plus the rounding of the quotient, the square and the difference
+        v_ref = math.fsum((l - m_ref) ** 2) / n
+        tol = (n + 1024) * u * (s2 + 2 * abs(m_ref) * a1) / n + 8 * u * (s2 / n + m_ref * m_ref)
+        if abs(v_ref) + tol < 1e7:
+            assert abs(var - v_ref) <= tol, f"{tag}: finalize var {var!r}, want {v_ref!r} (tolerance {tol:.3e})"
+        elif v_ref - tol > 1e7:
+            assert var == 1e7, f"{tag}: finalize var {var!r}, want the clip 1e7"
+    return rep

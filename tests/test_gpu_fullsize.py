@@ -12,7 +12,7 @@ from cmcd_amd import mcdboundingmachine as mcdbm
 from cmcd_amd import parallel, synthetic, utils
 from oracle import cmcd_oracle as orc
 
-from helpers import compare_losses, run_oracle
+from helpers import check_stats, compare_losses, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +35,7 @@ def test_north_star_full_batch_against_oracle(hip_lib, param_set):
     assert rep["n_inf"] > 0                                     # init_sigma = 60 leaves particles beyond the floor
     lh = losses.double().cpu().numpy()
     assert abs(orc.ln_z(lh) - orc.ln_z(l_ref)) < 0.05           # BASELINE.json's ln Z bar
-    np.testing.assert_allclose(stats.cpu().numpy()[[0, 3]], orc.stats5(lh)[[0, 3]], rtol=1e-12)
+    check_stats(stats, losses, "config 3 full")                   # all five against float64, n_finite and the maximum exactly
     assert abs(float(mcdbm.ln_z_from_stats(stats, 2000)) - orc.ln_z(lh)) < 1e-9
 
 
