@@ -106,6 +106,17 @@ def lib():
         L.cmcd_resample_systematic.restype = C.c_int
         L.cmcd_resample_systematic.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
                                                C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmcd_sinkhorn_workspace_bytes.restype = C.c_int64
+        L.cmcd_sinkhorn_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        L.cmcd_sinkhorn_setup.restype = C.c_int
+        L.cmcd_sinkhorn_setup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
+        L.cmcd_sinkhorn_iterate.restype = C.c_int
+        L.cmcd_sinkhorn_iterate.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.cmcd_sinkhorn_cost.restype = C.c_int
+        L.cmcd_sinkhorn_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
         # measurement / diagnostic hooks (include/cmcd_hip_diag.h): absent from a boundary-only build (-DCMCD_NO_DIAG_HOOKS)
         global HAS_DIAG
         HAS_DIAG = hasattr(L, "cmcd_profile_enable")

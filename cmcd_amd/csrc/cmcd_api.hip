@@ -653,6 +653,55 @@ int cmcd_resample_systematic(const float* loss, const float* z, int64_t n, int32
                          static_cast<hipStream_t>(stream_));
 }
 
+// the shape checks the three cmcd_sinkhorn_* calls share; 0 = fine
+static int check_sinkhorn_shape(int64_t n, int32_t dim, int32_t groups) {
+  if (n < 2) return fail(CMCD_ERR_BAD_ARG, "n must be >= 2%s");
+  if (dim < 1) return fail(CMCD_ERR_BAD_ARG, "dim must be >= 1%s");
+  if (groups < 1) return fail(CMCD_ERR_BAD_ARG, "groups must be >= 1%s");
+  if (n > kSinkhornMaxN)
+    return fail(CMCD_ERR_UNSUPPORTED, "clouds of more than 8192 points are not solved (got %s%lld)", "", n);
+  if (groups > kSinkhornMaxGroups)
+    return fail(CMCD_ERR_UNSUPPORTED, "more than 65535 problems per call are not solved (got %s%lld)", "", groups);
+  return CMCD_OK;
+}
+
+int64_t cmcd_sinkhorn_workspace_bytes(int64_t n, int32_t dim, int32_t groups) {
+  if (n < 2 || n > kSinkhornMaxN || dim < 1 || groups < 1 || groups > kSinkhornMaxGroups) return 0;
+  return sinkhorn_workspace_bytes(n, groups);
+}
+
+int cmcd_sinkhorn_setup(const double* x, const double* y, const double* a, const double* b, int64_t n, int32_t dim,
+                        int32_t groups, double reg, void* workspace, int64_t workspace_bytes, void* stream_) {
+  if (!x || !y) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  int rc = check_sinkhorn_shape(n, dim, groups);
+  if (rc != CMCD_OK) return rc;
+  if (!(reg > 0.0) || reg > 1.79769313486231570815e308) return fail(CMCD_ERR_BAD_ARG, "reg must be positive and finite%s");
+  if ((rc = check_workspace(workspace, workspace_bytes, sinkhorn_workspace_bytes(n, groups))) != CMCD_OK) return rc;
+  return sinkhorn_setup_launch(x, y, a, b, n, dim, groups, reg, workspace, static_cast<hipStream_t>(stream_));
+}
+
+int cmcd_sinkhorn_iterate(int64_t n, int32_t dim, int32_t groups, int32_t first_iteration, int32_t count,
+                          int32_t num_iter_max, double stop_thr, void* workspace, int64_t workspace_bytes,
+                          int32_t* done_flags, void* stream_) {
+  int rc = check_sinkhorn_shape(n, dim, groups);
+  if (rc != CMCD_OK) return rc;
+  if (num_iter_max < 1 || num_iter_max == INT32_MAX) return fail(CMCD_ERR_BAD_ARG, "num_iter_max out of range%s");
+  if (first_iteration < 0 || count < 0 || count > num_iter_max - first_iteration)
+    return fail(CMCD_ERR_BAD_ARG, "iterations must lie in [0, num_iter_max]%s");
+  if ((rc = check_workspace(workspace, workspace_bytes, sinkhorn_workspace_bytes(n, groups))) != CMCD_OK) return rc;
+  return sinkhorn_iterate_launch(n, groups, first_iteration, count, num_iter_max, stop_thr, workspace, done_flags,
+                                 static_cast<hipStream_t>(stream_));
+}
+
+int cmcd_sinkhorn_cost(const double* x, const double* y, int64_t n, int32_t dim, int32_t groups, void* workspace,
+                       int64_t workspace_bytes, double* out, int32_t* done_flags, void* stream_) {
+  if (!x || !y || !out) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  int rc = check_sinkhorn_shape(n, dim, groups);
+  if (rc != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, sinkhorn_workspace_bytes(n, groups))) != CMCD_OK) return rc;
+  return sinkhorn_cost_launch(x, y, n, dim, groups, workspace, out, done_flags, static_cast<hipStream_t>(stream_));
+}
+
 #ifndef CMCD_NO_DIAG_HOOKS   // include/cmcd_hip_diag.h: compiled out of a boundary-only build
 const char* cmcd_last_kernel_name(void) { return g_kernel_name; }
 

@@ -1,5 +1,5 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers) and cmcd_resample.hip.  Not included by the other translation units: their seams are in
+// trajectory and merge kernels with their launchers), cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
 // cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,5 +44,19 @@ int64_t resample_workspace_bytes(int64_t n);
 // the arguments are cmcd_resample_systematic's, already checked; out_index / out_z / z nullable
 int resample_launch(const float* loss, const float* z, int64_t n, int32_t dim, int32_t groups, uint32_t seed, void* workspace,
                     int32_t* out_index, float* out_z, double* out_stats, hipStream_t stream);
+
+// cmcd_sinkhorn.hip: batched float64 Sinkhorn between equal-size clouds, grid (row tiles, problems), one launch per iteration.
+constexpr int kSinkhornRows = 64;          // rows of K per workgroup
+constexpr int kSinkhornThreads = 256;
+constexpr int64_t kSinkhornMaxN = 8192;    // v[n] stays in LDS: 64 KiB of doubles
+constexpr int32_t kSinkhornMaxGroups = 65535;   // gridDim.y
+int64_t sinkhorn_workspace_bytes(int64_t n, int32_t groups);
+// the arguments are those of the cmcd_sinkhorn_* entry points, already checked; a / b / done_flags nullable
+int sinkhorn_setup_launch(const double* x, const double* y, const double* a, const double* b, int64_t n, int32_t dim,
+                          int32_t groups, double reg, void* workspace, hipStream_t stream);
+int sinkhorn_iterate_launch(int64_t n, int32_t groups, int32_t first_iteration, int32_t count, int32_t num_iter_max,
+                            double stop_thr, void* workspace, int32_t* done_flags, hipStream_t stream);
+int sinkhorn_cost_launch(const double* x, const double* y, int64_t n, int32_t dim, int32_t groups, void* workspace, double* out,
+                         int32_t* done_flags, hipStream_t stream);
 
 }  // namespace cmcd

@@ -245,19 +245,24 @@ def main(config):
         tgt = torch.from_numpy(sample_from_target_fn(1, n)).to(device)
         other = torch.from_numpy(sample_from_target_fn(2, n)).to(device)
         clouds = [("", samples)] + ([("_ema", samples_ema)] if config.use_ema else [])
+        self_w2 = None
         for prefix, cloud in clouds:
+            # one batched solve (cmcd_amd.sinkhorn) per cloud: the cloud as it is, the same cloud importance-resampled within
+            # each seed group (weights exp(-loss), systematic scheme), the cloud weighted by softmax(-loss), and — once —
+            # the two target draws against each other
+            cloud_losses = eval_losses_ema if prefix else eval_losses
+            resampled, _, _ = resample.resample(cloud_losses, cloud, groups=config.n_input_dist_seeds, seed=config.seed)
             w2 = utils.calculate_W2_distances(cloud, tgt, other, config.n_samples, config.n_input_dist_seeds,
-                                              config.n_samples, log_prefix=prefix)
+                                              config.n_samples, log_prefix=prefix, losses=cloud_losses,
+                                              also={"resampled": resampled}, self_w2=self_w2)
+            self_w2 = (w2["self_w2_dist" + prefix], w2["self_w2_dist_std" + prefix])
             say("W2%s to the target %.4f (+- %.4f); between two target draws %.4f (+- %.4f)" % (
                 prefix, w2["w2_dist" + prefix], w2["w2_dist_std" + prefix], w2["self_w2_dist" + prefix],
                 w2["self_w2_dist_std" + prefix]))
-            # the same cloud importance-resampled within each seed group (weights exp(-loss), systematic scheme)
-            resampled, _, _ = resample.resample(eval_losses_ema if prefix else eval_losses, cloud,
-                                                groups=config.n_input_dist_seeds, seed=config.seed)
-            w2 = utils.calculate_W2_distances(resampled, tgt, other, config.n_samples, config.n_input_dist_seeds,
-                                              config.n_samples, log_prefix=prefix)
             say("W2%s of the resampled cloud to the target %.4f (+- %.4f)" % (
-                prefix, w2["w2_dist" + prefix], w2["w2_dist_std" + prefix]))
+                prefix, w2["w2_dist_resampled" + prefix], w2["w2_dist_resampled_std" + prefix]))
+            say("W2%s of the weighted cloud to the target %.4f (+- %.4f)" % (
+                prefix, w2["w2_weighted_dist" + prefix], w2["w2_weighted_dist_std" + prefix]))
     if config.save_params and rank == 0:
         utils.save_params(config.save_params, params_flat, unflatten)
     if dist.is_initialized():

@@ -146,12 +146,58 @@ def W2_distance(x, y, reg=0.01, num_iter_max=10000, stop_thr=1e-16):
     return float((P * M).sum())
 
 
+def _is_device(t):
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
 def calculate_W2_distances(samples, target_samples, other_target_samples, n_samples, n_input_dist_seeds, n_sinkhorn,
-                           log_prefix=""):
-    """/root/reference/src/utils.py:251-282, returning the four numbers it logs to W&B."""
+                           log_prefix="", batched=None, losses=None, also=None, self_w2=None):
+    """/root/reference/src/utils.py:251-282, returning the four numbers it logs to W&B.
+
+    `batched=None` takes the device path when all three clouds are device tensors: cloud -> target and target -> other target
+    for every seed group are then solved in ONE `sinkhorn.w2_batched` call (float64 HIP, same arithmetic) instead of
+    2 x n_input_dist_seeds `W2_distance` calls; `batched=False` and CPU inputs keep the loop.  Device path only:
+    `losses` ([n_input_dist_seeds * n_samples], the evaluation's) adds `w2_weighted_dist[_std]`: the same metric with the cloud's
+    rows weighted a = softmax(-loss) within each group, in float64 — the importance-weighted cloud without resampling noise
+    (a loss of +inf weighs 0); `also` ({name: cloud}) adds `w2_dist_<name>[_std]` for further clouds against the same target,
+    in the same call; `self_w2` (the (mean, std) an earlier call on the same targets returned) skips the target -> other
+    target problems."""
     import numpy as np
-    w2, self_w2 = [], []
     assert n_sinkhorn <= n_samples
+    if batched is None:
+        batched = _is_device(samples) and _is_device(target_samples) and _is_device(other_target_samples)
+    if batched:
+        from . import sinkhorn
+        G = n_input_dist_seeds
+
+        def groups(t):          # [G * n_samples, d] -> the first n_sinkhorn rows of every group
+            if not _is_device(t):
+                raise RuntimeError("the CMCD hot path runs on a ROCm device only: a cloud is not a device tensor")
+            t = t.detach()
+            return t.reshape(G, n_samples, -1)[:, :n_sinkhorn].to(torch.float64)
+        tgt = groups(target_samples)
+        uniform = torch.full((G, n_sinkhorn), 1.0 / n_sinkhorn, dtype=torch.float64, device=tgt.device)
+        sets = [("w2_dist", groups(samples), tgt, uniform)]
+        if self_w2 is None:
+            sets.append(("self_w2_dist", tgt, groups(other_target_samples), uniform))
+        for name, cloud in (also or {}).items():
+            sets.append((f"w2_dist_{name}", groups(cloud), tgt, uniform))
+        if losses is not None:
+            w = torch.softmax(-groups(losses.reshape(-1, 1))[:, :, 0], dim=1)
+            sets.append(("w2_weighted_dist", sets[0][1], tgt, w))
+        res = sinkhorn.w2_batched(torch.cat([s[1] for s in sets]), torch.cat([s[2] for s in sets]),
+                                  a=torch.cat([s[3] for s in sets]))
+        cost = res["cost"].view(len(sets), G).cpu().numpy()
+        out = {}
+        for row, s in zip(cost, sets):
+            out[f"{s[0]}{log_prefix}"] = float(np.mean(row))
+            out[f"{s[0]}_std{log_prefix}"] = float(np.std(row))
+        if self_w2 is not None:
+            out[f"self_w2_dist{log_prefix}"], out[f"self_w2_dist_std{log_prefix}"] = float(self_w2[0]), float(self_w2[1])
+        return out
+    if losses is not None or also or self_w2 is not None:
+        raise RuntimeError("the CMCD hot path runs on a ROCm device only: losses= / also= / self_w2= belong to the batched path")
+    w2, self_w2 = [], []
     for i in range(n_input_dist_seeds):
         sl = slice(i * n_samples, i * n_samples + n_sinkhorn)
         w2.append(W2_distance(samples[sl], target_samples[sl]))

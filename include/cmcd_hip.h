@@ -301,6 +301,36 @@ int cmcd_resample_systematic(const float* loss, const float* z, int64_t n, int32
                              void* workspace, int64_t workspace_bytes, int32_t* out_index, float* out_z,
                              double* out_stats /*[groups][5]*/, void* stream);
 
+/* ---- Batched entropic optimal transport between equal-size point clouds: the evaluation's Sinkhorn W2
+ * (/root/reference/src/utils.py:207-216, `ot.sinkhorn2(a, b, M / M.max(), reg)`), float64 throughout, `groups` independent
+ * problems per call.  Problem g has clouds x[g][n][dim], y[g][n][dim] and weights a[g][n], b[g][n] (a null pointer = uniform
+ * 1 / n):  M_ij = ||x_i - y_j||^2 / max_ij ||x_i - y_j||^2,  K = exp(-M / reg),  u = v = 1 / n;  iteration `it` = 0, 1, ...:
+ * v <- b / (K^T u), u <- a / (K v), and when it % 10 == 0: err = sum_j (v_j (K^T u)_j - b_j)^2, stop if err < stop_thr; at most
+ * num_iter_max iterations;  cost = sum_ij u_i K_ij v_j M_ij.  The arithmetic is restated in tests/test_gpu_sinkhorn.py.
+ * Three calls share one workspace, whose content is the state of the solve:
+ *   setup    builds K, the initial u and K^T u.  A problem with a non-finite coordinate or weight, or whose points all
+ *            coincide (max M = 0), is finished at once with status 2.
+ *   iterate  enqueues the iterations first_iteration ... first_iteration + count - 1, one launch each (and, when that reaches
+ *            num_iter_max, one more launch that takes the last check and closes the problems at the cap).  Successive calls
+ *            must continue where the previous one stopped.  A finished problem costs its workgroups one load.
+ *            done_flags[groups] (int32, nullable) receives 1 for every finished problem.
+ *   cost     writes out[g] = {cost, iterations carried out, err at the last check (NaN before the first), status} as four
+ *            doubles; status 0 converged, 1 cap reached (or not finished yet), 2 not solvable (cost NaN).
+ * Every sum is taken in an order fixed by n alone (row tiles of 64, workgroups of 256): a problem's bits do not depend on
+ * the other problems of the call, on which of them are finished, or on the stream.  No floating-point atomics.
+ * 2 <= n <= 8192 and groups <= 65535 (CMCD_ERR_UNSUPPORTED above), dim >= 1.  Workspace, with T = ceil(n / 64):
+ *   bytes = 32 groups + 8 (groups n^2 + 5 groups n + 2 groups T n + groups T), rounded up to a multiple of 16.
+ * No call synchronises or allocates; all three can be captured into a hipGraph.  All pointers [device]. */
+int64_t cmcd_sinkhorn_workspace_bytes(int64_t n, int32_t dim, int32_t groups);   /* 0 on bad arguments */
+int cmcd_sinkhorn_setup(const double* x, const double* y, const double* a /*nullable*/, const double* b /*nullable*/, int64_t n,
+                        int32_t dim, int32_t groups, double reg, void* workspace, int64_t workspace_bytes, void* stream);
+int cmcd_sinkhorn_iterate(int64_t n, int32_t dim, int32_t groups, int32_t first_iteration, int32_t count,
+                          int32_t num_iter_max, double stop_thr, void* workspace, int64_t workspace_bytes,
+                          int32_t* done_flags /*[groups], nullable*/, void* stream);
+int cmcd_sinkhorn_cost(const double* x, const double* y, int64_t n, int32_t dim, int32_t groups, void* workspace,
+                       int64_t workspace_bytes, double* out /*[groups][4]*/, int32_t* done_flags /*[groups], nullable*/,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
