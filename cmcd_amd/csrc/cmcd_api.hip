@@ -216,6 +216,24 @@ static int check_workspace(const void* ptr, int64_t bytes, int64_t need) {
   return CMCD_OK;
 }
 
+// every leaf this configuration reads must lie inside params_flat
+static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_params) {
+  const int64_t K = d.nbridges, D = d.dim, E = d.emb_dim, DIN = net_in_dim(d), IN = DIN + E;
+  auto need = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
+  bool ok = need(lay.vd_mean, D) && need(lay.vd_logdiag, D) && need(lay.eps, 1) && need(lay.mgridref_y, d.ngrid + 1) &&
+            (d.mode != CMCD_MODE_CAIS_UHA_SN || need(lay.gamma, 1));
+  if (d.mode == CMCD_MODE_ULA) {
+    // no network leaves
+  } else if (d.arch == CMCD_ARCH_GEFFNER)
+    ok = ok && need(lay.g_emb, K * E) && need(lay.g_factor, 1) && need(lay.g_w1, IN * IN) && need(lay.g_b1, IN) &&
+         need(lay.g_w2, IN * IN) && need(lay.g_b2, IN) && need(lay.g_w3, IN * D) && need(lay.g_b3, D);
+  else
+    ok = ok && need(lay.d_phase, 64) && need(lay.d_tw1, 128 * 64) && need(lay.d_tb1, 64) && need(lay.d_tw2, 64 * 64) &&
+         need(lay.d_tb2, 64) && need(lay.d_sw1, (DIN + 64) * 64) && need(lay.d_sb1, 64) && need(lay.d_sw2, 64 * 64) &&
+         need(lay.d_sb2, 64) && need(lay.d_sw3, 64 * D) && need(lay.d_sb3, D);
+  return ok;
+}
+
 // many_gmm: target_consts = {scale, means[n_mixes][2]} (any other target: nothing to check here)
 static int check_many_gmm(const cmcd_desc& d, const float* target_consts, int64_t n_target) {
   if (d.target == CMCD_TARGET_MANY_GMM &&
@@ -227,10 +245,11 @@ static int check_many_gmm(const cmcd_desc& d, const float* target_consts, int64_
 // ------------------------------------------------------------------------------------------
 // the plan of one call: what runs (effective descriptor) and where it lives in the caller's workspace
 //   forward:     [forward tables + statistics records]
+//   reverse:     the forward layout (same tables, one statistics record per 16-particle tile); overdamped modes, no lgcp
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
 // ------------------------------------------------------------------------------------------
-enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD };
+enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE };
 
 struct CallPlan {
   cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
@@ -266,6 +285,14 @@ static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKin
   }
   p.total = p.need = p.fwd * 4;
   if (kind == PLAN_FORWARD) return CMCD_OK;
+  if (kind == PLAN_REVERSE) {
+    if (d.mode == CMCD_MODE_CAIS_UHA_SN)
+      return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain exists for the overdamped modes only (MCD_CAIS_UHA_sn has no reverse kernel)%s");
+    if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain has no lgcp kernel%s");
+    if (!reverse_available(d, p.w.T))
+      return fail(CMCD_ERR_UNSUPPORTED, "no reverse-chain kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    return CMCD_OK;
+  }
 
   const WsLayout& w = p.w;
   int64_t gws, traj_fl = kept_traj_floats(d, n), scratch_fl = 0;
@@ -336,25 +363,10 @@ static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
   if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
   const cmcd_desc& d = *desc;
-  const int64_t K = d.nbridges, D = d.dim, E = d.emb_dim, DIN = net_in_dim(d), IN = DIN + E;
+  const int64_t K = d.nbridges, D = d.dim;
   const bool uha = d.mode == CMCD_MODE_CAIS_UHA_SN;
 
-  // every leaf this configuration reads must lie inside params_flat
-  auto need = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
-  bool ok = need(lay->vd_mean, D) && need(lay->vd_logdiag, D) && need(lay->eps, 1) &&
-            need(lay->mgridref_y, d.ngrid + 1) && (!uha || need(lay->gamma, 1));
-  if (d.mode == CMCD_MODE_ULA) {
-    // no network leaves
-  } else if (d.arch == CMCD_ARCH_GEFFNER)
-    ok = ok && need(lay->g_emb, K * E) && need(lay->g_factor, 1) && need(lay->g_w1, IN * IN) &&
-         need(lay->g_b1, IN) && need(lay->g_w2, IN * IN) && need(lay->g_b2, IN) && need(lay->g_w3, IN * D) &&
-         need(lay->g_b3, D);
-  else
-    ok = ok && need(lay->d_phase, 64) && need(lay->d_tw1, 128 * 64) && need(lay->d_tb1, 64) &&
-         need(lay->d_tw2, 64 * 64) && need(lay->d_tb2, 64) && need(lay->d_sw1, (DIN + 64) * 64) &&
-         need(lay->d_sb1, 64) && need(lay->d_sw2, 64 * 64) && need(lay->d_sb2, 64) &&
-         need(lay->d_sw3, 64 * D) && need(lay->d_sb3, D);
-  if (!ok) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
   if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
   if (d.target == CMCD_TARGET_LGCP && (!target_consts || n_target != D * D + D + 3))
     return fail(CMCD_ERR_BAD_ARG, "lgcp needs target_consts = {Kinv[d,d], counts[d], mu0, a, lognorm}%s");
@@ -449,6 +461,41 @@ static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
   return CMCD_OK;
 }
 
+// the reverse-time chain: x[n][dim] target draws -> out_w, out_z0, statistics over l := w (cmcd_reverse.hip)
+static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, const float* x, int64_t n,
+                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
+                        int64_t workspace_bytes, float* out_w, float* out_z0, double* out_stats, void* stream_) {
+  // 1. validate
+  int rc = check_desc(desc);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  const cmcd_desc& d = *desc;
+  // 2. plan (refuses the modes and targets without a reverse kernel before the layout is looked at)
+  CallPlan p;
+  if ((rc = make_plan(d, n, n_target, PLAN_REVERSE, false, p)) != CMCD_OK) return rc;
+  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
+  const cmcd_desc& e = p.d;
+  const WsLayout& w = p.w;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  // 3. prep: the forward call's tables, formed by the same launch
+  launch_prep(e, *lay, w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
+  // 4. launch: one statistics record per 16-particle tile
+  double* partials = reinterpret_cast<double*>(ws + w.partials);
+  TrajArgs ta{seeds, params, ws, partials, out_w, out_z0, *lay, w, n, (int32_t)d.nbridges, d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0,
+              e.grad_clipping, nullptr, d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_traj_kernel");
+  if ((rc = reverse_launch(e, w, ta, x, stream)) != CMCD_OK) return rc;
+  // 5. merge the statistics
+  launch_finalize(partials, w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
 // the VarGrad gradient on the tables (and, for work items and lgcp, the trajectory) in the workspace; kept: left there by
 // cmcd_bound_var_forward, otherwise formed here
 static int var_grad_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
@@ -527,6 +574,16 @@ int cmcd_bound_forward_prepared(const cmcd_desc* desc, const cmcd_layout* lay, c
                                 double* out_stats, void* stream_) {
   return forward_impl(desc, lay, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
                       out_loss, out_z, out_stats, stream_, true);
+}
+
+int64_t cmcd_reverse_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_REVERSE); }
+
+int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, const float* x, int64_t n,
+                       const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                       void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, double* out_stats,
+                       void* stream_) {
+  return reverse_impl(desc, lay, seeds, x, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_w,
+                      out_z0, out_stats, stream_);
 }
 
 int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,

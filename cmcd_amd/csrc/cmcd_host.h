@@ -1,5 +1,5 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers), cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
+// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
 // cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +35,12 @@ void launch_finalize(const double* partials, int32_t count, double* out5, hipStr
                      uint32_t stamp);
 void launch_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
                             hipStream_t stream);
+
+// cmcd_reverse.hip: the reverse-time chain of the overdamped modes (target draws x[n][dim] through the backward kernels), one
+// wave per 16-particle tile.  Reads the tables launch_prep left in ta.ws; ta.out_loss receives w, ta.out_z the end state z_0,
+// ta.partials one statistics record per tile (w.n_waves of them) over l := w.  No instance for MCD_CAIS_UHA_sn and lgcp.
+bool reverse_available(const cmcd_desc& d, int T);
+int reverse_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, const float* x, hipStream_t stream);
 
 // cmcd_resample.hip: importance statistics + systematic resampling, one workgroup per group of n / groups rows, one launch.
 // The group is walked in chunks of kResampleChunk rows with a float64 running sum carried between them.

@@ -59,6 +59,7 @@ def get_config():
     c.init_gamma = 10.0         # extra: the reference has no such flag — mcdbm.initialize's default gamma = 10.0 is what
     #                             its main.py always uses (main.py:148-159); only MCD_CAIS_UHA_sn reads gamma
     c.compute_w2 = True         # extra: --noconfig.compute_w2 skips the Sinkhorn W2 block of main.py:248-271 (test harness)
+    c.compute_eubo = True       # extra: --noconfig.compute_eubo skips the reverse-chain diagnostics (EUBO, reverse ln Z / ESS)
     # fields of the reference's config this driver accepts so that its README command lines run unchanged, but whose
     # only legal value here is the default (dds nets are 64-wide, the lgcp posterior is un-whitened, 40 mixtures
     # unless n_mixes says otherwise) or that configure subsystems left out (NICE, W&B, the cluster launcher)
@@ -235,12 +236,32 @@ def main(config):
     ess = utils.log_importance_diagnostics(eval_losses)
     say("Importance weights behind ln Z: ESS %.1f (+- %.1f) of %d samples per group (%.1f %%)." % (
         ess["ess"], ess["ess_std"], config.n_samples, 100.0 * ess["ess_frac"]))
+    # The other half of the diagnostics (no analogue in the reference): exact target draws through the backward kernels.
+    reverse = (config.compute_eubo and sample_from_target_fn is not None and rank == 0 and
+               config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn"))
+    if reverse:
+        from .model_handler import exact_target_draws
+        x_tgt = torch.from_numpy(exact_target_draws(config.model, sample_from_target_fn, 3, n, dim)).to(device)   # (seeds 1, 2: the W2 block)
+
+        def say_reverse(p, forward_elbo, forward_ln_Z, prefix=""):
+            w, _, _ = mcdbm.bound_reverse(eval_seeds, x_tgt, p, unflatten, params_fixed, log_prob_model,
+                                          eps_schedule=config.eps_schedule, grad_clipping=config.grad_clipping)
+            r = utils.log_reverse_diagnostics(w.view(config.n_input_dist_seeds, config.n_samples), log_prefix=prefix)
+            say("Reverse chain%s: EUBO %.2f, reverse ln Z %.2f, reverse ESS %.1f (+- %.1f) of %d (%.1f %%); ln Z bracket "
+                "[ELBO %.2f, EUBO %.2f], forward ln Z %.2f." % (
+                    prefix, r["eubo" + prefix], r["reverse_ln_Z" + prefix], r["reverse_ess" + prefix],
+                    r["reverse_ess_std" + prefix], config.n_samples, 100.0 * r["reverse_ess_frac" + prefix], forward_elbo,
+                    r["eubo" + prefix], forward_ln_Z))
+
+        say_reverse(params_flat, final_elbo, final_ln_Z)
     if config.use_ema:
         eval_losses_ema, samples_ema = utils.sample(config, config.n_samples, config.n_input_dist_seeds, ema_params, unflatten,
                                           params_fixed, log_prob_model, loss_fn, eval_seeds, log_prefix="eval")
         e2, z2 = utils.log_final_losses(eval_losses_ema.cpu(), log_prefix="_ema")
         say("With EMA, got ELBO %.2f." % e2)
         say("With EMA, got ln Z %.2f." % z2)
+        if reverse:
+            say_reverse(ema_params, e2, z2, prefix="_ema")
     if sample_from_target_fn is not None and config.model in ("funnel", "gmm") and rank == 0 and config.compute_w2:   # main.py:248-271
         tgt = torch.from_numpy(sample_from_target_fn(1, n)).to(device)
         other = torch.from_numpy(sample_from_target_fn(2, n)).to(device)

@@ -410,6 +410,47 @@ def bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob, eps_sch
     return losses, z, stats
 
 
+def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """The reverse-time chain (include/cmcd_hip.h: cmcd_bound_reverse): `x[n, dim]`, draws from the target, pushed through the
+    backward kernels of the sampler with the noise of `seeds[n]`.  Returns (w[N] f32, z0[N, dim] f32, stats[5] f64), all
+    device tensors, enqueued asynchronously on the current stream: w is the functional `bound_forward` returns as -loss, on a
+    path drawn from the target's side; the statistics are taken over l := w.  A non-finite row of x gives w = +inf.
+    The reference has no such call.  Overdamped modes on gmm / funnel / many_gmm only (NotImplementedError otherwise)."""
+    plan = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    seeds, n = _inputs(seeds, params_flat)
+    device = params_flat.device
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
+        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, params_fixed[0]):
+        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {params_fixed[0]}]")
+    L = _lib.lib()
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    dev_index, stream, capturing = here
+    nbytes = _nbytes(plan, "cmcd_reverse_workspace_bytes", n)
+    if nbytes <= 0:
+        raise NotImplementedError(_lib.last_error() or "no reverse-chain kernel for this configuration")
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev")
+    _prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
+    consts = log_prob.consts_on(device)
+    w, z0, stats = _outputs(n, params_fixed[0], device)
+    _lib.check(L.cmcd_bound_reverse(
+        C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
+        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), stats.data_ptr(), stream))
+    return w, z0, stats
+
+
+def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E_P[w] >= ln Z, the upper half of the bracket whose lower half is
+    -compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
+    w, z0, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                 eps_schedule=eps_schedule, grad_clipping=grad_clipping)
+    return (stats[1] / w.numel()).to(torch.float32), (w, z0)
+
+
 def compute_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
     """/root/reference/src/mcdboundingmachine.py:183-205 -> (mean(losses), (losses, z))."""
     losses, z, stats = bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob,

@@ -102,6 +102,24 @@ def _many_gmm_sampler(consts, n_mixes):
     return sample
 
 
+def exact_target_draws(model, sampler, seed, n, dim):
+    """n draws (float32 [n, dim]) from the density the kernels EVALUATE for `model`, for the reverse-time chain
+    (mcdboundingmachine.bound_reverse), whose bounds hold only for draws from exactly that density.  The W2 samplers above
+    keep two traits of the reference that make them something else: the gmm sampler draws from the 3-component mixture, not
+    from its flip-symmetrised density (each row is swapped here with probability 1/2), and the funnel sampler scales x by
+    exp(-v / 2) and clips v, where the density has x | v ~ N(0, e^v) and v ~ N(0, 3^2) (drawn here as such)."""
+    g = np.random.default_rng(int(seed))
+    if model == "funnel":
+        v = 3.0 * g.standard_normal((n, 1))
+        return np.concatenate((v, g.standard_normal((n, dim - 1)) * np.exp(v / 2)), axis=1).astype(np.float32)
+    if model == "gmm":
+        x = np.asarray(sampler(g, n), np.float32)
+        return np.ascontiguousarray(np.where(g.random((n, 1)) < 0.5, x, x[:, ::-1]), dtype=np.float32)
+    if model == "many_gmm":
+        return np.ascontiguousarray(sampler(g, (n,)), dtype=np.float32)
+    raise NotImplementedError(f"no exact sampler for target {model!r}")
+
+
 def load_model_funnel(model="funnel", config=None):
     """/root/reference/src/model_handler.py:124-154"""
     d = int(_cfg(config, "funnel_d", 10))

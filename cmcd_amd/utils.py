@@ -52,6 +52,34 @@ def log_importance_diagnostics(eval_losses, log_prefix=""):
 log_importance_diagnostics.last = {}
 
 
+def log_reverse_diagnostics(w_groups, log_prefix=""):
+    """w_groups: [n_input_dist_seeds, n_samples] DEVICE tensor of reverse log-weights (mcdboundingmachine.bound_reverse on
+    draws from the target) -> per group the EUBO mean(w) >= ln Z, the reverse estimate ln Z = -(logsumexp(-w) - log n_samples)
+    and the effective sample size of the reverse importance weights exp(-w); each as mean and standard deviation (ddof = 0)
+    over the groups, the ESS also as a fraction of n_samples.  The ESS and ln Z come from one launch
+    (cmcd_amd.resample.importance_stats, which reads w as a loss); the reference reports no such figures."""
+    from . import resample
+    n_groups, n_samples = w_groups.shape
+    st = resample.importance_stats(w_groups, groups=n_groups)
+    eubo = w_groups.to(torch.float64).mean(dim=1)
+    ln_z, ess = -st["ln_Z"], st["ess"]
+    out = {
+        f"eubo{log_prefix}": float(eubo.mean()),
+        f"eubo_std{log_prefix}": float(eubo.std(unbiased=False)),
+        f"reverse_ln_Z{log_prefix}": float(ln_z.mean()),
+        f"reverse_ln_Z_std{log_prefix}": float(ln_z.std(unbiased=False)),
+        f"reverse_ess{log_prefix}": float(ess.mean()),
+        f"reverse_ess_std{log_prefix}": float(ess.std(unbiased=False)),
+        f"reverse_ess_frac{log_prefix}": float(ess.mean()) / n_samples,
+        f"reverse_ess_frac_std{log_prefix}": float(ess.std(unbiased=False)) / n_samples,
+    }
+    log_reverse_diagnostics.last = out
+    return out
+
+
+log_reverse_diagnostics.last = {}
+
+
 def sample(info, n_samples, n_input_dist_seeds, params_flat, unflatten, params_fixed, log_prob_model, loss_fn,
            eval_seeds, log_prefix=""):
     """/root/reference/src/opt.py:167-197 -> (elbos [n_input_dist_seeds][n_samples], zs [n*m, dim]).

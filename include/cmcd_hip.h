@@ -163,6 +163,40 @@ int cmcd_bound_forward_prepared(const cmcd_desc* desc, const cmcd_layout* lay,
                                 float* out_loss, float* out_z, double* out_stats,
                                 void* stream);
 
+/* ---- The reverse-time chain: draws from the TARGET pushed through the backward kernels of the sampler.  No analogue in the
+ * reference, which runs its chain from q only; the arithmetic is its forward chain's (/root/reference/src/mcd_cais.py:46-89,
+ * mcd_cais_var.py, mcd_over_orig.py:22-56, mcdboundingmachine.py:126-179) walked the other way, restated in float64 NumPy in
+ * tests/test_gpu_reverse.py.  With the schedules beta_i, eps_i, the clip rule, the network s(., i) and q of cmcd_bound_forward
+ * for the same (desc, layout, params) — the same prep tables — and sigma_i = sqrt(2 eps_i), particle p runs
+ *   z_K = x_p;  w = log p(z_K)
+ *   for i = K-1 .. 0:   m_b = z_{i+1} - eps_i gradU(z_{i+1}, beta_i) + eps_i s(z_{i+1}, j)     j = i + 1 (MCD_CAIS_sn, MCD_CAIS_var_sn),
+ *                                                                         j = i (MCD_ULA_sn), no network term (MCD_ULA)
+ *                       z_i = m_b + sigma_i xi_r,  r = K-1-i
+ *                       m_f = z_i - eps_i gradU(z_i, beta_i) - eps_i s(z_i, i)                 (network term: the CAIS modes only)
+ *                       w  += log N(z_i; m_b, sigma_i) - log N(z_{i+1}; m_f, sigma_i)
+ *   w -= log q(z_0)
+ * so w is the functional cmcd_bound_forward returns as -loss, on a path drawn from p(z_K) prod B_i.  E[w] >= ln Z (the EUBO:
+ * with the forward call's ELBO it brackets ln Z), and exp(-w) are the importance weights of the reverse estimate of 1 / Z.
+ * xi_r comes from the forward call's key chain without its first key: (_, gen) = split(PRNGKey(seed)); (C, _) = split(gen);
+ * gen_0 = second(split(C)); step r: (G, H) = split(gen), xi_r = normal(G, (dim,)), gen = second(split(H)).
+ *   x[n*dim] float32 [device], seeds[n] int32 [device]  ->  out_w[n], out_z0[n*dim] = z_0 [device, float32],
+ *   out_stats[5] [device, float64] = the statistics above over l := w (they merge with cmcd_stats_merge[_device]):
+ *   EUBO = out_stats[1] / n;  reverse ln Z = -(out_stats[3] + log out_stats[4] - log n).
+ * A particle whose x row holds a non-finite entry, or whose w comes out NaN, gets w = +inf (weight 0; its z_0 row is
+ * meaningless): the EUBO of such a batch is +inf, never NaN.
+ * Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward; workspace of cmcd_reverse_workspace_bytes (0 where
+ * the call is unsupported).  One kernel form (one wave per 16-particle tile) for the overdamped modes on gmm, funnel (dim 10)
+ * and many_gmm with the nets cmcd_bound_forward's wave-per-tile kernel is built for; MCD_CAIS_UHA_sn, lgcp and other widths:
+ * CMCD_ERR_UNSUPPORTED. */
+int64_t cmcd_reverse_workspace_bytes(const cmcd_desc* desc, int64_t n);
+int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* layout,
+                       const int32_t* seeds, const float* x, int64_t n,
+                       const float* params, int64_t n_params,
+                       const float* target_consts, int64_t n_target,
+                       void* workspace, int64_t workspace_bytes,
+                       float* out_w, float* out_z0, double* out_stats,
+                       void* stream);
+
 /* (Measurement and diagnostic hooks — kernel-time events, the PRNG capture of the parity tests, the probes' switches — are NOT
  * part of this boundary: they are declared in include/cmcd_hip_diag.h and compiled out of the library by
  * -DCMCD_NO_DIAG_HOOKS; a deployment binds nothing of them.) */
