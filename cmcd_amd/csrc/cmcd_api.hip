@@ -246,10 +246,11 @@ static int check_many_gmm(const cmcd_desc& d, const float* target_consts, int64_
 // the plan of one call: what runs (effective descriptor) and where it lives in the caller's workspace
 //   forward:     [forward tables + statistics records]
 //   reverse:     the forward layout (same tables, one statistics record per 16-particle tile); overdamped modes, no lgcp
+//   segment:     the forward layout again (bridges [k0, k1) from a caller-supplied state); overdamped modes, no lgcp
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
 // ------------------------------------------------------------------------------------------
-enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE };
+enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT };
 
 struct CallPlan {
   cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
@@ -291,6 +292,14 @@ static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKin
     if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain has no lgcp kernel%s");
     if (!reverse_available(d, p.w.T))
       return fail(CMCD_ERR_UNSUPPORTED, "no reverse-chain kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    return CMCD_OK;
+  }
+  if (kind == PLAN_SEGMENT) {
+    if (d.mode == CMCD_MODE_CAIS_UHA_SN)
+      return fail(CMCD_ERR_UNSUPPORTED, "chain segments exist for the overdamped modes only (MCD_CAIS_UHA_sn has no segment kernel)%s");
+    if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "chain segments have no lgcp kernel%s");
+    if (!segment_available(d, p.w.T))
+      return fail(CMCD_ERR_UNSUPPORTED, "no segment kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
     return CMCD_OK;
   }
 
@@ -496,6 +505,45 @@ static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
   return CMCD_OK;
 }
 
+// bridges [k0, k1) of the forward chain from the state (z, wpath, key); seeds are read when k0 == 0 (cmcd_segment.hip)
+static int segment_impl(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0, int32_t k1, const int32_t* seeds, int64_t n,
+                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
+                        int64_t workspace_bytes, float* z, float* wpath, uint32_t* key, float* out_lg, double* out_stats,
+                        void* stream_) {
+  // 1. validate
+  int rc = check_desc(desc);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !params || !workspace || !z || !wpath || !key || !out_lg || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  const cmcd_desc& d = *desc;
+  if (k0 < 0 || k0 >= k1 || k1 > d.nbridges)
+    return fail(CMCD_ERR_BAD_ARG, "segment bridges must satisfy 0 <= k0 < k1 <= nbridges (got k1 = %s%lld)", "", k1);
+  if (k0 == 0 && !seeds) return fail(CMCD_ERR_BAD_ARG, "a segment that starts at bridge 0 needs seeds%s");
+  // 2. plan (refuses the modes and targets without a segment kernel before the layout is looked at)
+  CallPlan p;
+  if ((rc = make_plan(d, n, n_target, PLAN_SEGMENT, false, p)) != CMCD_OK) return rc;
+  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
+  const cmcd_desc& e = p.d;
+  const WsLayout& w = p.w;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  // 3. prep: the forward call's tables, formed by the same launch, on every segment
+  launch_prep(e, *lay, w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
+  // 4. launch: one statistics record per 16-particle tile
+  double* partials = reinterpret_cast<double*>(ws + w.partials);
+  TrajArgs ta{seeds, params, ws, partials, nullptr, nullptr, *lay, w, n, (int32_t)d.nbridges, d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0,
+              e.grad_clipping, nullptr, d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_traj_kernel");
+  if ((rc = segment_launch(e, w, ta, k0, k1, z, wpath, key, out_lg, stream)) != CMCD_OK) return rc;
+  // 5. merge the statistics
+  launch_finalize(partials, w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
 // the VarGrad gradient on the tables (and, for work items and lgcp, the trajectory) in the workspace; kept: left there by
 // cmcd_bound_var_forward, otherwise formed here
 static int var_grad_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
@@ -584,6 +632,16 @@ int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* lay, const int3
                        void* stream_) {
   return reverse_impl(desc, lay, seeds, x, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_w,
                       out_z0, out_stats, stream_);
+}
+
+int64_t cmcd_segment_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_SEGMENT); }
+
+int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0, int32_t k1, const int32_t* seeds, int64_t n,
+                       const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                       void* workspace, int64_t workspace_bytes, float* z_inout, float* wpath_inout, uint32_t* key_inout,
+                       float* out_lg, double* out_stats, void* stream_) {
+  return segment_impl(desc, lay, k0, k1, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
+                      z_inout, wpath_inout, key_inout, out_lg, out_stats, stream_);
 }
 
 int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,

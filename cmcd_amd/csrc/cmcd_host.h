@@ -1,5 +1,5 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
+// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip, cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
 // cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,6 +41,14 @@ void launch_vargrad_weights(const float* loss, const double* stats, int64_t n, i
 // ta.partials one statistics record per tile (w.n_waves of them) over l := w.  No instance for MCD_CAIS_UHA_sn and lgcp.
 bool reverse_available(const cmcd_desc& d, int T);
 int reverse_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, const float* x, hipStream_t stream);
+
+// cmcd_segment.hip: bridges [k0, k1) of the overdamped forward chain from a caller-supplied state (z, wpath, key), one wave per
+// 16-particle tile.  Reads the tables launch_prep left in ta.ws and ta.seeds when k0 == 0; z / wpath / key are read (k0 > 0) and
+// overwritten in place, lg receives log gamma_k1(z), ta.partials one statistics record per tile over l := -(wpath + lg).
+// The instances of the reverse call; none for MCD_CAIS_UHA_sn and lgcp.
+bool segment_available(const cmcd_desc& d, int T);
+int segment_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, int32_t k0, int32_t k1, float* z, float* wpath,
+                   uint32_t* key, float* lg, hipStream_t stream);
 
 // cmcd_resample.hip: importance statistics + systematic resampling, one workgroup per group of n / groups rows, one launch.
 // The group is walked in chunks of kResampleChunk rows with a float64 running sum carried between them.

@@ -60,6 +60,7 @@ def get_config():
     #                             its main.py always uses (main.py:148-159); only MCD_CAIS_UHA_sn reads gamma
     c.compute_w2 = True         # extra: --noconfig.compute_w2 skips the Sinkhorn W2 block of main.py:248-271 (test harness)
     c.compute_eubo = True       # extra: --noconfig.compute_eubo skips the reverse-chain diagnostics (EUBO, reverse ln Z / ESS)
+    c.smc_eval = False          # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc: resampling between bridges)
     # fields of the reference's config this driver accepts so that its README command lines run unchanged, but whose
     # only legal value here is the default (dds nets are 64-wide, the lgcp posterior is un-whitened, 40 mixtures
     # unless n_mixes says otherwise) or that configure subsystems left out (NICE, W&B, the cluster launcher)
@@ -254,6 +255,31 @@ def main(config):
                     r["eubo" + prefix], forward_ln_Z))
 
         say_reverse(params_flat, final_elbo, final_ln_Z)
+    # SMC evaluation (no analogue in the reference): the same chain with the groups resampled between bridges when their ESS drops
+    smc_on = (config.smc_eval and rank == 0 and config.model in ("funnel", "gmm", "many_gmm") and
+              config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn"))
+    if smc_on:
+        from . import sinkhorn, smc
+
+        def say_smc(p, prefix=""):
+            G = config.n_input_dist_seeds
+            res = smc.smc_bound(eval_seeds, p, unflatten, params_fixed, log_prob_model, eps_schedule=config.eps_schedule,
+                                grad_clipping=config.grad_clipping, groups=G, seed=config.seed)
+            r = utils.log_smc_diagnostics(res, log_prefix=prefix)
+            line = "SMC%s: ln Z %.2f (+- %.2f), %d resampling events in %d stages, final ESS %.1f (+- %.1f) of %d (%.1f %%)" % (
+                prefix, r["smc_ln_Z" + prefix], r["smc_ln_Z_std" + prefix], r["smc_resampling_events" + prefix],
+                r["smc_stages" + prefix], r["smc_ess" + prefix], r["smc_ess_std" + prefix], config.n_samples,
+                100.0 * r["smc_ess_frac" + prefix])
+            if sample_from_target_fn is not None and config.compute_w2:
+                cloud, _, _ = resample.resample(res["losses"], res["z"], groups=G, seed=config.seed)
+                draws = sample_from_target_fn(1, (n,)) if config.model == "many_gmm" else sample_from_target_fn(1, n)
+                tgt_smc = torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float32)).to(device)
+                cost = sinkhorn.w2_batched(cloud.view(G, config.n_samples, dim), tgt_smc.view(G, config.n_samples, dim))["cost"]
+                line += "; W2 of the resampled SMC cloud to the target %.4f (+- %.4f)" % (
+                    float(cost.mean()), float(cost.std(unbiased=False)))
+            say(line + ".")
+
+        say_smc(params_flat)
     if config.use_ema:
         eval_losses_ema, samples_ema = utils.sample(config, config.n_samples, config.n_input_dist_seeds, ema_params, unflatten,
                                           params_fixed, log_prob_model, loss_fn, eval_seeds, log_prefix="eval")
@@ -262,6 +288,8 @@ def main(config):
         say("With EMA, got ln Z %.2f." % z2)
         if reverse:
             say_reverse(ema_params, e2, z2, prefix="_ema")
+        if smc_on:
+            say_smc(ema_params, prefix="_ema")
     if sample_from_target_fn is not None and config.model in ("funnel", "gmm") and rank == 0 and config.compute_w2:   # main.py:248-271
         tgt = torch.from_numpy(sample_from_target_fn(1, n)).to(device)
         other = torch.from_numpy(sample_from_target_fn(2, n)).to(device)

@@ -1,6 +1,7 @@
 """Host-side Threefry-2x32 (the jax.random generator) — product code needs it only for target
 constants that the reference draws from a PRNG (many_gmm means,
-/root/reference/src/model_handler.py:255-261).  The device kernels carry their own copy."""
+/root/reference/src/model_handler.py:255-261) and to name the chain keys a segment of the chain hands on
+(`chain_keys`; cmcd_amd/smc.py).  The device kernels carry their own copy."""
 import numpy as np
 
 _ROT = (13, 15, 26, 6, 17, 29, 16, 24)
@@ -38,3 +39,27 @@ def uniform(seed, shape, minval, maxval):
     u = ((bits >> np.uint32(9)) | np.uint32(0x3F800000)).view(np.float32) - np.float32(1.0)
     lo, hi = np.float32(minval), np.float32(maxval)
     return np.maximum(lo, u * (hi - lo) + lo).reshape(shape)
+
+
+def split(k0, k1):
+    """jax.random.split((k0, k1)) -> ((a0, a1), (b0, b1)); ints, or integer arrays of at least 64 bits (element-wise)."""
+    a0, b0 = _threefry(k0, k1, 0, 2)
+    a1, b1 = _threefry(k0, k1, 1, 3)
+    return (a0, a1), (b0, b1)
+
+
+def chain_keys(seeds, k):
+    """gen_0 .. gen_k of the forward chain's key chain for every seed -> uint32[k + 1, N, 2]: (_, B) = split(PRNGKey(seed));
+    (C, _) = split(B); gen_0 = second(split(C)); step i draws its noise from first(split(gen_i)) and hands on
+    gen_{i+1} = second(split(second(split(gen_i)))).  gen_k is the key a chain segment that stops at bridge k returns."""
+    seeds = np.asarray(seeds).astype(np.int64).reshape(-1) & _M
+    _, b = split(np.zeros_like(seeds), seeds)
+    c, _ = split(*b)
+    _, gen = split(*c)
+    out = np.empty((k + 1, seeds.size, 2), np.uint32)
+    for i in range(k + 1):
+        out[i, :, 0], out[i, :, 1] = gen[0], gen[1]
+        if i < k:
+            _, h = split(*gen)
+            _, gen = split(*h)
+    return out

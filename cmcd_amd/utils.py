@@ -80,6 +80,28 @@ def log_reverse_diagnostics(w_groups, log_prefix=""):
 log_reverse_diagnostics.last = {}
 
 
+def log_smc_diagnostics(result, log_prefix=""):
+    """result: what cmcd_amd.smc.smc_bound returned -> the SMC estimate of ln Z as mean and standard deviation (ddof = 0) over
+    the seed groups, the number of resampling events (group x cut), and the effective sample size of the final weighted cloud
+    (mean, standard deviation, and as a fraction of the group size).  The reference reports no such figures."""
+    ln_z, ess = result["ln_Z"], result["ess"][-1]
+    m = result["losses"].numel() // ln_z.numel()
+    out = {
+        f"smc_ln_Z{log_prefix}": float(ln_z.mean()),
+        f"smc_ln_Z_std{log_prefix}": float(ln_z.std(unbiased=False)),
+        f"smc_resampling_events{log_prefix}": int(result["resampled"].sum()),
+        f"smc_stages{log_prefix}": int(result["resampled"].numel()),
+        f"smc_ess{log_prefix}": float(ess.mean()),
+        f"smc_ess_std{log_prefix}": float(ess.std(unbiased=False)),
+        f"smc_ess_frac{log_prefix}": float(ess.mean()) / m,
+    }
+    log_smc_diagnostics.last = out
+    return out
+
+
+log_smc_diagnostics.last = {}
+
+
 def sample(info, n_samples, n_input_dist_seeds, params_flat, unflatten, params_fixed, log_prob_model, loss_fn,
            eval_seeds, log_prefix=""):
     """/root/reference/src/opt.py:167-197 -> (elbos [n_input_dist_seeds][n_samples], zs [n*m, dim]).

@@ -197,6 +197,45 @@ int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* layout,
                        float* out_w, float* out_z0, double* out_stats,
                        void* stream);
 
+/* ---- Resumable segments of the forward chain: bridges [k0, k1) from a caller-supplied particle state, so that the weights can
+ * be examined and the particles resampled BETWEEN bridges (sequential Monte Carlo over the annealing path; the Python driver is
+ * cmcd_amd.smc).  No analogue in the reference, which runs its chain from q to bridge K in one piece; the arithmetic is the
+ * forward call's, cut at a bridge, restated in float64 NumPy in tests/smc_restatement.py.  With the schedules beta_i, eps_i, the
+ * clip rule, the network s(., i) and q of cmcd_bound_forward for the same (desc, layout, params) — the same prep tables —
+ * particle p runs
+ *   k0 == 0:  key chain and z_0 exactly as cmcd_bound_forward;  wpath = -log q(z_0);  gen = gen_0
+ *   k0  > 0:  z = z_inout[p], wpath = wpath_inout[p], gen = key_inout[p]      (uint32[2]: the forward chain's gen_k0)
+ *   for i = k0 .. k1-1:  the forward call's step i, unchanged:  z' = m_f(z, i) + sigma_i xi_i with xi_i = normal(first(split(gen)));
+ *                        wpath += log B_i(z | z') - log F_i(z' | z);  z <- z';  gen <- second(split(second(split(gen))))
+ *   lg = log gamma_k1(z):  gamma_K = p;  0 < k < K:  log gamma_k = beta_{k-1} log p + (1 - beta_{k-1}) log q
+ *   out:  z_inout[p] = z, wpath_inout[p] = wpath, key_inout[p] = gen_k1, out_lg[p] = lg;
+ *         out_stats[5] = the statistics of cmcd_bound_forward over l := -(wpath + lg).
+ * Why beta_{k-1}: step k-1 uses beta_{k-1} at both of its ends, so with a zero network wpath + lg telescopes to the plain AIS
+ * weight of particles that target pi_{beta_{k-1}} = p^beta q^(1 - beta).  log p = -inf (the many_gmm floor) gives lg = -inf
+ * whatever beta is, never 0 * inf; a NaN stays NaN (the divergence signal, as in the forward call).  At k1 == nbridges,
+ * -(wpath + lg) is the loss cmcd_bound_forward returns (same arithmetic; its wave-per-tile kernel evaluates the 132-wide net in
+ * another order, so the last bits may differ).  wpath is carried WITHOUT the gamma term: segments [0, k) then [k, K) need no
+ * cancellation and return the bits of the single segment [0, K) in z, wpath, lg and the key — the kernel is one
+ * runtime-bounded loop with a single evaluation site, so the evaluation at a cut is the same machine code in both segments.
+ * It is also evaluated by both: one extra evaluation (grad log p, grad log q, the network) per cut.
+ * The state is read and overwritten in place (each particle by its own lanes only).  Keys belong to the particle SLOT: a
+ * caller that resamples z between segments leaves key_inout alone, so that two offspring of one ancestor draw different noise.
+ *   0 <= k0 < k1 <= nbridges, else CMCD_ERR_BAD_ARG;  seeds[n] int32 [device] is read when k0 == 0 (null there:
+ *   CMCD_ERR_BAD_ARG) and may be null otherwise.  z_inout[n*dim], wpath_inout[n], out_lg[n] float32, key_inout[n*2] uint32,
+ *   out_stats[5] float64, all [device].
+ * Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward; workspace of cmcd_segment_workspace_bytes (0 where
+ * the call is unsupported).  Every call runs the prep launch (there is no prepared-table form).  One kernel form (one wave per
+ * 16-particle tile) for the four overdamped modes on gmm, funnel (dim 10) and many_gmm with the nets of cmcd_bound_reverse
+ * (dds 64; geffner on 2 / 4 / 9 neuron tiles, funnel 4 / 9); MCD_CAIS_UHA_sn, lgcp and other widths: CMCD_ERR_UNSUPPORTED. */
+int64_t cmcd_segment_workspace_bytes(const cmcd_desc* desc, int64_t n);
+int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* layout, int32_t k0, int32_t k1,
+                       const int32_t* seeds /* k0 == 0; else nullable */, int64_t n,
+                       const float* params, int64_t n_params,
+                       const float* target_consts, int64_t n_target,
+                       void* workspace, int64_t workspace_bytes,
+                       float* z_inout /*[n*dim]*/, float* wpath_inout /*[n]*/, uint32_t* key_inout /*[n*2]*/,
+                       float* out_lg /*[n]*/, double* out_stats /*[5]*/, void* stream);
+
 /* (Measurement and diagnostic hooks — kernel-time events, the PRNG capture of the parity tests, the probes' switches — are NOT
  * part of this boundary: they are declared in include/cmcd_hip_diag.h and compiled out of the library by
  * -DCMCD_NO_DIAG_HOOKS; a deployment binds nothing of them.) */

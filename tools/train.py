@@ -39,6 +39,7 @@ ap.add_argument("--lr", type=float, default=1e-3)
 ap.add_argument("--n_samples", type=int, default=500)
 ap.add_argument("--n_input_dist_seeds", type=int, default=30)
 ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--smc_eval", action="store_true", help="add the SMC evaluation (resampling between bridges) to both evaluations")
 ap.add_argument("--file_path", default="", help="lgcp: pines.csv (default: the bin-count fixture under tests/golden)")
 cfg = ap.parse_args()
 
@@ -95,6 +96,7 @@ if WORLD > 1:
 
 
 x_tgt = None
+res_sampler = res[2] if len(res) > 2 else None
 if len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and \
         cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn"):
     from cmcd_amd.model_handler import exact_target_draws
@@ -116,6 +118,21 @@ def evaluate(p, tag):
         print("%s: EUBO %.4f   reverse ln Z %.4f   reverse ESS %.1f (+- %.1f) of %d (%.1f %%)   ln Z bracket [%.4f, %.4f]" % (
             tag, r["eubo"], r["reverse_ln_Z"], r["reverse_ess"], r["reverse_ess_std"], cfg.n_samples,
             100.0 * r["reverse_ess_frac"], e, r["eubo"]))
+
+    if cfg.smc_eval and x_tgt is not None:      # (same modes and targets as the reverse chain)
+        from cmcd_amd import resample, sinkhorn, smc
+        G = cfg.n_input_dist_seeds
+        out = smc.smc_bound(eval_seeds, p, unflatten, fixed, log_prob_model, eps_schedule=cfg.eps_schedule,
+                            grad_clipping=cfg.grad_clipping, groups=G, seed=cfg.seed)
+        r = utils.log_smc_diagnostics(out)
+        cloud, _, _ = resample.resample(out["losses"], out["z"], groups=G, seed=cfg.seed)
+        draws = res_sampler(1, (G * cfg.n_samples,)) if cfg.model == "many_gmm" else res_sampler(1, G * cfg.n_samples)
+        tgt = torch.from_numpy(draws).float().cuda()
+        cost = sinkhorn.w2_batched(cloud.view(G, cfg.n_samples, dim), tgt.view(G, cfg.n_samples, dim))["cost"]
+        print("%s: SMC ln Z %.4f (+- %.4f)   %d resampling events in %d stages   final ESS %.1f (+- %.1f) of %d (%.1f %%)   "
+              "W2 of the resampled SMC cloud %.4f (+- %.4f)" % (
+                  tag, r["smc_ln_Z"], r["smc_ln_Z_std"], r["smc_resampling_events"], r["smc_stages"], r["smc_ess"], r["smc_ess_std"],
+                  cfg.n_samples, 100.0 * r["smc_ess_frac"], float(cost.mean()), float(cost.std(unbiased=False))))
 
 
 evaluate(flat, "before")
