@@ -103,14 +103,20 @@ def dds_time_embedding(sn, t, dtype):
     return (h @ sn["t_w2"] + sn["t_b2"]).astype(dtype)
 
 
-def apply_dds(sn, z, t, dtype):
-    """PISNet.__call__  /root/reference/src/nn_dds.py:145-164."""
+def _record(trace, key, a):
+    if trace is not None:
+        trace.setdefault(key, []).append(np.array(a, copy=True))
+
+
+def apply_dds(sn, z, t, dtype, trace=None):
+    """PISNet.__call__  /root/reference/src/nn_dds.py:145-164.  `trace`: receives the output before its clamp."""
     dt = np.dtype(dtype).type
     tau = dds_time_embedding(sn, t, dtype)
     x = np.concatenate([z, np.broadcast_to(tau, (z.shape[0], tau.shape[0]))], 1)
     h = gelu(x @ sn["s_w1"] + sn["s_b1"])
     h = gelu(h @ sn["s_w2"] + sn["s_b2"])
     out = h @ sn["s_w3"] + sn["s_b3"]
+    _record(trace, "out", out)
     return np.clip(out, dt(-1e4), dt(1e4))
 
 
@@ -124,8 +130,19 @@ def apply_geffner(sn, z, i, dtype):
     return (u @ sn["W3"] + sn["b3"]) * sn["factor_sn"]
 
 
-def apply_sn(arch, sn, z, i, dtype):
-    return apply_dds(sn, z, i, dtype) if arch == "dds" else apply_geffner(sn, z, i, dtype)
+def apply_sn(arch, sn, z, i, dtype, trace=None):
+    return apply_dds(sn, z, i, dtype, trace) if arch == "dds" else apply_geffner(sn, z, i, dtype)
+
+
+def _trace_scores(trace, target, zz, gp, gq):
+    """What oracle/cmcd_oracle_torch.py's `trace=` records, from this restatement in its own dtype: log p before the
+    target's floor (targets without one: log p), grad log p and grad log q before clipping."""
+    if trace is None:
+        return
+    unfloored = getattr(target, "unfloored", None)
+    _record(trace, "lp", unfloored(zz) if unfloored else target(zz)[0])
+    _record(trace, "gp", gp)
+    _record(trace, "gq", gq)
 
 
 # --------------------------------------------------------------------------- kernels
@@ -143,7 +160,7 @@ def cast_params(params, dtype):
 
 # --------------------------------------------------------------------------- the bound
 def compute_log_elbo_batch(seeds, params, dim, nbridges, mode, arch, target,
-                           eps_schedule=None, grad_clipping=False, dtype=np.float32, reuse=False):
+                           eps_schedule=None, grad_clipping=False, dtype=np.float32, reuse=False, trace=None):
     """Per-particle loss and final sample.  /root/reference/src/mcdboundingmachine.py:126-179
     with the evolve loop of /root/reference/src/mcd_cais.py:46-96 (``MCD_CAIS_sn``) or
     /root/reference/src/mcd_cais_var.py:57-112 (``MCD_CAIS_var_sn``; forward values differ
@@ -151,12 +168,13 @@ def compute_log_elbo_batch(seeds, params, dim, nbridges, mode, arch, target,
 
     reuse=False evaluates grad/net twice per step like the reference; reuse=True carries the
     backward evaluation into the next step's forward kernel (bit-identical).
+    trace: a dict that receives, per evaluation, the quantities the hard gates act on (see _trace_scores, apply_dds).
     Returns (loss[N], z[N, dim]) in ``dtype``.
     """
     if mode not in MODES:
         raise NotImplementedError("Mode not implemented.")
     if mode == "MCD_CAIS_UHA_sn":
-        return compute_log_elbo_batch_uha(seeds, params, dim, nbridges, arch, target, dtype=dtype)
+        return compute_log_elbo_batch_uha(seeds, params, dim, nbridges, arch, target, dtype=dtype, trace=trace)
     dt = np.dtype(dtype).type
     p = cast_params(params, dtype)
     vd, sn = p["vd"], p.get("sn")
@@ -182,6 +200,7 @@ def compute_log_elbo_batch(seeds, params, dim, nbridges, mode, arch, target,
     def grads(zz):
         _, gp = target(zz)
         gq = q_grad(vd, zz)
+        _trace_scores(trace, target, zz, gp, gq)
         if grad_clipping:
             gp = np.clip(gp, -clip, clip)
             if var_mode:
@@ -198,7 +217,7 @@ def compute_log_elbo_batch(seeds, params, dim, nbridges, mode, arch, target,
         if reuse and carried is not None:
             g_z, s_z = carried
         else:
-            g_z, s_z = grads(z), (None if ula else apply_sn(arch, sn, z, i, dtype))
+            g_z, s_z = grads(z), (None if ula else apply_sn(arch, sn, z, i, dtype, trace))
         uf = grad_u(g_z, beta)
         if ula:
             fk_mean = z - eps * uf
@@ -209,7 +228,7 @@ def compute_log_elbo_batch(seeds, params, dim, nbridges, mode, arch, target,
         if mode == "MCD_ULA":
             g_n, s_n = grads(z_new), None
         else:
-            g_n, s_n = grads(z_new), apply_sn(arch, sn, z_new, i if ula else i + 1, dtype)
+            g_n, s_n = grads(z_new), apply_sn(arch, sn, z_new, i if ula else i + 1, dtype, trace)
         ub = grad_u(g_n, beta)
         bk_mean = z_new - eps * ub if s_n is None else z_new - eps * ub + eps * s_n
         w = w + (log_prob_kernel(z, bk_mean, scale) - log_prob_kernel(z_new, fk_mean, scale))
@@ -220,7 +239,7 @@ def compute_log_elbo_batch(seeds, params, dim, nbridges, mode, arch, target,
     return (dt(-1.0) * w).astype(dtype), z.astype(dtype)
 
 
-def compute_log_elbo_batch_uha(seeds, params, dim, nbridges, arch, target, dtype=np.float32):
+def compute_log_elbo_batch_uha(seeds, params, dim, nbridges, arch, target, dtype=np.float32, trace=None):
     """``MCD_CAIS_UHA_sn`` — second-order (underdamped) CMCD.  /root/reference/src/mcdboundingmachine.py:126-179 with
     the evolve loop of /root/reference/src/mcd_under_lp_a_cais.py:6-115: state (z, rho), score network on
     ``concat(z, rho)`` with the SAME time index i in the forward and the backward kernel (:51-54,77-80), momentum
@@ -250,13 +269,14 @@ def compute_log_elbo_batch_uha(seeds, params, dim, nbridges, arch, target, dtype
     def grad_u(zz, beta):                                             # :23-30
         _, gp = target(zz)
         gq = q_grad(vd, zz)
+        _trace_scores(trace, target, zz, gp, gq)
         return dt(-1.0) * (beta * np.clip(gp, -clip, clip) + (dt(1.0) - beta) * gq)
 
     for i in range(nbridges):
         beta, eps = betas[i], eps_tab[i]
         uf = grad_u(z, beta)                                          # :46
         eta_aux = gamma * eps                                         # :50
-        s_old = apply_sn(arch, sn, np.concatenate([z, rho], 1), i, dtype)
+        s_old = apply_sn(arch, sn, np.concatenate([z, rho], 1), i, dtype, trace)
         fk_rho_mean = rho * (dt(1.0) - eta_aux) - dt(2.0) * eta_aux * s_old          # :52-54
         scale = np.sqrt(dt(2.0) * eta_aux)                            # :56
         rho_prime = fk_rho_mean + scale * noise[:, i, :].astype(dtype)               # :58-59
@@ -264,7 +284,7 @@ def compute_log_elbo_batch_uha(seeds, params, dim, nbridges, arch, target, dtype
         z_new = z + eps * rho_pp                                      # :63
         ub = grad_u(z_new, beta)                                      # :65
         rho_new = rho_pp - eps * ub / dt(2.0)                         # :67
-        s_new = apply_sn(arch, sn, np.concatenate([z, rho_prime], 1), i, dtype)      # :77-80: old z, new momentum
+        s_new = apply_sn(arch, sn, np.concatenate([z, rho_prime], 1), i, dtype, trace)   # :77-80: old z, new momentum
         bk_rho_mean = rho_prime * (dt(1.0) - eta_aux) + dt(2.0) * eta_aux * s_new
         w = w + (log_prob_kernel(rho, bk_rho_mean, scale) - log_prob_kernel(rho_prime, fk_rho_mean, scale))  # :83-88
         z, rho = z_new, rho_new

@@ -34,7 +34,13 @@ def logp_gmm(z):
         comp = torch.distributions.MultivariateNormal(means, covariance_matrix=covs)
         return torch.logsumexp(comp.log_prob(x[:, None, :]) + math.log(1 / 3), dim=1)
 
-    return torch.logaddexp(raw(z), raw(z.flip(-1))) - math.log(2.0)
+    # The value is torch.logaddexp's, as before.  The derivative is taken through logsumexp: logaddexp's backward is
+    # grad / (1 + exp(b - a)), whose own derivative is inf * 0 = NaN once the two halves differ by more than ~709 nats
+    # (40 units from the modes) — the Hessian the full gradient needs there.  The two values agree to an ulp, so their
+    # difference is exact and adding it back returns logaddexp's value bit for bit.
+    a, b = raw(z), raw(z.flip(-1))
+    lse = torch.logsumexp(torch.stack([a, b]), dim=0)
+    return lse + (torch.logaddexp(a, b) - lse).detach() - math.log(2.0)
 
 
 def logp_funnel(z):
@@ -44,12 +50,19 @@ def logp_funnel(z):
             - 0.5 * torch.exp(-v) * (z[:, 1:] ** 2).sum(-1))
 
 
-def logp_many_gmm(z, n_mixes=40, loc_scaling=40.0):
+def logp_many_gmm_unfloored(z, n_mixes=40, loc_scaling=40.0):
     mu = torch.tensor(np.asarray(many_gmm_means(n_mixes, 2, loc_scaling), np.float64), dtype=z.dtype)
     s = math.log1p(math.exp(0.1))
     comp = (-0.5 * ((z[:, None, :] - mu) / s) ** 2 - math.log(s) - 0.5 * LOG_2PI).sum(-1)
-    lp = torch.logsumexp(comp - math.log(mu.shape[0]), dim=1)
+    return torch.logsumexp(comp - math.log(mu.shape[0]), dim=1)
+
+
+def logp_many_gmm(z, n_mixes=40, loc_scaling=40.0):
+    lp = logp_many_gmm_unfloored(z, n_mixes, loc_scaling)
     return torch.where(lp > -1e4, lp, torch.full_like(lp, -math.inf))   # model_handler.py:279-280
+
+
+logp_many_gmm.unfloored = logp_many_gmm_unfloored   # what `trace=` records and the "floor" straight-through differentiates
 
 
 def make_logp_lgcp(flat_bin_counts, m=40):
@@ -69,9 +82,39 @@ def make_logp_lgcp(flat_bin_counts, m=40):
 TARGETS = {"gmm": logp_gmm, "funnel": logp_funnel, "many_gmm": logp_many_gmm}
 
 
-def grad_logp(logp_fn, z, create_graph):
-    """jax.grad(log_prob_model)(z) per particle; zero where log p is floored to -inf."""
+def _record(trace, key, t):
+    if trace is not None:
+        trace.setdefault(key, []).append(t.detach().numpy().copy())
+
+
+def _gate(x, lo, hi, open_gate):
+    """clamp(x, lo, hi); `open_gate`: the same value with the derivative of the identity (straight-through)."""
+    c = torch.clamp(x, lo, hi)
+    return x + (c - x).detach() if open_gate else c
+
+
+def _unfloored(logp_fn):
+    return getattr(logp_fn, "unfloored", logp_fn)
+
+
+def _final_logp(logp_fn, z, open_floor):
+    lp = logp_fn(z)
+    if not open_floor or _unfloored(logp_fn) is logp_fn:
+        return lp
+    raw = _unfloored(logp_fn)(z)
+    return raw + (lp - raw).detach()      # -inf where floored, with the unfloored mixture's derivative
+
+
+def grad_logp(logp_fn, z, create_graph, trace=None, open_floor=False):
+    """jax.grad(log_prob_model)(z) per particle; zero where log p is floored to -inf.  `trace` receives the log-density
+    before its floor; `open_floor`: the score (and, through create_graph, the Hessian) of the unfloored density."""
     zz = z if z.requires_grad else z.detach().requires_grad_(True)
+    if trace is not None:
+        with torch.no_grad():
+            _record(trace, "lp", _unfloored(logp_fn)(z.detach()))
+    if open_floor and _unfloored(logp_fn) is not logp_fn:
+        (g,) = torch.autograd.grad(_unfloored(logp_fn)(zz).sum(), zz, create_graph=create_graph)
+        return g
     lp = logp_fn(zz)
     fin = torch.isfinite(lp)
     (g,) = torch.autograd.grad(torch.where(fin, lp, torch.zeros_like(lp)).sum(), zz, create_graph=create_graph)
@@ -83,7 +126,7 @@ def gelu(x):
     return x * 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
-def apply_dds(sn, z, t):
+def apply_dds(sn, z, t, trace=None, open_clamp=False):
     coeff = torch.tensor(_np_oracle.timestep_coeff().astype(np.float64), dtype=z.dtype)
     arg = coeff * float(t) + sn["timestep_phase"].reshape(-1)
     emb = torch.cat([torch.sin(arg), torch.cos(arg)])
@@ -91,10 +134,12 @@ def apply_dds(sn, z, t):
     x = torch.cat([z, tau.expand(z.shape[0], -1)], 1)
     h = gelu(x @ sn["s_w1"] + sn["s_b1"])
     h = gelu(h @ sn["s_w2"] + sn["s_b2"])
-    return torch.clamp(h @ sn["s_w3"] + sn["s_b3"], -1e4, 1e4)
+    out = h @ sn["s_w3"] + sn["s_b3"]
+    _record(trace, "out", out)
+    return _gate(out, -1e4, 1e4, open_clamp)
 
 
-def apply_geffner(sn, z, i):
+def apply_geffner(sn, z, i, trace=None, open_clamp=False):   # no clamp in this net: nothing to trace or open
     nb = sn["emb"].shape[0]
     emb = sn["emb"][min(max(int(i), 0), nb - 1)]
     u = torch.cat([z, emb.expand(z.shape[0], -1)], 1)
@@ -132,10 +177,28 @@ def to_torch(params, requires_grad=True):
     return t.requires_grad_(requires_grad)
 
 
-def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, grad_clipping=False):
-    """Per-particle losses [N] (float64), differentiable wrt the leaves of `p`."""
+GATES = frozenset({"floor", "clip", "clamp"})
+
+
+def _gates(straight_through):
+    st = frozenset(straight_through or ())
+    if not st <= GATES:
+        raise ValueError(f"straight_through takes names from {sorted(GATES)}, got {sorted(st - GATES)}")
+    return st
+
+
+def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, grad_clipping=False, trace=None,
+           straight_through=None):
+    """Per-particle losses [N] (float64), differentiable wrt the leaves of `p`.
+
+    trace: a dict that receives one [N] / [N, dim] float64 array per evaluation, in evaluation order (step i: z_i then
+    z_{i+1}), under "lp" (log p before the many_gmm floor), "gp" / "gq" (grad log p / grad log q before any clipping) and
+    "out" (the dds output before its clamp; one per network call).
+    straight_through: names from GATES; the forward values stay what they are, the derivative is taken as if the named
+    gate were open — the gradient a kernel without that gate would return.  Test infrastructure only."""
+    st = _gates(straight_through)
     if mode == "MCD_CAIS_UHA_sn":
-        return losses_uha(seeds, p, dim, nbridges, arch, target_name)
+        return losses_uha(seeds, p, dim, nbridges, arch, target_name, trace=trace, straight_through=st)
     var_mode = mode == "MCD_CAIS_var_sn"
     # MCD_ULA / MCD_ULA_sn (/root/reference/src/mcd_over_orig.py:6-65 via mcd_utils.py:35-58): constant eps, no
     # clipping, no network in the forward kernel; the backward kernel's network (ULA_sn only) takes index i
@@ -150,7 +213,10 @@ def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, 
     std = torch.exp(vd["logdiag"])
     betas = betas_from_grid(p["mgridref_y"], nbridges)
     eps_tab = eps_table(p["eps"], nbridges, eps_schedule)
-    apply = apply_dds if arch == "dds" else apply_geffner
+    apply_net = apply_dds if arch == "dds" else apply_geffner
+
+    def apply(sn, z, t):
+        return apply_net(sn, z, t, trace, "clamp" in st)
 
     def log_q(z):
         return (-((z - vd["mean"]) ** 2) / (2 * std * std) - torch.log(std) - 0.5 * LOG_2PI).sum(-1)
@@ -162,11 +228,13 @@ def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, 
 
     def grad_u(z, beta):
         gq = -(z - vd["mean"]) / (std * std)           # jax.grad of vd.log_prob wrt z
-        gp = grad_logp(logp_fn, z, create_graph=not var_mode)
+        gp = grad_logp(logp_fn, z, create_graph=not var_mode, trace=trace, open_floor="floor" in st)
+        _record(trace, "gp", gp)
+        _record(trace, "gq", gq)
         if grad_clipping:
-            gp = torch.clamp(gp, -clip, clip)
+            gp = _gate(gp, -clip, clip, "clip" in st)
             if var_mode:
-                gq = torch.clamp(gq, -clip, clip)
+                gq = _gate(gq, -clip, clip, "clip" in st)
         return -1.0 * (beta * gp + (1.0 - beta) * gq)
 
     z = std * e0 + vd["mean"]                          # reparameterised sample
@@ -188,15 +256,16 @@ def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, 
             bk = z_new - eps * ub + eps * apply(sn, z_new, i if ula else i + 1)
         w = w + log_kernel(z, bk, scale) - log_kernel(z_new, fk, scale)
         z = z_new
-    w = w + logp_fn(z)
+    w = w + _final_logp(logp_fn, z, "floor" in st)
     return -w, z
 
 
-def losses_uha(seeds, p, dim, nbridges, arch, target_name):
+def losses_uha(seeds, p, dim, nbridges, arch, target_name, trace=None, straight_through=None):
     """``MCD_CAIS_UHA_sn`` (/root/reference/src/mcd_under_lp_a_cais.py:6-115 under mcdboundingmachine.py:126-179), no
     stop_gradient anywhere: the gradient is the full reparameterised one through (z, rho).  Same statement as
     oracle/cmcd_oracle.py:compute_log_elbo_batch_uha (cos^2 schedule always on, clip 1e2 on grad log p only, both
-    network calls at time index i on concat(z, rho) / concat(z, rho'))."""
+    network calls at time index i on concat(z, rho) / concat(z, rho')).  `trace` / `straight_through`: as in `losses`."""
+    st = _gates(straight_through)
     logp_fn = TARGETS[target_name] if isinstance(target_name, str) else target_name
     e0, rho0, noise = prng.particle_noise_uha(np.asarray(seeds), dim, nbridges)
     e0 = torch.tensor(e0.astype(np.float64))
@@ -207,7 +276,10 @@ def losses_uha(seeds, p, dim, nbridges, arch, target_name):
     betas = betas_from_grid(p["mgridref_y"], nbridges)
     eps_tab = eps_table(p["eps"], nbridges, "cos_sq")
     gamma = p["gamma"]
-    apply = apply_dds if arch == "dds" else apply_geffner
+    apply_net = apply_dds if arch == "dds" else apply_geffner
+
+    def apply(sn, z, t):
+        return apply_net(sn, z, t, trace, "clamp" in st)
 
     def log_q(z):
         return (-((z - vd["mean"]) ** 2) / (2 * std * std) - torch.log(std) - 0.5 * LOG_2PI).sum(-1)
@@ -217,7 +289,10 @@ def losses_uha(seeds, p, dim, nbridges, arch, target_name):
 
     def grad_u(z, beta):
         gq = -(z - vd["mean"]) / (std * std)
-        gp = torch.clamp(grad_logp(logp_fn, z, create_graph=True), -1e2, 1e2)
+        gp = grad_logp(logp_fn, z, create_graph=True, trace=trace, open_floor="floor" in st)
+        _record(trace, "gp", gp)
+        _record(trace, "gq", gq)
+        gp = _gate(gp, -1e2, 1e2, "clip" in st)
         return -1.0 * (beta * gp + (1.0 - beta) * gq)
 
     one = torch.ones((), dtype=torch.float64)
@@ -239,15 +314,17 @@ def losses_uha(seeds, p, dim, nbridges, arch, target_name):
         w = w + log_kernel(rho, bk, scale) - log_kernel(rho_prime, fk, scale)
         z, rho = z_new, rho_new
     w = w + log_kernel(rho, torch.zeros_like(rho), one)
-    w = w + logp_fn(z)
+    w = w + _final_logp(logp_fn, z, "floor" in st)
     return -w, z
 
 
-def bound_and_grad(seeds, params_np, dim, nbridges, mode, arch, target_name, eps_schedule=None, grad_clipping=False):
+def bound_and_grad(seeds, params_np, dim, nbridges, mode, arch, target_name, eps_schedule=None, grad_clipping=False,
+                   trace=None, straight_through=None):
     """value = var(losses, ddof=0) for MCD_CAIS_var_sn, mean(losses) otherwise; grads = d value / d leaf
-    as a dict with the layout of `params_np` (what jax.grad(compute_bound_fn, 1) returns, leaf by leaf)."""
+    as a dict with the layout of `params_np` (what jax.grad(compute_bound_fn, 1) returns, leaf by leaf).
+    `trace` / `straight_through`: see `losses`."""
     p = to_torch(params_np)
-    l, z = losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule, grad_clipping)
+    l, z = losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule, grad_clipping, trace, straight_through)
     value = l.var(unbiased=False) if mode == "MCD_CAIS_var_sn" else l.mean()
     leaves = []
 

@@ -103,6 +103,14 @@ class ManyGmm:
         # named `var` in the reference but passed as *scale* (:262-266)
         self.scale = float(np.log1p(np.exp(log_var_scaling)))
 
+    def unfloored(self, z):
+        """log p before the -1e4 floor (what the gate compares): test plumbing, see cmcd_oracle._trace_scores."""
+        dt = z.dtype.type
+        diff = (z[:, None, :] - self.means.astype(z.dtype)[None]) / dt(self.scale)
+        logit = (dt(-0.5) * np.sum(diff * diff, -1)
+                 - dt(self.dim * (np.log(self.scale) + 0.5 * LOG_2PI)) - dt(np.log(self.n_mixes)))
+        return _logsumexp(logit, 1).astype(z.dtype)
+
     def __call__(self, z):
         dt = z.dtype.type
         mu = self.means.astype(z.dtype)

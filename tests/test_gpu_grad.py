@@ -617,6 +617,132 @@ def test_gradient_with_a_17_component_mixture(hip_lib, param_set, monkeypatch, i
         assert np.abs(grad[off:off + 2].double().cpu().numpy() - g["vd"][leaf]).max() <= 2e-3 * np.abs(g["vd"][leaf]).max()
 
 
+# ---------------------------------------------------------------------------------------------- the gated cases
+# tests/gated_cases.py: inputs at which the target floor, the score clip and the dds output clamp ACT (asserted on the CPU
+# in tests/test_oracle_grad.py).  Same bars as everywhere else in this file.
+import gated_cases as gc
+
+_GATED_ORACLE = {}
+
+
+def gated_oracle(case, param_set):
+    """(built case on the device, (value, losses, flat gradient) of the float64 oracle), once per (case, parameter set)."""
+    key = (case[0], param_set)
+    if key not in _GATED_ORACLE:
+        b = gc.build_case(case, device="cuda")
+        _GATED_ORACLE[key] = (b, oracle_grad_flat(b, np.asarray(case[3], np.int32)))
+    return _GATED_ORACLE[key]
+
+
+def compare_losses_with_inf(losses, l_ref):
+    """The loss check of this file (2e-3) on the finite particles; the +inf particles must be the same set; no NaN."""
+    l = np.asarray(losses, np.float64)
+    assert not np.isnan(l).any(), "NaN loss"
+    assert np.array_equal(np.isinf(l), np.isinf(l_ref)) and not (l == -np.inf).any(), (l, l_ref)
+    f = np.isfinite(l_ref)
+    np.testing.assert_allclose(l[f], l_ref[f], rtol=2e-3, atol=2e-3)
+
+
+def gated_call(b, case):
+    fn = mcdbm.compute_log_var_grad if case[4] == "MCD_CAIS_var_sn" else mcdbm.compute_bound_grad
+    seeds = torch.from_numpy(np.asarray(case[3], np.int32)).cuda()
+    grad, (losses, z) = fn(seeds, b["params_flat"], b["unflatten"], b["params_fixed"], b["target"],
+                           eps_schedule=b["eps_schedule"], grad_clipping=b["grad_clipping"])
+    torch.cuda.synchronize()
+    return grad, losses
+
+
+def assert_paths_agree(out, un):
+    """The bars of test_gpu_fullsize.test_work_item_and_whole_chain_gradients_agree_on_a_large_batch."""
+    assert torch.equal(out[0][1], out[1][1])
+    ga, gb = out[0][0], out[1][0]
+    assert float((ga * gb).sum() / (ga.norm() * gb.norm())) > 1 - 1e-8
+    for path, (off, shape) in un.layout.items():
+        numel = max(1, int(np.prod(shape)))
+        a, r = ga[off:off + numel], gb[off:off + numel]
+        scale = float(r.abs().max())
+        if scale > 1e-9:
+            assert float((a - r).abs().max()) <= 2e-4 * scale, (path, float((a - r).abs().max()), scale)
+
+
+_GATED_PATHS = {"MCD_CAIS_sn": [(1, 0), (2, 0), (1, 1), (2, 1), (3, 1)], "MCD_CAIS_var_sn": [(None, 0), (None, 1)],
+                "MCD_ULA_sn": [(1, 0), (2, 1), (1, 1)]}
+_GATED_RUNS = [pytest.param(c, v, i, id=f"{c[0]}-variant{v}-item{i}")
+               for c in gc.cases_of(*_GATED_PATHS) for v, i in _GATED_PATHS[c[4]]]
+
+
+@pytest.mark.parametrize("case,variant,item", _GATED_RUNS)
+def test_gradient_where_a_gate_acts_matches_autograd(hip_lib, param_set, monkeypatch, case, variant, item):
+    """Every leaf against autograd where floored particles, clipped scores or clamped network outputs make a derivative
+    exactly zero: both gradient paths, the three forward variants of MCD_CAIS_sn, both parameter sets."""
+    if variant is not None:
+        monkeypatch.setattr(mcdbm, "KERNEL_VARIANT", variant)
+    monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
+    b, (val, l_ref, g_ref) = gated_oracle(case, param_set)
+    assert b["params_fixed"][2] == case[4]
+    try:
+        grad, losses = gated_call(b, case)
+    except NotImplementedError as e:
+        if variant is not None and variant >= 2 and "cooperative" in str(e):
+            pytest.skip("no cooperative instance for this net")
+        raise
+    compare_losses_with_inf(losses.cpu().numpy(), l_ref)
+    if case[0] == "floor-end":
+        assert np.isinf(l_ref).any() and bool(torch.isfinite(grad).all())
+    _compare(case[0], case[2], b["unflatten"], grad.double().cpu(), g_ref)
+
+
+@pytest.mark.parametrize("case", gc.cases_of(*_GATED_PATHS), ids=lambda c: c[0])
+def test_gradient_paths_agree_where_a_gate_acts(hip_lib, param_set, monkeypatch, case):
+    b, _ = gated_oracle(case, param_set)
+    out = {}
+    for item in (0, 1):
+        monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
+        grad, losses = gated_call(b, case)
+        assert bool(torch.isfinite(grad).all())
+        out[item] = (grad.double().cpu(), losses.cpu())
+    assert_paths_agree(out, b["unflatten"])
+
+
+def test_vargrad_with_an_infinite_loss_is_nan_where_the_finite_batch_has_a_gradient(hip_lib, monkeypatch):
+    """many_gmm at sigma_0 = 60, 33 particles, one of them beyond the floor at z_K: var(losses) is NaN and so is every weight
+    (test_vargrad_weights_follow_the_variance_clip), so jax.grad returns NaN wherever the gradient is not structurally zero:
+    NaN at every entry that is non-zero on the finite sub-batch, exactly zero on every leaf that is exactly zero there.  opt.run
+    on such a batch stops as it does on a NaN loss."""
+    import types
+    from cmcd_amd import opt
+    b = synthetic.build("many_gmm_var_n16000_k256", device="cuda", nbridges=4, init_sigma=60.0, emb_dim=20)
+    seeds = torch.from_numpy(synthetic.parity_seeds(33)).cuda()
+    args = (b["params_flat"], b["unflatten"], b["params_fixed"], b["target"])
+    kw = dict(eps_schedule=b["eps_schedule"], grad_clipping=b["grad_clipping"])
+    for item in (0, 1):
+        monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
+        g_all, (l_all, _) = mcdbm.compute_log_var_grad(seeds, *args, **kw)
+        inf = torch.isinf(l_all)
+        assert 1 <= int(inf.sum()) < 33 and not bool(torch.isnan(l_all).any())
+        g_fin, (l_fin, _) = mcdbm.compute_log_var_grad(seeds[~inf], *args, **kw)
+        assert bool(torch.isfinite(l_fin).all()) and bool(torch.isfinite(g_fin).all())
+        g_all, g_fin = g_all.cpu(), g_fin.cpu()
+        touched = 0
+        for path, (off, shape) in b["unflatten"].layout.items():
+            numel = max(1, int(np.prod(shape)))
+            a, r = g_all[off:off + numel], g_fin[off:off + numel]
+            if float(r.abs().max()) == 0.0:
+                assert float(a.abs().max()) == 0.0, f"{path}: expected exactly zero gradient"   # NaN fails this too
+            else:
+                touched += 1
+                assert bool(torch.isnan(a[r != 0]).all()), f"{path}: finite entries where jax.grad returns NaN"
+        assert touched >= 4
+    calls = {"n": 0}
+
+    def grad_and_loss(_, params_flat, *rest):
+        calls["n"] += 1
+        return mcdbm.compute_log_var_grad(seeds, params_flat, *rest, **kw)
+    opt.run(types.SimpleNamespace(N=33), 1e-3, 5000, b["params_flat"], b["unflatten"], b["params_fixed"], b["target"],
+            grad_and_loss, ("eps", "vd", "mgridref_y"), 0)
+    assert calls["n"] < 5000
+
+
 REPEAT_CASES = [
     # (synthetic config, particles, overrides, gradient function, CMCD_GRAD_ITEM)
     ("gmm_n300_k8", 300, dict(), "compute_bound_grad", 0),
@@ -627,6 +753,8 @@ REPEAT_CASES = [
     ("many_gmm_n2000_k256_dds", 500, dict(nbridges=12, init_sigma=15.0, nn_arch="geffner", emb_dim=100), "compute_bound_grad", 0),
     ("gmm_n300_k8", 333, dict(boundmode="MCD_ULA_sn"), "compute_bound_grad", 1),
     ("gmm_n300_k8", 333, dict(boundmode="MCD_ULA"), "compute_bound_grad", 0),
+    ("gated:floor-mid", 33, None, "compute_bound_grad", 0),        # floored particles (tests/gated_cases.py)
+    ("gated:clamp-dds-gmm", 17, None, "compute_bound_grad", 1),    # clamped network outputs
 ]
 
 
@@ -637,8 +765,14 @@ def test_repeated_gradient_calls_are_bitwise_identical(hip_lib, monkeypatch, nam
     shared tables and the same call returned gradients that differed in the last bits from run to run.  Twenty calls
     with other launches in between (so the waves of the gradient kernel do not arrive in one fixed order)."""
     monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
-    b = synthetic.build(name, device="cuda", **over)
-    seeds = torch.from_numpy(synthetic.parity_seeds(n)).cuda()
+    if name.startswith("gated:"):
+        case = gc.case_by_id(name[len("gated:"):])
+        b = gc.build_case(case, device="cuda")
+        seeds = torch.from_numpy(np.asarray(case[3], np.int32)).cuda()
+        assert seeds.numel() == n
+    else:
+        b = synthetic.build(name, device="cuda", **over)
+        seeds = torch.from_numpy(synthetic.parity_seeds(n)).cuda()
     call = getattr(mcdbm, fn)
     kw = dict(eps_schedule=b["eps_schedule"], grad_clipping=b["grad_clipping"])
     first = None

@@ -9,6 +9,7 @@ from cmcd_amd import mcdboundingmachine as mcdbm
 from cmcd_amd import synthetic
 from oracle import prng
 
+import gated_cases as gc
 from helpers import compare_losses, run_oracle
 from test_gpu_prng import ulp_distance
 
@@ -215,16 +216,55 @@ def test_reparameterised_gradient_matches_autograd(hip_lib, param_set, variant, 
 
 
 @pytest.mark.parametrize("item", [0, 1], ids=["whole_chain", "work_items"])
+@pytest.mark.parametrize("case", gc.cases_of(MODE), ids=lambda c: c[0])
+def test_gradient_where_a_gate_acts_matches_autograd(hip_lib, param_set, variant, monkeypatch, case, item):
+    """tests/gated_cases.py through cmcd_uha.hip: particles floored mid-chain (uha-floor; the 1e2 clip acts there too) and
+    clamped dds outputs (uha-clamp), every leaf against autograd, same bars as above; the forward that keeps the trajectory
+    is varied on the whole-chain path only, as above."""
+    if item and variant != 3:
+        pytest.skip("the work-item path reads the same kept trajectory whatever forward wrote it")
+    from test_gpu_grad import _compare, compare_losses_with_inf, gated_call, gated_oracle
+    monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
+    b, (val, l_ref, g_ref) = gated_oracle(case, param_set)
+    assert b["params_fixed"][2] == MODE
+    grad, losses = gated_call(b, case)
+    compare_losses_with_inf(losses.cpu().numpy(), l_ref)
+    assert bool(torch.isfinite(grad).all())
+    _compare(case[0], case[2], b["unflatten"], grad.double().cpu(), g_ref)
+    assert float(g_ref[b["unflatten"].offset("gamma")].abs()) > 0
+
+
+@pytest.mark.parametrize("case", gc.cases_of(MODE), ids=lambda c: c[0])
+def test_gradient_paths_agree_where_a_gate_acts(hip_lib, param_set, monkeypatch, case):
+    from test_gpu_grad import assert_paths_agree, gated_call, gated_oracle
+    b, _ = gated_oracle(case, param_set)
+    out = {}
+    for item in (0, 1):
+        monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
+        grad, losses = gated_call(b, case)
+        assert bool(torch.isfinite(grad).all())
+        out[item] = (grad.double().cpu(), losses.cpu())
+    assert_paths_agree(out, b["unflatten"])
+
+
+@pytest.mark.parametrize("item", [0, 1], ids=["whole_chain", "work_items"])
 @pytest.mark.parametrize("name,n,over", [("many_gmm_n2000_k256_dds", 500, dict(nbridges=16, init_sigma=15.0)),
                                          ("gmm_n300_k8", 300, dict()),
-                                         ("funnel_n300_k64", 100, dict(nbridges=8))])
+                                         ("funnel_n300_k64", 100, dict(nbridges=8)),
+                                         ("gated:uha-floor", 33, None), ("gated:uha-clamp", 17, None)])
 def test_repeated_gradient_calls_are_bitwise_identical(hip_lib, monkeypatch, name, n, over, item):
     """The sums over particles behind d bias-table / d beta / d eps go through one slot per (tile, bridge / point) and a
     fixed-order reduction (cmcd_uha.hip: UhaGradArgs::det, uha_det_reduce_kernel); round 3 used float atomics on the shared
     tables, so the same call returned gradients that differed in the last bits from run to run."""
     monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
-    b = synthetic.build(name, device="cuda", boundmode=MODE, **over)
-    seeds = torch.from_numpy(synthetic.parity_seeds(n)).cuda()
+    if name.startswith("gated:"):    # tests/gated_cases.py: floored particles / clamped network outputs
+        case = gc.case_by_id(name[len("gated:"):])
+        b = gc.build_case(case, device="cuda")
+        seeds = torch.from_numpy(np.asarray(case[3], np.int32)).cuda()
+        assert seeds.numel() == n
+    else:
+        b = synthetic.build(name, device="cuda", boundmode=MODE, **over)
+        seeds = torch.from_numpy(synthetic.parity_seeds(n)).cuda()
     first = None
     noise = torch.randn(1 << 20, device="cuda")
     for rep in range(20):

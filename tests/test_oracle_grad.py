@@ -89,3 +89,107 @@ def test_detached_graph_is_not_the_true_derivative():
     assert abs(fd - analytic) > 1e-3 * max(abs(fd), abs(analytic))
     # ... while the one parameter path that never crosses a detach, d(-log q(z0))/d logdiag, is exact:
     assert np.allclose(g["vd"]["logdiag"].sum() != 0, True)
+
+
+# ------------------------------------------------------------------------------------------------ the gated cases
+# tests/gated_cases.py: inputs at which the floor, the score clip and the dds clamp act.  What each case is for is asserted
+# here, on the float64 oracle, so that an edit of a seed list or an override cannot quietly empty a case.
+import gated_cases as gc
+
+_GATED = {}
+
+
+def _gated(case, param_set):
+    """(built case, oracle outputs, trace) once per (case, parameter set)."""
+    key = (case[0], param_set)
+    if key not in _GATED:
+        b = gc.build_case(case)
+        trace = {}
+        _GATED[key] = (b, gc.oracle(b, case[3], trace=trace), trace)
+    return _GATED[key]
+
+
+_IDS = [c[0] for c in gc.GATED_CASES]
+
+
+def test_gated_cases_cover_the_issue_and_stay_small():
+    assert set(_IDS) == set(gc.GATE) == set(gc.CONDITION) and len(set(_IDS)) == len(_IDS)
+    k8 = 0
+    for cid, config, over, seeds, mode in gc.GATED_CASES:
+        assert len(seeds) in (17, 33), cid
+        assert over["nbridges"] in (2, 4, 8), cid
+        k8 += over["nbridges"] == 8
+    assert k8 <= 1
+
+
+@pytest.mark.parametrize("case", gc.GATED_CASES, ids=_IDS)
+def test_gated_case_seeds_are_the_survivors_of_the_guard_band(case):
+    """(c): the seeds are parity_seeds(n0), n0 = the last one, minus the particles whose chain comes within DELTA of a
+    threshold under either parameter set; at most 15 % are dropped."""
+    n0 = case[3][-1]
+    assert gc.select_seeds(case, n0) == tuple(case[3])
+    print(case[0], "n0", n0, "dropped", n0 - len(case[3]))
+    assert n0 - len(case[3]) <= 0.15 * n0
+
+
+@pytest.mark.parametrize("case", gc.GATED_CASES, ids=_IDS)
+def test_gated_case_gate_is_active_and_clear_of_its_threshold(param_set, case):
+    """(a) between 10 % and 90 % of the relevant evaluations are gated; (b) no traced value within DELTA of a threshold."""
+    b, _, trace = _gated(case, param_set)
+    share = gc.gate_share(case, b, trace)
+    margin = gc.band_margin(b, trace)
+    print(case[0], param_set, "gated share", share, "nearest value to a threshold (relative)", "%.2e" % margin)
+    assert share and all(0.1 <= v <= 0.9 for v in share.values()), share
+    assert not gc.band_violations(b, trace).any() and margin > gc.DELTA
+
+
+@pytest.mark.parametrize("case", gc.GATED_CASES, ids=_IDS)
+def test_guard_band_is_ten_times_the_float32_gap(param_set, case):
+    """DELTA >= 10 x the worst relative difference between the float32 and the float64 NumPy restatement on the traced
+    quantities (and >= 1e-4): a float32 kernel cannot land on the other side of a gate."""
+    gap = gc.float32_gap(case, gc.build_case(case))
+    print(case[0], param_set, "float32 gap %.2e" % gap)
+    assert gc.DELTA >= 1e-4 and 10 * gap <= gc.DELTA
+    assert gap <= gc.MEASURED_GAP
+
+
+@pytest.mark.parametrize("case", gc.GATED_CASES, ids=_IDS)
+def test_opening_the_gate_moves_the_gradient(param_set, case):
+    """(d): the gradient with the case's gate open (straight-through) differs from the true one by more than ten times the
+    2e-3 bar of the GPU comparison on one leaf or more — a kernel without the gate cannot pass the case."""
+    b, (_, _, _, g_true), _ = _gated(case, param_set)
+    _, _, _, g_open = gc.oracle(b, case[3], straight_through={gc.GATE[case[0]]})
+    sep = gc.leaf_separation(g_true, g_open)
+    leaf = max(sep, key=lambda k: sep[k] if np.isfinite(sep[k]) else -1.0)
+    print(case[0], param_set, "largest separation: leaf", leaf, "%.3g" % sep[leaf])
+    assert np.isfinite(sep[leaf]) and sep[leaf] > gc.SEPARATION
+
+
+@pytest.mark.parametrize("case", gc.GATED_CASES, ids=_IDS)
+def test_gated_case_oracle_gradient_is_finite(param_set, case):
+    """(e) for floor-end, and the same for every case: the oracle's gradient is finite on every leaf, also where particles
+    are floored at z_K and the value is +inf; no loss is NaN or -inf."""
+    _, (value, losses, _, g), _ = _gated(case, param_set)
+    assert not np.isnan(losses).any() and not (losses == -np.inf).any()
+    if case[0] == "floor-end":
+        assert value == np.inf and np.isinf(losses).any()
+    if case[0] == "clip-pq-1e2":
+        assert np.isfinite(losses).all()
+    flat = gc.leaf_separation(g, g)   # walks every leaf
+    for path in flat:
+        node = g
+        for k in path.split("/"):
+            node = node[k]
+        assert np.isfinite(node).all(), path
+
+
+def test_trace_and_straight_through_leave_the_default_outputs_alone():
+    """trace= only records; an empty straight_through set is the default: same bits."""
+    case = gc.case_by_id("clamp-dds-gmm")
+    b = gc.build_case(case)
+    ref = gc.oracle(b, case[3])
+    got = gc.oracle(b, case[3], trace={}, straight_through=set())
+    assert ref[0] == got[0] and np.array_equal(ref[1], got[1]) and np.array_equal(ref[2], got[2])
+    assert gc.leaf_separation(ref[3], got[3]) and max(gc.leaf_separation(ref[3], got[3]).values()) == 0.0
+    with pytest.raises(ValueError):
+        gc.oracle(b, case[3], straight_through={"relu"})
