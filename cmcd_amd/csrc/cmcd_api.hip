@@ -470,39 +470,50 @@ static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
   return CMCD_OK;
 }
 
+// What cmcd_bound_reverse and cmcd_bound_segment do between their own argument checks and their kernel launch, in this order:
+// plan (refuses the modes and targets without an instance before the layout is looked at), layout, many_gmm constants,
+// workspace, the prep launch (the forward call's tables, formed by the same launch, on every call), and the TrajArgs of a
+// wave-per-tile launch with one statistics record per 16-particle tile.
+static int chain_call_begin(const cmcd_desc& d, const cmcd_layout* lay, PlanKind kind, const int32_t* seeds, int64_t n,
+                            const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
+                            int64_t workspace_bytes, float* out_loss, float* out_z, hipStream_t stream, CallPlan& p, TrajArgs& ta) {
+  int rc;
+  if ((rc = make_plan(d, n, n_target, kind, false, p)) != CMCD_OK) return rc;
+  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
+  float* ws = static_cast<float*>(workspace);
+  launch_prep(p.d, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
+  ta = TrajArgs{seeds, params, ws, reinterpret_cast<double*>(ws + p.w.partials), out_loss, out_z, *lay, p.w, n, (int32_t)d.nbridges,
+                d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0, p.d.grad_clipping, nullptr,
+                d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
+  return CMCD_OK;
+}
+
+// ... and behind it: merge the statistics
+static int chain_call_end(const TrajArgs& ta, double* out_stats, hipStream_t stream) {
+  launch_finalize(ta.partials, ta.w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
 // the reverse-time chain: x[n][dim] target draws -> out_w, out_z0, statistics over l := w (cmcd_reverse.hip)
 static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, const float* x, int64_t n,
                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
                         int64_t workspace_bytes, float* out_w, float* out_z0, double* out_stats, void* stream_) {
-  // 1. validate
   int rc = check_desc(desc);
   if (rc != CMCD_OK) return rc;
   if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_stats)
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
   if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  const cmcd_desc& d = *desc;
-  // 2. plan (refuses the modes and targets without a reverse kernel before the layout is looked at)
-  CallPlan p;
-  if ((rc = make_plan(d, n, n_target, PLAN_REVERSE, false, p)) != CMCD_OK) return rc;
-  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
-  const cmcd_desc& e = p.d;
-  const WsLayout& w = p.w;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  // 3. prep: the forward call's tables, formed by the same launch
-  launch_prep(e, *lay, w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
-  // 4. launch: one statistics record per 16-particle tile
-  double* partials = reinterpret_cast<double*>(ws + w.partials);
-  TrajArgs ta{seeds, params, ws, partials, out_w, out_z0, *lay, w, n, (int32_t)d.nbridges, d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0,
-              e.grad_clipping, nullptr, d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
+  CallPlan p;
+  TrajArgs ta;
+  if ((rc = chain_call_begin(*desc, lay, PLAN_REVERSE, seeds, n, params, n_params, target_consts, n_target, workspace,
+                             workspace_bytes, out_w, out_z0, stream, p, ta)) != CMCD_OK) return rc;
   snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_traj_kernel");
-  if ((rc = reverse_launch(e, w, ta, x, stream)) != CMCD_OK) return rc;
-  // 5. merge the statistics
-  launch_finalize(partials, w.n_waves, out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
+  if ((rc = reverse_launch(p.d, p.w, ta, x, stream)) != CMCD_OK) return rc;
+  return chain_call_end(ta, out_stats, stream);
 }
 
 // bridges [k0, k1) of the forward chain from the state (z, wpath, key); seeds are read when k0 == 0 (cmcd_segment.hip)
@@ -510,38 +521,22 @@ static int segment_impl(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k
                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
                         int64_t workspace_bytes, float* z, float* wpath, uint32_t* key, float* out_lg, double* out_stats,
                         void* stream_) {
-  // 1. validate
   int rc = check_desc(desc);
   if (rc != CMCD_OK) return rc;
   if (!lay || !params || !workspace || !z || !wpath || !key || !out_lg || !out_stats)
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
   if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  const cmcd_desc& d = *desc;
-  if (k0 < 0 || k0 >= k1 || k1 > d.nbridges)
+  if (k0 < 0 || k0 >= k1 || k1 > desc->nbridges)
     return fail(CMCD_ERR_BAD_ARG, "segment bridges must satisfy 0 <= k0 < k1 <= nbridges (got k1 = %s%lld)", "", k1);
   if (k0 == 0 && !seeds) return fail(CMCD_ERR_BAD_ARG, "a segment that starts at bridge 0 needs seeds%s");
-  // 2. plan (refuses the modes and targets without a segment kernel before the layout is looked at)
-  CallPlan p;
-  if ((rc = make_plan(d, n, n_target, PLAN_SEGMENT, false, p)) != CMCD_OK) return rc;
-  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
-  const cmcd_desc& e = p.d;
-  const WsLayout& w = p.w;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  // 3. prep: the forward call's tables, formed by the same launch, on every segment
-  launch_prep(e, *lay, w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
-  // 4. launch: one statistics record per 16-particle tile
-  double* partials = reinterpret_cast<double*>(ws + w.partials);
-  TrajArgs ta{seeds, params, ws, partials, nullptr, nullptr, *lay, w, n, (int32_t)d.nbridges, d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0,
-              e.grad_clipping, nullptr, d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
+  CallPlan p;
+  TrajArgs ta;
+  if ((rc = chain_call_begin(*desc, lay, PLAN_SEGMENT, seeds, n, params, n_params, target_consts, n_target, workspace,
+                             workspace_bytes, nullptr, nullptr, stream, p, ta)) != CMCD_OK) return rc;
   snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_traj_kernel");
-  if ((rc = segment_launch(e, w, ta, k0, k1, z, wpath, key, out_lg, stream)) != CMCD_OK) return rc;
-  // 5. merge the statistics
-  launch_finalize(partials, w.n_waves, out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
+  if ((rc = segment_launch(p.d, p.w, ta, k0, k1, z, wpath, key, out_lg, stream)) != CMCD_OK) return rc;
+  return chain_call_end(ta, out_stats, stream);
 }
 
 // the VarGrad gradient on the tables (and, for work items and lgcp, the trajectory) in the workspace; kept: left there by

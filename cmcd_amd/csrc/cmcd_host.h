@@ -1,5 +1,6 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip, cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
+// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip (both through cmcd_tile.h, which holds what
+// the two share), cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
 // cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
 #pragma once
 #include <hip/hip_runtime.h>

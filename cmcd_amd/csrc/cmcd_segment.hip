@@ -19,18 +19,12 @@
 // when m > k0 and opens step m when m < k1; at a cut both segments run the same machine code on the same z_k (the segment
 // that ends there closes step k - 1 and forms lg, the one that starts there opens step k): one extra evaluation per cut.
 //
-// Mapping = the wave-per-tile trajectory kernel's (cmcd_kernels.hip: traj_kernel; cmcd_reverse.hip): one wave owns 16 particles
+// Mapping = the wave-per-tile trajectory kernel's (cmcd_kernels.hip: traj_kernel; the network, the key-chain step, the statistics
+// butterflies, the instance table and the launch are shared with cmcd_reverse.hip: cmcd_tile.h): one wave owns 16 particles
 // for the whole segment, lane (g, c) holds particle c and the hidden units {16 t + 4 g + r}; layer 2 on v_mfma_f32_16x16x4_f32
 // with the packed W2 A fragments streamed from LDS, layers 1 and 3 on the VALU; state, key and wpath stay in registers; one
 // statistics record per tile for finalize_kernel.  A NaN stays a NaN (the divergence signal, as in the forward call).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "cmcd_common.h"
-#include "cmcd_device.h"
-#include "cmcd_hip.h"
-#include "cmcd_host.h"
+#include "cmcd_tile.h"
 
 namespace cmcd {
 
@@ -42,153 +36,6 @@ struct SegmentArgs {
   uint32_t* key;     // [n][2]  in (k0 > 0) and out: gen_k0 -> gen_k1
   float* lg;         // [n]     out
 };
-
-// the A fragments of input tile ti + 1 requested while tile ti's matrix instructions run: the forward kernel's rule
-constexpr bool segment_pf(int ARCH, int D, int T) { return T == 9 || (D == 2 && (T == 2 || ARCH == CMCD_ARCH_DDS)); }
-
-// s(z, idx) for the 16 particles of this wave; brow / urow = row idx of the bias / residual tables (traj_kernel's eval_net).
-//   dds:     h1 = gelu(W1^T [z; tau] + b1); h2 = gelu(W2^T h1 + b2); clip(W3^T h2 + b3, +-1e4)
-//   geffner: u = [z; emb]; u += softplus(u W1 + b1); u += softplus(u W2 + b2); factor (u W3 + b3)
-template <int ARCH, int D, int T, bool PF>
-__device__ __forceinline__ void segment_eval_net(const float (&z)[D], const float* __restrict__ brow,
-                                                 const float* __restrict__ urow, const float* lds_w2, const float* lds_w1z,
-                                                 const float* lds_b2, const float* lds_w3t, const float* lds_b3, int lane,
-                                                 float (&s)[D]) {
-  constexpr int HP = 16 * T;
-  const int g = lane >> 4;
-  asm volatile("" ::: "memory");  // keep the LDS-resident weights streaming (no LICM into VGPRs)
-  f32x4 h[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    f32x4 pre = *reinterpret_cast<const f32x4*>(brow + 16 * t + 4 * g);
-#pragma unroll
-    for (int j = 0; j < D; ++j) pre += z[j] * *reinterpret_cast<const f32x4*>(lds_w1z + j * HP + 16 * t + 4 * g);
-    if (ARCH == CMCD_ARCH_DDS) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h[t][r] = gelu_fast(pre[r]);
-    } else {
-      f32x4 u = *reinterpret_cast<const f32x4*>(urow + 16 * t + 4 * g);
-      if (16 * t < D) {  // the first D neurons of u are z itself
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int nidx = 16 * t + 4 * g + r;
-#pragma unroll
-          for (int j = 0; j < D; ++j)
-            if (j >= 16 * t && j < 16 * t + 16) u[r] = (nidx == j) ? z[j] : u[r];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h[t][r] = u[r] + softplus(pre[r]);
-    }
-  }
-  // layer 2 on the matrix cores: acc[to] rows = neurons 16 to + 4 g + r, columns = particles
-  f32x4 acc[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t) acc[t] = *reinterpret_cast<const f32x4*>(lds_b2 + 16 * t + 4 * g);
-  if (PF) {
-    f32x4 af[2][T];
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int to = 0; to < T; ++to) af[0][to] = *reinterpret_cast<const f32x4*>(lds_w2 + (to * 64 + lane) * 4);
-#pragma unroll
-    for (int ti = 0; ti < T; ++ti) {
-      asm volatile("" ::: "memory");
-      if (ti + 1 < T) {
-#pragma unroll
-        for (int to = 0; to < T; ++to)
-          af[(ti + 1) & 1][to] = *reinterpret_cast<const f32x4*>(lds_w2 + (((ti + 1) * T + to) * 64 + lane) * 4);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // the reads stay in front of the matrix instructions they overlap
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int to = 0; to < T; ++to)
-          acc[to] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[ti & 1][to][r], h[ti][r], acc[to], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else {
-#pragma unroll
-    for (int ti = 0; ti < T; ++ti) {
-      asm volatile("" ::: "memory");
-      f32x4 af[T];
-#pragma unroll
-      for (int to = 0; to < T; ++to) af[to] = *reinterpret_cast<const f32x4*>(lds_w2 + ((ti * T + to) * 64 + lane) * 4);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int to = 0; to < T; ++to) acc[to] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[to][r], h[ti][r], acc[to], 0, 0, 0);
-      }
-    }
-  }
-  // layer 3: every lane sums over its 4 T neurons, then the 4 lanes of a particle combine
-  float part[D];
-#pragma unroll
-  for (int j = 0; j < D; ++j) part[j] = 0.f;
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    f32x4 h2;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) h2[r] = (ARCH == CMCD_ARCH_DDS) ? gelu_fast(acc[t][r]) : h[t][r] + softplus(acc[t][r]);
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(lds_w3t + j * HP + 16 * t + 4 * g);
-      part[j] += h2[0] * wv[0] + h2[1] * wv[1] + h2[2] * wv[2] + h2[3] * wv[3];
-    }
-  }
-  const float factor = lds_b3[15];
-#pragma unroll
-  for (int j = 0; j < D; ++j) {
-    const float o = group_sum(part[j]) + lds_b3[j];
-    s[j] = (ARCH == CMCD_ARCH_DDS) ? fminf(fmaxf(o, -1e4f), 1e4f) : o * factor;
-  }
-}
-
-// one step of the key chain: (G, H) = split(gen); nz = normal(G, (D,)); gen = second(split(H)).  Lane row g computes block
-// (g & 1) of split(gen); the 2 + ceil(D / 2) blocks of split(H) and normal(G) are dealt to the four rows (traj_kernel's).
-template <int D>
-__device__ __forceinline__ void segment_chain_step(uint32_t& k0, uint32_t& k1, int g, float (&nz)[2 * ((D + 1) / 2)]) {
-  constexpr int Hh = (D + 1) / 2;
-  constexpr int NB = 2 + Hh;
-  const int gb = g & 1;
-  uint32_t x0 = gb, x1 = 2 + gb;
-  threefry2x32(k0, k1, x0, x1);
-  uint32_t g0, g1, h0, h1;
-  rows01(x0, g0, g1);
-  rows01(x1, h0, h1);
-#pragma unroll
-  for (int b0 = 0; b0 < NB; b0 += 4) {
-    const int b = b0 + g;
-    const bool is_split = b < 2;
-    const int jn = b - 2;   // block of normal(G): encrypts (jn, Hh + jn), pad counter 0
-    uint32_t y0 = is_split ? b : jn;
-    uint32_t y1 = is_split ? 2 + b : ((Hh + jn < D) ? Hh + jn : 0);
-    threefry2x32(is_split ? h0 : g0, is_split ? h1 : g1, y0, y1);
-    if (b0 == 0) rows01(y1, k0, k1);
-    if (D == 2) {
-      // the one normal block sits on row 2 with both words: word 1 moves to row 3, one conversion serves both
-      uint32_t t0, t1;
-      swap16(y1, y1, t0, t1);
-      const float dev = bits_to_normal(g == 3 ? t0 : y0);
-      uint32_t rr[4];
-      rows0123(__float_as_uint(dev), rr);
-      nz[0] = __uint_as_float(rr[2]);
-      nz[1] = __uint_as_float(rr[3]);
-    } else {
-      uint32_t r0[4], r1[4];
-      rows0123(__float_as_uint(bits_to_normal(y0)), r0);
-      rows0123(__float_as_uint(bits_to_normal(y1)), r1);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int jj = b0 + q - 2;
-        if (jj >= 0 && jj < Hh) {
-          nz[jj] = __uint_as_float(r0[q]);
-          nz[Hh + jj] = __uint_as_float(r1[q]);
-        }
-      }
-    }
-  }
-}
 
 template <int TARGET, int ARCH, int D, int T>
 __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_kernel(SegmentArgs sa) {
@@ -249,8 +96,8 @@ __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_ke
   if (ks == 0) {
     // ---- the forward call's start: split(PRNGKey(seed)) -> (A, B); z_0 = mean + std normal(A); gen_0 = second(split(first(split(B))))
     const int32_t seed = a.seeds[pl];
-    uint32_t x0 = gb, x1 = 2 + gb;
-    threefry2x32(0u, (uint32_t)seed, x0, x1);
+    uint32_t x0, x1;
+    tile_split(0u, (uint32_t)seed, gb, x0, x1);
     uint32_t a0, a1, b0, b1;
     rows01(x0, a0, a1);
     rows01(x1, b0, b1);
@@ -272,12 +119,10 @@ __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_ke
     }
 #pragma unroll
     for (int j = 0; j < D; ++j) z[j] = qstd[j] * nz[j] + qmean[j];
-    x0 = gb; x1 = 2 + gb;
-    threefry2x32(b0, b1, x0, x1);
+    tile_split(b0, b1, gb, x0, x1);
     uint32_t c0, c1;
     rows01(x0, c0, c1);
-    x0 = gb; x1 = 2 + gb;
-    threefry2x32(c0, c1, x0, x1);
+    tile_split(c0, c1, gb, x0, x1);
     rows01(x1, k0, k1);
     // wpath = -log q(z_0)
     w = 0.f;
@@ -318,8 +163,8 @@ __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_ke
     } else {
       // CAIS: s(z_m, m) serves both kernels; MCD_ULA_sn: s(z_m, m - 1) serves the backward kernel of step m - 1 only
       const int64_t row = (a.ula == 2) ? (m > 0 ? m - 1 : 0) : m;
-      segment_eval_net<ARCH, D, T, segment_pf(ARCH, D, T)>(z, bias1 + row * HP, utab + row * HP, lds_w2, lds_w1z, lds_b2,
-                                                           lds_w3t, lds_b3, lane, sn);
+      tile_eval_net<ARCH, D, T, tile_pf(ARCH, D, T), false>(z, bias1 + row * HP, utab + row * HP, lds_w2, lds_w1z, lds_b2,
+                                                       lds_w3t, lds_b3, lane, sn);
     }
     float gq[D];
 #pragma unroll
@@ -347,7 +192,7 @@ __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_ke
     const float* scr = a.ws + a.w.sched + 8 * (int64_t)m;   // {beta, eps, sigma, log sigma + log sqrt(2 pi), 1 / (2 sigma^2), ..}
     const float beta = scr[0], eps = scr[1], sig = scr[2], cst = scr[3], inv2s2 = scr[4];
     float nz[2 * Hh];
-    segment_chain_step<D>(k0, k1, g, nz);
+    tile_chain_step<D>(k0, k1, g, nz);
     fk_lp = 0.f;
 #pragma unroll
     for (int j = 0; j < D; ++j) {
@@ -391,16 +236,9 @@ __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_ke
   double sm = use ? (double)loss : 0.0;
   double sq = use ? (double)loss * (double)loss : 0.0;
   double mx = use ? -(double)loss : -INFINITY;
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) {
-    cnt += __shfl_xor(cnt, o);
-    sm += __shfl_xor(sm, o);
-    sq += __shfl_xor(sq, o);
-    mx = fmax(mx, __shfl_xor(mx, o));
-  }
+  tile_stats_butterfly(cnt, sm, sq, mx);
   double ex = (use && mx > -INFINITY && mx < INFINITY) ? exp(-(double)loss - mx) : 0.0;
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) ex += __shfl_xor(ex, o);
+  tile_stats_butterfly(ex);
   if (lane == 0) {
     double* o = a.partials + wave * CMCD_NSTATS;
     o[0] = cnt; o[1] = sm; o[2] = sq; o[3] = mx; o[4] = ex;
@@ -410,58 +248,19 @@ __global__ __launch_bounds__(512, (T > 4 || D > 4) ? 2 : 4) void segment_traj_ke
 // ------------------------------------------------------------------------------------------
 // launcher (cmcd_host.h)
 // ------------------------------------------------------------------------------------------
-typedef void (*segment_fn)(SegmentArgs);
+struct SegmentFamily {
+  typedef void (*fn)(SegmentArgs);
+  template <int TARGET, int ARCH, int D, int T>
+  static fn get() { return segment_traj_kernel<TARGET, ARCH, D, T>; }
+};
 
-template <int TARGET>
-static segment_fn segment_pick_geffner2(int T) {
-  switch (T) {
-    case 2: return segment_traj_kernel<TARGET, CMCD_ARCH_GEFFNER, 2, 2>;
-    case 4: return segment_traj_kernel<TARGET, CMCD_ARCH_GEFFNER, 2, 4>;
-    case 9: return segment_traj_kernel<TARGET, CMCD_ARCH_GEFFNER, 2, 9>;
-    default: return nullptr;
-  }
-}
-
-// the instances of the reverse call: gmm / many_gmm (d = 2) and funnel (d = 10); dds 64, geffner on 2, 4 and 9 neuron tiles
-// (funnel: 4 and 9 — its widths start at 4 tiles, cmcd_api.hip: hidden_width)
-static segment_fn segment_pick(const cmcd_desc& d, int T) {
-  if (d.mode == CMCD_MODE_CAIS_UHA_SN || d.target == CMCD_TARGET_LGCP) return nullptr;
-  if (d.arch == CMCD_ARCH_DDS) {
-    if (T != 4) return nullptr;
-    if (d.target == CMCD_TARGET_MANY_GMM && d.dim == 2) return segment_traj_kernel<CMCD_TARGET_MANY_GMM, CMCD_ARCH_DDS, 2, 4>;
-    if (d.target == CMCD_TARGET_GMM && d.dim == 2) return segment_traj_kernel<CMCD_TARGET_GMM, CMCD_ARCH_DDS, 2, 4>;
-    if (d.target == CMCD_TARGET_FUNNEL && d.dim == 10) return segment_traj_kernel<CMCD_TARGET_FUNNEL, CMCD_ARCH_DDS, 10, 4>;
-    return nullptr;
-  }
-  if (d.arch != CMCD_ARCH_GEFFNER) return nullptr;
-  if (d.target == CMCD_TARGET_MANY_GMM && d.dim == 2) return segment_pick_geffner2<CMCD_TARGET_MANY_GMM>(T);
-  if (d.target == CMCD_TARGET_GMM && d.dim == 2) return segment_pick_geffner2<CMCD_TARGET_GMM>(T);
-  if (d.target == CMCD_TARGET_FUNNEL && d.dim == 10) {
-    if (T == 4) return segment_traj_kernel<CMCD_TARGET_FUNNEL, CMCD_ARCH_GEFFNER, 10, 4>;
-    if (T == 9) return segment_traj_kernel<CMCD_TARGET_FUNNEL, CMCD_ARCH_GEFFNER, 10, 9>;
-  }
-  return nullptr;
-}
-
-bool segment_available(const cmcd_desc& d, int T) { return segment_pick(d, T) != nullptr; }
+bool segment_available(const cmcd_desc& d, int T) { return tile_pick<SegmentFamily>(d, T) != nullptr; }
 
 int segment_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, int32_t k0, int32_t k1, float* z, float* wpath,
                    uint32_t* key, float* lg, hipStream_t stream) {
-  segment_fn fn = segment_pick(d, w.T);
+  SegmentFamily::fn fn = tile_pick<SegmentFamily>(d, w.T);
   if (!fn) return fail(CMCD_ERR_UNSUPPORTED, "no segment kernel instance for this (mode, target, dim, arch, width=%s%lld)", "", w.HP);
-  const int64_t tiles = w.n_waves, D = d.dim;
-  const size_t lds_bytes = size_t(w.HP * w.HP + 2 * D * w.HP + w.HP + 16 + w.tgt_floats) * 4;
-  if (lds_bytes > 160 * 1024) return fail(CMCD_ERR_UNSUPPORTED, "network too wide for LDS%s");
-  // waves per workgroup: the forward wave-per-tile kernel's rule (cmcd_kernels.hip: traj_launch)
-  const int64_t per_cu = (160 * 1024) / (int64_t)lds_bytes;
-  int nw = tiles <= 1024 ? 1 : (tiles <= 8192 ? 4 : 8);
-  if (per_cu < 2 && tiles > 256) nw = tiles <= 1024 ? 4 : 8;
-  CMCD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes));
-  const unsigned blocks = unsigned((tiles + nw - 1) / nw);
-  SegmentArgs sa{ta, k0, k1, z, wpath, key, lg};
-  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * nw), lds_bytes, stream, sa);
-  return CMCD_OK;
+  return tile_launch(fn, d, w, SegmentArgs{ta, k0, k1, z, wpath, key, lg}, stream);
 }
 
 }  // namespace cmcd

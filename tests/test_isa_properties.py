@@ -387,3 +387,34 @@ def test_reverse_sweep_gemm_consumer_sums_without_atomics(lgcp_asm, kern):
     assert _scratch(tail) == 0
     assert not any("atomic" in l for l in body)
     assert sum("s_barrier" in l for l in body) >= 2      # cross-wave product sum, then the cross-wave column sums
+
+
+# ------------------------------------------------------------------------- r12: the reverse and segment kernels (cmcd_tile.h)
+@pytest.fixture(scope="module")
+def reverse_asm(tmp_path_factory):
+    from cmcd_amd import build
+    return _asm(tmp_path_factory, "cmcd_reverse.hip", build.EXTRA_FLAGS.get("cmcd_reverse.hip", []))
+
+
+@pytest.fixture(scope="module")
+def segment_asm(tmp_path_factory):
+    from cmcd_amd import build
+    return _asm(tmp_path_factory, "cmcd_segment.hip", build.EXTRA_FLAGS.get("cmcd_segment.hip", []))
+
+
+# (target, arch, D, T) of the eleven instances: gmm 0 / funnel 1 / many_gmm 2, geffner 0 / dds 1
+TILE_INSTANCES = [(t, 0, 2, T) for t in (0, 2) for T in (2, 4, 9)] + [(t, 1, 2, 4) for t in (0, 2)] + \
+                 [(1, 0, 10, 4), (1, 0, 10, 9), (1, 1, 10, 4)]
+# bytes of scratch per lane in the build of the commit before the two files were put on cmcd_tile.h; every other instance 0
+TILE_SCRATCH = {"reverse": {(1, 0, 10, 4): 116, (1, 0, 10, 9): 132}, "segment": {(1, 0, 10, 4): 52, (1, 0, 10, 9): 92}}
+
+
+def test_reverse_and_segment_instances_keep_their_scratch_sizes(reverse_asm, segment_asm):
+    """r12: moving the shared pieces of the two kernels into cmcd_tile.h was to leave their machine code alone; a helper that
+    looks harmless can change the register allocation of a whole kernel (the funnel geffner instances sit at 256 registers and
+    spill).  The eleven instances of each kernel report the ScratchSize they had before."""
+    for name, lines, args in (("reverse", reverse_asm, "11ReverseArgs"), ("segment", segment_asm, "11SegmentArgs")):
+        for inst in TILE_INSTANCES:
+            sym = "_ZN4cmcd19%s_traj_kernelILi%dELi%dELi%dELi%dEEEvNS_%sE" % ((name,) + inst + (args,))
+            _, tail = _kernel_whole(lines, sym)
+            assert _scratch(tail) == TILE_SCRATCH[name].get(inst, 0), (name, inst, _scratch(tail))
