@@ -32,6 +32,14 @@ class Layout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in LAYOUT_FIELDS]
 
 
+HAIS_LAYOUT_FIELDS = ("vd_mean", "vd_logdiag", "eps", "eta", "md", "mgridref_y", "gridref_x", "target_x", "ngrid")
+
+
+class HaisLayout(C.Structure):
+    """cmcd_hais_layout of include/cmcd_hip.h."""
+    _fields_ = [(k, C.c_int64) for k in HAIS_LAYOUT_FIELDS]
+
+
 class ProjectRange(C.Structure):
     """cmcd_project_range of include/cmcd_hip.h."""
     _fields_ = [("offset", C.c_int64), ("length", C.c_int64), ("kind", C.c_int32), ("reserved", C.c_int32),
@@ -102,6 +110,12 @@ def lib():
         L.cmcd_mfvi_bound_grad.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmcd_hais_workspace_bytes.restype = C.c_int64
+        L.cmcd_hais_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+        L.cmcd_hais_bound_grad.restype = C.c_int
+        L.cmcd_hais_bound_grad.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HaisLayout), C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmcd_adam_step.restype = C.c_int
         L.cmcd_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_float,

@@ -4,8 +4,9 @@ mean-field VI bound (`nbridges = 0`) that /root/reference/src/main.py:82-109 opt
 
 `initialize` reproduces the reference's parameter tree (and so the `params_flat` layout) for any
 `nbridges`; `compute_bound` / `grad_and_loss` run on the GPU through the C ABI (`cmcd_mfvi_bound_grad`)
-for `nbridges = 0` and raise `NotImplementedError` for the UHA chain (`nbridges >= 1`, ais_utils.evolve —
-outside this build's scope)."""
+for `nbridges = 0` and raise `NotImplementedError` for `nbridges >= 1`: the UHA chain (ais_utils.evolve, Hamiltonian AIS) is
+reached through `cmcd_amd.hais`, whose `initialize` is this module's and whose `compute_bound` / `grad_and_loss` take the same
+arguments (`cmcd_hais_bound_grad`)."""
 import torch
 
 from . import _lib

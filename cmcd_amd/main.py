@@ -6,8 +6,9 @@
   ->  opt.sample / log_final_losses (n_input_dist_seeds x n_samples)  [-> the same with the EMA parameters]
 
 Flag names, defaults and the `--config.x value` / `--config.x=value` / `--noconfig.x` forms follow
-/root/reference/src/configs/base.py:77-155 (ml_collections + absl).  Left out: W&B, plotting, the inference-gym rows of the lr table.  Modes outside the overdamped family and 2nd-order
-CMCD (`MCD_CAIS_UHA_sn`) raise NotImplementedError exactly like the library.  Under torchrun the particles of every iteration are sharded over the
+/root/reference/src/configs/base.py:77-155 (ml_collections + absl).  Left out: W&B, plotting, the inference-gym rows of the lr table.  `UHA` (Hamiltonian AIS, the reference's default
+boundmode) runs through cmcd_amd.hais on one GPU; modes outside it, the overdamped family and 2nd-order CMCD (`MCD_CAIS_UHA_sn`)
+raise NotImplementedError exactly like the library.  Under torchrun the particles of every iteration are sharded over the
 ranks (parallel.make_sharded_grad_and_loss)."""
 import os
 import sys
@@ -200,25 +201,44 @@ def main(config):
         say("Done training initial parameters, got ELBO %.2f." % elbo_init)
     vdparams_init = {k: v.detach().cpu().clone() for k, v in unflatten(params_flat)[0]["vd"].items()}
 
-    if "MCD" not in config.boundmode:
-        raise NotImplementedError("Mode %s not implemented." % config.boundmode)       # UHA: outside this build
-    trainable = ("eta", "gamma")
-    if config.train_eps:
-        trainable += ("eps",)
-    if config.train_vi:
-        trainable += ("vd",)
-    if config.train_betas:
-        trainable += ("mgridref_y",)
-    say(f"Params being trained : {trainable}")
-    params_flat, unflatten, params_fixed = mcdbm.initialize(
-        dim=dim, nbridges=config.nbridges, vdparams=vdparams_init, eta=config.init_eta, eps=config.init_eps,
-        gamma=config.init_gamma, trainable=trainable, mode=config.boundmode, emb_dim=config.emb_dim, nlayers=config.nlayers,
-        nn_arch=config.nn_arch, device=device)
-    grad_and_loss, loss_fn = mcdbm.make_grad_and_loss(config.boundmode, eps_schedule=config.eps_schedule,
-                                                      grad_clipping=config.grad_clipping)
-    if world > 1:
-        grad_and_loss = parallel.make_sharded_grad_and_loss(config.boundmode, eps_schedule=config.eps_schedule,
-                                                            grad_clipping=config.grad_clipping)
+    if config.boundmode == "UHA":                                          # main.py:115-136
+        # Hamiltonian AIS (cmcd_amd.hais).  The reference writes `trainable = "eta"`, a str, and its `trainable + ("eps",)` raises
+        # TypeError with its own default flags; the tuple below is what it means.
+        from . import hais
+        if world > 1:
+            raise NotImplementedError("boundmode UHA runs on one GPU: its particles are not sharded over ranks")
+        trainable = ("eta",)
+        if config.train_eps:
+            trainable += ("eps",)
+        if config.train_vi:
+            trainable += ("vd",)
+        if config.train_betas:
+            trainable += ("mgridref_y",)
+        say(f"Params being trained : {trainable}")
+        params_flat, unflatten, params_fixed = hais.initialize(
+            dim=dim, nbridges=config.nbridges, eta=config.init_eta, eps=config.init_eps, lfsteps=config.lfsteps,
+            vdparams=vdparams_init, trainable=trainable, device=device)
+        grad_and_loss, loss_fn = hais.grad_and_loss, hais.compute_bound
+    elif "MCD" in config.boundmode:
+        trainable = ("eta", "gamma")
+        if config.train_eps:
+            trainable += ("eps",)
+        if config.train_vi:
+            trainable += ("vd",)
+        if config.train_betas:
+            trainable += ("mgridref_y",)
+        say(f"Params being trained : {trainable}")
+        params_flat, unflatten, params_fixed = mcdbm.initialize(
+            dim=dim, nbridges=config.nbridges, vdparams=vdparams_init, eta=config.init_eta, eps=config.init_eps,
+            gamma=config.init_gamma, trainable=trainable, mode=config.boundmode, emb_dim=config.emb_dim, nlayers=config.nlayers,
+            nn_arch=config.nn_arch, device=device)
+        grad_and_loss, loss_fn = mcdbm.make_grad_and_loss(config.boundmode, eps_schedule=config.eps_schedule,
+                                                          grad_clipping=config.grad_clipping)
+        if world > 1:
+            grad_and_loss = parallel.make_sharded_grad_and_loss(config.boundmode, eps_schedule=config.eps_schedule,
+                                                                grad_clipping=config.grad_clipping)
+    else:
+        raise NotImplementedError("Mode %s not implemented." % config.boundmode)
 
     t0 = time.time()
     _, params_flat, ema_params = opt.run(config, config.lr, config.iters, params_flat, unflatten, params_fixed,

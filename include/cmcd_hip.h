@@ -313,6 +313,42 @@ int cmcd_mfvi_bound_grad(int32_t target, int32_t dim, int64_t off_vd_mean, int64
                          void* workspace, int64_t workspace_bytes,
                          float* out_loss, float* out_z, double* out_stats, float* grad, void* stream);
 
+/* ---- UHA, Hamiltonian AIS: the reference's plain bounding machine with nbridges >= 1 (config.boundmode = "UHA",
+ * /root/reference/src/boundingmachine.py:73-111 -> ais_utils.py:7-69 -> momdist.py:13-28), bound and reparameterised gradient.
+ * No network.  Per seed, with s = exp(md), L = lfsteps, gU(z, b) = -(b grad log p(z) + (1 - b) grad log q(z)) (no clip):
+ *   (A, B) = split(PRNGKey(seed));  z = mean + exp(logdiag) normal(A);  w = -log q(z)
+ *   C = first(split(B));  (R, G') = split(C);  rho_prev = s normal(R);  gen = second(split(G'))
+ *   beta = interp(target_x, gridref_x, [0, cumsum(mgridref_y) / sum(mgridref_y)])
+ *   for i = 0 .. nbridges-1:
+ *     (G, H) = split(gen);  xi = normal(G);  gen = second(split(H))
+ *     rho = eta rho_prev + sqrt(1 - eta^2) s xi
+ *     r = rho - eps/2 gU(z, beta_i);  z += eps r / s^2;  (L-1) times: r -= eps gU(z, beta_i), z += eps r / s^2;
+ *     r -= eps/2 gU(z, beta_i);  w += log N(r; 0, s) - log N(rho; 0, s);  rho_prev = r
+ *   w += log p(z);  loss = -w
+ * (eps is the scalar parameter, constant over the bridges; no initial or final momentum term; delta_H is not produced).
+ * out_loss / out_z / out_stats as cmcd_bound_forward.  grad (nullable: forward only) [n_params], overwritten:
+ * omega * sum_n d loss_n / d {vd.mean, vd.logdiag, eps, eta, md, mgridref_y}, zeros elsewhere; omega = 1 / N_total.  The forward
+ * call and the gradient call return the same loss bits, repeated calls the same gradient bits (per-tile slots summed in a
+ * fixed order, no floating-point atomics).  A gradient call keeps (nbridges L + 1) + (2 nbridges + 1) rows of n dim floats in the
+ * workspace.  Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward.
+ * Targets: gmm, many_gmm (dim 2), funnel (dim 10); lgcp and every other (target, dim): CMCD_ERR_UNSUPPORTED, and 0 from the
+ * size query.  nbridges <= 4096, ngrid <= 1024, eta < 1. */
+typedef struct cmcd_hais_layout {          /* offsets (in floats) of the leaves inside params_flat */
+  int64_t vd_mean, vd_logdiag;             /* [dim] each                                      */
+  int64_t eps, eta;                        /* scalars                                         */
+  int64_t md;                              /* [dim]  log scales of the momentum distribution  */
+  int64_t mgridref_y;                      /* [ngrid+1]                                       */
+  int64_t gridref_x;                       /* [ngrid+2]                                       */
+  int64_t target_x;                        /* [nbridges]                                      */
+  int64_t ngrid;                           /* len(mgridref_y) - 1 (a count, not an offset)    */
+} cmcd_hais_layout;
+int64_t cmcd_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int32_t with_grad);
+int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* layout,
+                         const int32_t* seeds, int64_t n, const float* params, int64_t n_params,
+                         const float* target_consts, int64_t n_target, float omega,
+                         void* workspace, int64_t workspace_bytes,
+                         float* out_loss, float* out_z, double* out_stats, float* grad /* nullable: forward only */, void* stream);
+
 /* ---- Optimiser step of the training loop (/root/reference/src/opt.py:14-35,100-116) fused into one launch:
  * g = clip(grad, +-clip); Adam moments (optax.adam: bias correction 1 - b^step, eps outside the root);
  * params += -lr * m_hat / (sqrt(v_hat) + eps); projection of the listed ranges (opt.py:14-24);

@@ -22,6 +22,8 @@ ap.add_argument("--model", default="many_gmm")
 ap.add_argument("--boundmode", default="MCD_CAIS_sn")
 ap.add_argument("--N", type=int, default=300)
 ap.add_argument("--nbridges", type=int, default=8)
+ap.add_argument("--lfsteps", type=int, default=1, help="boundmode UHA: leap-frog steps per bridge")
+ap.add_argument("--init_eta", type=float, default=0.0, help="boundmode UHA: initial momentum persistence")
 ap.add_argument("--nn_arch", default="geffner")
 ap.add_argument("--emb_dim", type=int, default=20)
 ap.add_argument("--init_sigma", type=float, default=1.0)
@@ -76,8 +78,16 @@ if cfg.pretrain_mfvi:
     print("Done training initial parameters, got ELBO %.2f.  (%.2f ms/iter)" % (elbo_init, (time.time() - t) / cfg.mfvi_iters * 1e3))
 vdparams_init = {k: v.detach().cpu().clone() for k, v in unflatten(flat)[0]["vd"].items()}
 
-# 2. MCD machine
-trainable = ("eta", "gamma")
+# 2. the annealed machine: Hamiltonian AIS (boundmode UHA, cmcd_amd.hais) or one of the MCD modes
+if cfg.boundmode == "UHA":
+    from cmcd_amd import hais
+    if WORLD > 1:
+        raise NotImplementedError("boundmode UHA runs on one GPU: its particles are not sharded over ranks")
+    trainable = ("eta",)
+elif "MCD" in cfg.boundmode:
+    trainable = ("eta", "gamma")
+else:
+    raise NotImplementedError("Mode %s not implemented." % cfg.boundmode)
 if cfg.train_eps:
     trainable += ("eps",)
 if cfg.train_vi:
@@ -85,15 +95,19 @@ if cfg.train_vi:
 if cfg.train_betas:
     trainable += ("mgridref_y",)
 print(f"Params being trained : {trainable}")
-flat, unflatten, fixed = mcdbm.initialize(dim=dim, nbridges=cfg.nbridges, vdparams=vdparams_init, eps=cfg.init_eps,
-                                          trainable=trainable, mode=cfg.boundmode, emb_dim=cfg.emb_dim,
-                                          nn_arch=cfg.nn_arch, device="cuda")
-grad_and_loss, loss_fn = mcdbm.make_grad_and_loss(cfg.boundmode, eps_schedule=cfg.eps_schedule, grad_clipping=cfg.grad_clipping)
-if WORLD > 1:
-    from cmcd_amd import parallel
-    grad_and_loss = parallel.make_sharded_grad_and_loss(cfg.boundmode, eps_schedule=cfg.eps_schedule,
-                                                        grad_clipping=cfg.grad_clipping)
-
+if cfg.boundmode == "UHA":
+    flat, unflatten, fixed = hais.initialize(dim=dim, nbridges=cfg.nbridges, eta=cfg.init_eta, eps=cfg.init_eps,
+                                             lfsteps=cfg.lfsteps, vdparams=vdparams_init, trainable=trainable, device="cuda")
+    grad_and_loss, loss_fn = hais.grad_and_loss, hais.compute_bound
+else:
+    flat, unflatten, fixed = mcdbm.initialize(dim=dim, nbridges=cfg.nbridges, vdparams=vdparams_init, eps=cfg.init_eps,
+                                              trainable=trainable, mode=cfg.boundmode, emb_dim=cfg.emb_dim,
+                                              nn_arch=cfg.nn_arch, device="cuda")
+    grad_and_loss, loss_fn = mcdbm.make_grad_and_loss(cfg.boundmode, eps_schedule=cfg.eps_schedule, grad_clipping=cfg.grad_clipping)
+    if WORLD > 1:
+        from cmcd_amd import parallel
+        grad_and_loss = parallel.make_sharded_grad_and_loss(cfg.boundmode, eps_schedule=cfg.eps_schedule,
+                                                            grad_clipping=cfg.grad_clipping)
 
 x_tgt = None
 res_sampler = res[2] if len(res) > 2 else None
