@@ -233,3 +233,81 @@ def leaf_separation(g_true, g_open):
                 out["/".join(path + (k,))] = diff / scale if scale > 0 else (np.inf if diff > 0 else 0.0)
     walk(g_true, g_open, ())
     return out
+
+
+# ------------------------------------------------------------------------------------------ UHA (cmcd_amd.hais)
+# The plain Hamiltonian AIS mode has no network, clip or clamp: its one gate is the many_gmm floor, which the forward kernel
+# meets in Target::eval and the reverse sweep in Target::eval_hess.  The yardstick is tests/hais_restatement.py.
+#
+# q = N((150, 0), ~15^2) sits beyond the floor (modes within +-40; log p <= -1e4 from about 105 units off the nearest mode)
+# and eps = 1: a floored particle feels grad log q alone and drifts on its momentum; one that comes inside is kicked by a
+# score of order 190 and may shoot through the modes and out on the far side.  Of the seeds 1 .. 2048 some therefore come
+# inside before z_K, a few cross outwards and end floored, most stay floored and a quarter never are.
+#
+# Two guards decide which seeds may be used, both from the float64 restatement alone:
+#   band   an evaluation within DELTA (relative) of the floor: float32 and float64 could fall on different sides.  8 seeds.
+#   ridge  an unfloored evaluation at which the two largest component log-densities are within RIDGE_NATS = 16 nats.  At a
+#          log-density of order -1e4 a float32 is spaced 1e-3, so the mixture weights (a softmax of such numbers) carry a
+#          relative error of 1e-3 wherever two components both count; with eps = 1 and a Hessian of order (d / s^2)^2 / 4 ~ 80
+#          across the ridge between two modes d ~ 10 apart, the chain amplifies it.  Measured per particle on the first 120
+#          unfloored seeds: float32 restatement against float64, worst leaf, as a share of the batch gradient: up to 2.5e-2
+#          where the gap is below 8 nats, below 1.3e-5 above 8 nats, below 1.2e-6 above 16 nats.  e^-16 = 1.1e-7 is a float32's
+#          unit roundoff: beyond it the second component does not reach the sum.  Without this guard the batch's gap was
+#          7.7e-3 (vd/logdiag), with smaller eps or a nearer q anything between 1e-7 and 0.5, by which seeds hit a ridge.
+# Categories of the band-clear seeds: 118 floored at early evaluations and inside at z_K, 6 that end floored after an
+# unfloored evaluation, 1361 floored at every evaluation, 555 never floored.  The batch takes the first 16 / 4 / 5 / 8 of
+# them that are clear of the ridge guard too, in seed order.  tests/test_hais_oracle.py re-derives every figure.
+HAIS_FLOOR = dict(target="many_gmm", dim=2, K=4, L=2, eps=1.0, eta=0.6, seed=3, sigma=15.0, mean_scale=0.0,
+                  mean_add=(150.0, 0.0), pool=2048, take=(16, 4, 5, 8))
+HAIS_FLOOR_CATEGORIES = ("floored mid-chain, inside at z_K", "ends floored", "floored throughout", "never floored")
+RIDGE_NATS = 16.0
+
+
+def hais_floor_params(device="cpu"):
+    import hais_restatement as hr
+    c = HAIS_FLOOR
+    return hr.make_params(c["dim"], c["K"], c["L"], c["eps"], eta=c["eta"], seed=c["seed"], sigma=c["sigma"],
+                          mean_scale=c["mean_scale"], mean_add=c["mean_add"], device=device)
+
+
+def component_gap(z):
+    """[..., 2] positions -> the two largest component log-densities of many_gmm apart, in nats (float64)."""
+    import math
+    from oracle.targets import many_gmm_means
+    mu = np.asarray(many_gmm_means(40, 2, 40.0), np.float64)
+    s = math.log1p(math.exp(0.1))
+    comp = -0.5 * (((np.asarray(z, np.float64)[..., None, :] - mu) / s) ** 2).sum(-1)
+    top = np.sort(comp, axis=-1)[..., -2:]
+    return top[..., 1] - top[..., 0]
+
+
+_hais_floor_cache = {}
+
+
+def hais_floor_pool():
+    """-> (seeds[pool], near[pool] bool: an evaluation within DELTA of the floor, ridge[pool] bool: an unfloored evaluation
+    within RIDGE_NATS of a ridge, category[pool] in 0 .. 3 (the index into HAIS_FLOOR_CATEGORIES)), from the unfloored log p
+    and the positions of the float64 restatement at every one of the K L + 1 evaluations."""
+    if "pool" not in _hais_floor_cache:
+        import hais_restatement as hr
+        c = HAIS_FLOOR
+        flat, un, fixed = hais_floor_params()
+        seeds = np.arange(1, c["pool"] + 1, dtype=np.int32)
+        trace = {}
+        hr.forward(seeds, hr.params_numpy(un, flat), c["dim"], c["K"], c["L"], c["target"], trace=trace)
+        lp = np.stack(trace["lp"])                             # [K L + 1, pool]
+        assert lp.shape == (c["K"] * c["L"] + 1, c["pool"])
+        near = (np.abs(lp - FLOOR) <= DELTA * -FLOOR).any(0)
+        fl = lp <= FLOOR
+        ridge = ((component_gap(np.stack(trace["z"])) < RIDGE_NATS) & ~fl).any(0)
+        cat = np.where(fl.all(0), 2, np.where(fl[-1], 1, np.where(fl.any(0), 0, 3)))
+        _hais_floor_cache["pool"] = (seeds, near, ridge, cat)
+    return _hais_floor_cache["pool"]
+
+
+def hais_floor_batch():
+    """-> (seeds[33] in seed order, category[33]): the first take[k] seeds of every category that both guards leave."""
+    seeds, near, ridge, cat = hais_floor_pool()
+    ok = ~near & ~ridge
+    pick = np.sort(np.concatenate([np.flatnonzero(ok & (cat == k))[:t] for k, t in enumerate(HAIS_FLOOR["take"])]))
+    return seeds[pick], cat[pick]

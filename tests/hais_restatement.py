@@ -34,9 +34,10 @@ def params_numpy(unflatten, params_flat):
 LEAVES = (("vd", "mean"), ("vd", "logdiag"), ("eps",), ("eta",), ("md",), ("mgridref_y",))
 
 
-def to_torch(p, requires_grad=True):
-    """float64 torch leaves of the six differentiable leaves (the two grids are not needed: both are uniform)."""
-    t = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=torch.float64).requires_grad_(requires_grad)
+def to_torch(p, requires_grad=True, dtype=torch.float64):
+    """torch leaves (float64 unless `dtype` says otherwise) of the six differentiable leaves (the two grids are not needed:
+    both are uniform)."""
+    t = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=dtype).requires_grad_(requires_grad)
     return {"vd": {"mean": t(p["vd"]["mean"]), "logdiag": t(p["vd"]["logdiag"])}, "eps": t(p["eps"]), "eta": t(p["eta"]),
             "md": t(p["md"]), "mgridref_y": t(p["mgridref_y"])}
 
@@ -66,21 +67,26 @@ def grad_u(p, logp_fn, z, beta, create_graph=True):
     return -1.0 * (beta * gp + (1.0 - beta) * gq)
 
 
-def leapfrog(p, logp_fn, z, rho, beta, lfsteps, create_graph=True):
-    """ais_utils.py:26-57 without delta_H; grad K(rho) = rho / s^2."""
+def leapfrog(p, logp_fn, z, rho, beta, lfsteps, create_graph=True, record=None):
+    """ais_utils.py:26-57 without delta_H; grad K(rho) = rho / s^2.  `record(z)` is called at the position of the opening kick
+    and of every inner kick (the closing kick's position is the next bridge's opening one, or z_K)."""
     eps, iv = p["eps"], torch.exp(-2.0 * p["md"])
+    if record is not None:
+        record(z)
     rho = rho - eps * grad_u(p, logp_fn, z, beta, create_graph) / 2.0
     z = z + eps * rho * iv
     for _ in range(lfsteps - 1):
+        if record is not None:
+            record(z)
         rho = rho - eps * grad_u(p, logp_fn, z, beta, create_graph)
         z = z + eps * rho * iv
     rho = rho - eps * grad_u(p, logp_fn, z, beta, create_graph) / 2.0
     return z, rho
 
 
-def noise(seeds, dim, nbridges):
+def noise(seeds, dim, nbridges, dtype=torch.float64):
     e0, n0, xi = prng.particle_noise_uha(np.asarray(seeds), dim, nbridges)
-    t = lambda a: torch.tensor(a.astype(np.float64))
+    t = lambda a: torch.tensor(a.astype(np.float64), dtype=dtype)
     return t(e0), t(n0), t(xi)
 
 
@@ -88,10 +94,20 @@ def z0_of(p, e0):
     return torch.exp(p["vd"]["logdiag"]) * e0 + p["vd"]["mean"]
 
 
-def losses(seeds, p, dim, nbridges, lfsteps, target, create_graph=True):
-    """-> (losses[N], z[N, dim]) float64, differentiable in the leaves of `p` (a to_torch dict)."""
+def losses(seeds, p, dim, nbridges, lfsteps, target, create_graph=True, trace=None):
+    """-> (losses[N], z[N, dim]) in the dtype of `p` (a to_torch dict: float64 unless asked otherwise), differentiable in its
+    leaves.  `trace` (a dict) receives, at each of the K L + 1 evaluations in chain order, log p BEFORE its floor under "lp"
+    ([N] NumPy arrays) and the position under "z" ([N, dim]): the last entries are the end point's."""
     logp_fn = ot.TARGETS[target] if isinstance(target, str) else target
-    e0, n0, xi = noise(seeds, dim, nbridges)
+    record = None
+    if trace is not None:
+        raw = getattr(logp_fn, "unfloored", logp_fn)
+
+        def record(zz):
+            with torch.no_grad():
+                trace.setdefault("lp", []).append(raw(zz.detach()).numpy().copy())
+                trace.setdefault("z", []).append(zz.detach().numpy().copy())
+    e0, n0, xi = noise(seeds, dim, nbridges, dtype=p["eps"].dtype)
     s = torch.exp(p["md"])
     z = z0_of(p, e0)
     w = -log_q(p["vd"], z)
@@ -100,42 +116,65 @@ def losses(seeds, p, dim, nbridges, lfsteps, target, create_graph=True):
         rho_prev = s * n0
         for i in range(nbridges):
             rho = p["eta"] * rho_prev + torch.sqrt(1.0 - p["eta"] ** 2) * s * xi[:, i, :]
-            z, r = leapfrog(p, logp_fn, z, rho, betas[i], lfsteps, create_graph)
+            z, r = leapfrog(p, logp_fn, z, rho, betas[i], lfsteps, create_graph, record)
             w = w + log_mom(p["md"], r) - log_mom(p["md"], rho)
             rho_prev = r
+    if record is not None:
+        record(z)
     w = w + logp_fn(z)
     return -w, z
 
 
-def bound_and_grad(seeds, p_np, dim, nbridges, lfsteps, target):
-    """-> (losses, z, {leaf path: d mean(losses) / d leaf}) as NumPy; what jax.grad(bm.compute_bound, 1) returns, leaf by leaf."""
-    p = to_torch(p_np)
+def bound_and_grad(seeds, p_np, dim, nbridges, lfsteps, target, dtype=torch.float64):
+    """-> (losses, z, {leaf path: d mean(losses) / d leaf}) as NumPy; what jax.grad(bm.compute_bound, 1) returns, leaf by leaf.
+    `dtype = torch.float32` runs the same arithmetic in single precision: only to measure what float32 alone costs on a case."""
+    p = to_torch(p_np, dtype=dtype)
     l, z = losses(seeds, p, dim, nbridges, lfsteps, target)
     gs = torch.autograd.grad(l.mean(), [leaf(p, path) for path in LEAVES], allow_unused=True)
-    grads = {path: (np.zeros(tuple(leaf(p, path).shape)) if g is None else g.detach().numpy()) for path, g in zip(LEAVES, gs)}
+    grads = {path: (np.zeros(tuple(leaf(p, path).shape)) if g is None else g.detach().numpy().astype(np.float64))
+             for path, g in zip(LEAVES, gs)}
     return l.detach().numpy(), z.detach().numpy(), grads
 
 
-def forward(seeds, p_np, dim, nbridges, lfsteps, target):
+def forward(seeds, p_np, dim, nbridges, lfsteps, target, trace=None, dtype=torch.float64):
     """Losses and end points without building the second-order graph."""
-    p = to_torch(p_np, requires_grad=False)
+    p = to_torch(p_np, requires_grad=False, dtype=dtype)
     with torch.enable_grad():
-        l, z = losses(seeds, p, dim, nbridges, lfsteps, target, create_graph=False)
+        l, z = losses(seeds, p, dim, nbridges, lfsteps, target, create_graph=False, trace=trace)
     return l.detach().numpy(), z.detach().numpy()
 
 
+def float32_gap(seeds, p_np, dim, nbridges, lfsteps, target):
+    """{leaf path: max |g32 - g64| / max |g64|}: the restatement's gradient in float32 against its float64 run, same seeds."""
+    g64 = bound_and_grad(seeds, p_np, dim, nbridges, lfsteps, target)[2]
+    g32 = bound_and_grad(seeds, p_np, dim, nbridges, lfsteps, target, dtype=torch.float32)[2]
+    return {path: float(np.abs(g32[path] - g64[path]).max() / np.abs(g64[path]).max()) for path in LEAVES}
+
+
+def fractions(nbridges, ngrid):
+    """The interpolation weight of every bridge inside its cell of gridref_x (ot.betas_from_grid's `frac`), float64."""
+    pos = np.arange(1, nbridges + 1, dtype=np.float64) / (nbridges + 1) * (ngrid + 1)
+    j = np.clip(np.floor(pos).astype(np.int64) + 1, 1, ngrid + 1)
+    return pos - (j - 1), j
+
+
 def make_params(dim, nbridges, lfsteps, eps, eta=0.6, seed=0, trainable=("eta", "eps", "vd", "mgridref_y", "md"), device="cpu",
-                mean_scale=1.0, sigma=1.0, vd=None):
+                mean_scale=1.0, sigma=1.0, vd=None, ngrid=None, mean_add=None):
     """A parameter set with every leaf non-trivial: random mean and md, per-dimension logdiag, eta around 0.6, a non-uniform
-    mgridref_y; `vd = (mean, sigma)` replaces the random q by a given one.  -> (params_flat, unflatten, params_fixed) of cmcd_amd.hais.initialize."""
+    mgridref_y of length `ngrid + 1` (default min(nbridges, 32), the reference's; any other value takes the bridges off the
+    grid's nodes); `vd = (mean, sigma)` replaces the random q by a given one, `mean_add` shifts the drawn mean.
+    -> (params_flat, unflatten, params_fixed) of cmcd_amd.hais.initialize."""
     from cmcd_amd import hais
     rng = np.random.default_rng(seed)
     f32 = lambda a: torch.tensor(np.asarray(a, np.float32))
     drawn = {"mean": f32(mean_scale * rng.standard_normal(dim)), "logdiag": f32(math.log(sigma) + 0.2 * rng.standard_normal(dim))}
     if vd is not None:
         vd = {"mean": f32(vd[0]), "logdiag": f32(np.log(np.asarray(vd[1], np.float64)))}
+    if mean_add is not None:
+        drawn["mean"] = drawn["mean"] + f32(mean_add)
     md = f32(0.3 * rng.standard_normal(dim))
-    ngrid = min(nbridges, 32)
+    if ngrid is None:
+        ngrid = min(nbridges, 32)
     my = f32(0.5 + rng.random(ngrid + 1))
     return hais.initialize(dim, vdparams=vd if vd is not None else drawn, nbridges=nbridges, lfsteps=lfsteps, eps=eps, eta=eta, mdparams=md, mgridref_y=my,
                            trainable=trainable, device=device)

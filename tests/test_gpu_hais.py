@@ -5,14 +5,22 @@ bit-reproducibility, capture, error paths, training and the command-line driver.
 
 Parameter sets have every leaf non-trivial (hais_restatement.make_params: random mean and md, per-dimension logdiag, eta 0.6,
 non-uniform mgridref_y); eps per target so that the restatement's losses are finite on every seed — except the many_gmm floor
-case, whose q is wide enough for some end points to lie where log p is floored to -inf."""
+cases, whose q is wide enough (forward) or far enough out (gated_cases.HAIS_FLOOR, gradient) for log p to be floored to -inf.
+
+Which gradient case reaches what in cmcd_hais.hip: n = 145 / 133 (10 / 9 tiles) run hais_grad_kernel in three workgroups, the
+last with two (three) idle waves, and the eight-wide loop of hais_reduce_kernel once plus its remainder loop; K = 40, (K, ngrid)
+= (8, 3) and (5, 32) put the bridges off the grid's nodes (frac inside (0, 1), cells with several bridges and with none);
+the floor case runs the lp > -1e4 gate of eval_hess; n_mixes = 17 the generic component loops behind hais_stage_target;
+n_total the omega of the C call."""
 import functools
 import math
+import types
 
 import numpy as np
 import pytest
 import torch
 
+import gated_cases as gc
 import hais_restatement as hr
 from cmcd_amd import boundingmachine as bm
 from cmcd_amd import hais, model_handler, opt
@@ -29,22 +37,36 @@ def target_of(name):
     return model_handler.load_model(name)[0]
 
 
+DEVICE = "cuda"
+
+
 @functools.lru_cache(maxsize=None)
-def built(name, K, L, trainable=("eta", "eps", "vd", "mgridref_y", "md"), eps=None, sigma=None):
+def built(name, K, L, trainable=("eta", "eps", "vd", "mgridref_y", "md"), eps=None, sigma=None, ngrid=None, eta=0.6):
     dim, eps0, sigma0, mean_scale = TARGETS[name]
     flat, un, fixed = hr.make_params(dim, K, L, eps0 if eps is None else eps, seed=K + 10 * L, trainable=trainable,
-                                     device="cuda", mean_scale=mean_scale, sigma=sigma0 if sigma is None else sigma)
+                                     device=DEVICE, mean_scale=mean_scale, sigma=sigma0 if sigma is None else sigma,
+                                     ngrid=ngrid, eta=eta)
     return flat, un, fixed, hr.params_numpy(un, flat)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, K, L, n, with_grad=False):
+def many_gmm_of(n_mixes):
+    """(the library's target, the restatement's log p) of many_gmm with `n_mixes` components."""
+    from oracle import cmcd_oracle_torch as ot
+    tgt = model_handler.load_model("many_gmm", types.SimpleNamespace(n_mixes=n_mixes))[0]
+    assert tgt.n_mixes == n_mixes and tgt.consts_on("cpu").numel() == 1 + 2 * n_mixes
+    return tgt, functools.partial(ot.logp_many_gmm, n_mixes=n_mixes)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, K, L, n, with_grad=False, n_mixes=None, **kw):
     """The restatement on seeds 1 .. n, computed once per case and shared (read-only)."""
-    _, _, fixed, p_np = built(name, K, L)
+    _, _, fixed, p_np = built(name, K, L, **kw)
     seeds = np.arange(1, n + 1, dtype=np.int32)
+    logp = name if n_mixes is None else many_gmm_of(n_mixes)[1]
     if with_grad:
-        return hr.bound_and_grad(seeds, p_np, fixed[0], K, L, name)
-    return hr.forward(seeds, p_np, fixed[0], K, L, name) + (None,)
+        return hr.bound_and_grad(seeds, p_np, fixed[0], K, L, logp)
+    return hr.forward(seeds, p_np, fixed[0], K, L, logp) + (None,)
 
 
 def dev(seeds):
@@ -63,6 +85,8 @@ FORWARD = [("gmm", n, K, L) for n in (1, 16, 37) for K in (1, 8) for L in (1, 3)
     ("funnel", 37, 8, 2),
     ("gmm", 37, 64, 1),          # the long-chain branch of compare_losses
     ("gmm", 1040, 8, 1),         # 65 tiles: the finalize launch merges more than one round of records
+    ("many_gmm", 37, 8, 1), ("many_gmm", 37, 8, 3), ("many_gmm", 145, 4, 2),
+    ("funnel", 5, 2, 1), ("funnel", 133, 2, 2),
 ]
 
 
@@ -103,6 +127,22 @@ def test_forward_many_gmm_with_a_floored_end_point(hip_lib):
     print(rep, check_stats(stats, losses, tag="many_gmm floor"))
 
 
+@pytest.mark.parametrize("n_mixes", [7, 17, 64])
+def test_forward_many_gmm_with_other_mixture_sizes(hip_lib, n_mixes):
+    """config.n_mixes != 40 takes the generic component loops of pass1 / pass2 behind hais_stage_target (64: the library's
+    maximum), as tests/test_gpu_parity.py::test_many_gmm_with_other_mixture_sizes does for the older modes."""
+    n, K, L = 37, 4, 2
+    l_ref, z_ref, _ = reference("many_gmm", K, L, n, n_mixes=n_mixes)
+    assert np.isfinite(l_ref).all()
+    flat, un, fixed, _ = built("many_gmm", K, L)
+    losses, z, stats = hais.bound_forward(dev(np.arange(1, n + 1)), flat, un, fixed, many_gmm_of(n_mixes)[0])
+    torch.cuda.synchronize()
+    rep = compare_losses(losses.cpu().numpy(), l_ref, z.cpu().numpy(), z_ref, tag=f"many_gmm n_mixes={n_mixes}", K=K)
+    print(rep, check_stats(stats, losses, tag=f"n_mixes={n_mixes}"))
+    l40, _, _ = run_forward("many_gmm", K, L, np.arange(1, n + 1))
+    assert not torch.equal(l40, losses)                            # it is another target
+
+
 # ------------------------------------------------------------------------------------------ gradient parity
 def compare_grad(tag, un, g, ref_by_leaf, tol=2e-3):
     """The rule of tests/test_gpu_grad.py:_compare: per leaf max abs error / max |ref| <= 2e-3, exact zeros where the
@@ -128,7 +168,15 @@ def compare_grad(tag, un, g, ref_by_leaf, tol=2e-3):
     return g_ref
 
 
-GRAD = [("gmm", 37, 8, 1), ("gmm", 37, 8, 3), ("funnel", 37, 8, 2), ("many_gmm", 37, 8, 1)]
+GRAD = [("gmm", 37, 8, 1), ("gmm", 37, 8, 3), ("funnel", 37, 8, 2), ("many_gmm", 37, 8, 1),
+        ("gmm", 1, 1, 1),            # one particle, one bridge
+        ("gmm", 17, 1, 3),           # one bridge with inner leap-frog steps; the second tile holds one particle
+        ("gmm", 16, 8, 1),           # a full tile
+        ("funnel", 5, 2, 1), ("funnel", 21, 3, 3),
+        # 10 tiles: three workgroups of the sweep, the last with two idle waves; the reduction's eight-wide loop runs once
+        # and its remainder loop twice; the last tile holds one particle
+        ("gmm", 145, 4, 2), ("many_gmm", 145, 4, 1),
+        ("funnel", 133, 2, 2)]       # 9 tiles, the last with five particles
 
 
 @pytest.mark.parametrize("name,n,K,L", GRAD)
@@ -142,6 +190,122 @@ def test_gradient_matches_autograd(hip_lib, name, n, K, L):
     for path in hr.LEAVES:
         assert np.abs(g_ref[path]).max() > 0, f"{path}: the reference gradient of a trainable leaf is zero"
     compare_grad(f"{name} n={n} K={K} L={L}", un, grad, g_ref)
+
+
+def _gradient_case(tag, name, n, K, L, **kw):
+    l_ref, z_ref, g_ref = reference(name, K, L, n, with_grad=True, **kw)
+    assert np.isfinite(l_ref).all(), "no particle at the floor: the gradient check needs finite losses"
+    flat, un, fixed, _ = built(name, K, L, **kw)
+    grad, (losses, z) = hais.grad_and_loss(dev(np.arange(1, n + 1)), flat, un, fixed, target_of(name))
+    torch.cuda.synchronize()
+    compare_losses(losses.cpu().numpy(), l_ref, z.cpu().numpy(), z_ref, tag=tag, K=K)
+    compare_grad(tag, un, grad, g_ref)
+    return g_ref
+
+
+# (K, ngrid): the bridges' abscissae i / (K + 1) against the grid's nodes j / (ngrid + 1); tests/test_hais_oracle.py asserts
+# what each pair is here for
+OFF_GRID = [(40, None),     # ngrid = 32, the reference's for K > 32: fractions inside (0, 1), cells with one and with two bridges
+            (8, 3),         # two bridges in every cell
+            (5, 32)]        # 28 of the 33 cells empty
+
+
+@pytest.mark.parametrize("K,ngrid", OFF_GRID)
+def test_gradient_with_bridges_off_the_grid_nodes(hip_lib, K, ngrid):
+    """d beta -> d mgridref_y through a real interpolation (hais_reduce_kernel's gather with frac inside (0, 1))."""
+    g_ref = _gradient_case(f"gmm n=37 K={K} ngrid={ngrid}", "gmm", 37, K, 1, ngrid=ngrid)
+    m = g_ref[("mgridref_y",)]
+    assert m.shape == ((32 if ngrid is None else ngrid) + 1,) and np.abs(m).max() > 0
+
+
+@pytest.mark.parametrize("eta", [0.0, 0.99])
+def test_gradient_at_the_edges_of_eta(hip_lib, eta):
+    """eta = 0 (the refresh forgets the momentum; ce = 1) and eta = 0.99, its projection bound, where the sweep's
+    ic2 = 1 / (1 - eta^2) is about 50.  float32 alone costs 5.5e-7 / 4.4e-7 of a leaf here (hais_restatement.float32_gap,
+    asserted below 2e-4 in tests/test_hais_oracle.py)."""
+    _gradient_case(f"gmm n=37 K=4 L=2 eta={eta}", "gmm", 37, 4, 2, eta=eta)
+
+
+def test_gradient_many_gmm_with_17_components(hip_lib):
+    """The generic component loop of eval_hess (n_mixes != 40) through the sweep."""
+    n, K, L = 37, 4, 2
+    l_ref, z_ref, g_ref = reference("many_gmm", K, L, n, with_grad=True, n_mixes=17)
+    assert np.isfinite(l_ref).all()
+    flat, un, fixed, _ = built("many_gmm", K, L)
+    grad, (losses, z) = hais.grad_and_loss(dev(np.arange(1, n + 1)), flat, un, fixed, many_gmm_of(17)[0])
+    torch.cuda.synchronize()
+    compare_losses(losses.cpu().numpy(), l_ref, z.cpu().numpy(), z_ref, tag="many_gmm n_mixes=17", K=K)
+    for path in hr.LEAVES:
+        assert np.abs(g_ref[path]).max() > 0, path
+    compare_grad("many_gmm n_mixes=17", un, grad, g_ref)
+
+
+@functools.lru_cache(maxsize=None)
+def floor_sweep_reference():
+    seeds, cat = gc.hais_floor_batch()
+    flat, un, fixed = gc.hais_floor_params()
+    c = gc.HAIS_FLOOR
+    return (seeds, cat) + hr.bound_and_grad(seeds, hr.params_numpy(un, flat), c["dim"], c["K"], c["L"], c["target"])
+
+
+def test_gradient_with_the_floor_acting_in_the_sweep(hip_lib):
+    """gated_cases.HAIS_FLOOR: 33 particles of which 16 are floored at early evaluations and inside at z_K, 4 end floored
+    (loss +inf, gradient finite), 5 are floored throughout and 8 never; tests/test_hais_oracle.py asserts that on the float64
+    restatement, and that opening the gate moves every leaf but eta by 50 % or more (eta: 9 %) against a bar of 0.2 %.  The
+    sweep recomputes the gate in Target::eval_hess and undoes kicks with its score; the forward kernel took it from
+    Target::eval.  float32 alone costs at most 2.0e-7 of a leaf on this batch (mgridref_y; hais_restatement.float32_gap).
+    Run a second time in reverse order, so that floored and unfloored particles sit in other tiles and lanes."""
+    seeds, cat, l_ref, z_ref, g_ref = floor_sweep_reference()
+    flat, un, fixed = gc.hais_floor_params("cuda")
+    tgt = target_of("many_gmm")
+    inf = np.isinf(l_ref)
+    assert len(seeds) == 33 and int(inf.sum()) == 9 and np.array_equal(inf, (cat == 1) | (cat == 2))
+    grad, (losses, z) = hais.grad_and_loss(dev(seeds), flat, un, fixed, tgt)
+    torch.cuda.synchronize()
+    assert np.array_equal(np.isposinf(losses.cpu().numpy()), inf)
+    print(compare_losses(losses.cpu().numpy(), l_ref, z.cpu().numpy(), z_ref, tag="UHA floor", K=4))
+    assert bool(torch.isfinite(grad).all())
+    compare_grad("UHA floor", un, grad, g_ref)
+    perm = np.arange(len(seeds))[::-1].copy()
+    tile = np.arange(len(seeds)) // 16
+    assert (tile[perm] != tile).sum() >= 30                       # all but the middle of the batch change tile
+    grad_p, (losses_p, z_p) = hais.grad_and_loss(dev(seeds[perm]), flat, un, fixed, tgt)
+    torch.cuda.synchronize()
+    where = torch.from_numpy(perm).cuda()
+    assert torch.equal(losses_p, losses[where]) and torch.equal(z_p, z[where])
+    assert bool(torch.isfinite(grad_p).all())
+    compare_grad("UHA floor, reversed", un, grad_p, g_ref)
+
+
+def test_gradient_of_two_shards_with_n_total(hip_lib):
+    """omega = 1 / n_total: the gradients of seeds 1 .. 80 and 81 .. 145, both with n_total = 145, add up to the gradient of
+    the whole batch (compared with the float64 one); every shard's losses and end points are the whole call's bits."""
+    name, n, K, L = "gmm", 145, 4, 2
+    _, _, g_ref = reference(name, K, L, n, with_grad=True)
+    flat, un, fixed, _ = built(name, K, L)
+    tgt = target_of(name)
+    g_all, (l_all, z_all) = hais.grad_and_loss(dev(np.arange(1, n + 1)), flat, un, fixed, tgt)
+    g_a, (l_a, z_a) = hais.grad_and_loss(dev(np.arange(1, 81)), flat, un, fixed, tgt, n_total=n)
+    g_b, (l_b, z_b) = hais.grad_and_loss(dev(np.arange(81, n + 1)), flat, un, fixed, tgt, n_total=n)
+    torch.cuda.synchronize()
+    assert torch.equal(l_a, l_all[:80]) and torch.equal(l_b, l_all[80:])
+    assert torch.equal(z_a, z_all[:80]) and torch.equal(z_b, z_all[80:])
+    compare_grad("gmm shards 80 + 65 of 145", un, g_a.double() + g_b.double(), g_ref)
+    assert float((g_a - g_all).abs().max()) > 0                    # a shard alone is not the whole
+
+
+@pytest.mark.parametrize("name,n,K,L", [("gmm", 37, 8, 3), ("many_gmm", 145, 4, 1), ("funnel", 21, 3, 3)])
+def test_doubling_n_total_halves_the_gradient_bit_for_bit(hip_lib, name, n, K, L):
+    """Every adjoint of the sweep is homogeneous of degree one in omega and a factor of two is exact in binary floating
+    point, in the reduction and through the interpolation too."""
+    flat, un, fixed, _ = built(name, K, L)
+    seeds = dev(np.arange(1, n + 1))
+    g1, (l1, z1) = hais.grad_and_loss(seeds, flat, un, fixed, target_of(name))
+    g2, (l2, z2) = hais.grad_and_loss(seeds, flat, un, fixed, target_of(name), n_total=2 * n)
+    torch.cuda.synchronize()
+    assert float(g1.abs().max()) > 0
+    assert torch.equal(g2, 0.5 * g1)
+    assert torch.equal(l2, l1) and torch.equal(z2, z1)
 
 
 def test_only_the_trainable_leaf_carries_a_gradient(hip_lib):
@@ -215,6 +379,14 @@ def test_same_bits_forward_gradient_repeat_capture_and_batch_composition(hip_lib
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(g_c, g1) and torch.equal(l_c, l1) and torch.equal(z_c, z1)
+    # 145 particles: three workgroups in the sweep, ten slots in the reduction
+    flat4, un4, fixed4, _ = built(name, 4, 2)
+    many = dev(np.arange(1, 146))
+    g3, (l3, z3) = hais.grad_and_loss(many, flat4, un4, fixed4, tgt)
+    g4, (l4, z4) = hais.grad_and_loss(many, flat4, un4, fixed4, tgt)
+    torch.cuda.synchronize()
+    assert float(g3.abs().max()) > 0
+    assert torch.equal(g3, g4) and torch.equal(l3, l4) and torch.equal(z3, z4)
 
 
 def test_error_paths(hip_lib):

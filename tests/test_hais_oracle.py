@@ -1,12 +1,16 @@
 """Pins tests/hais_restatement.py (the float64 yardstick of cmcd_hais_bound_grad and cmcd_amd.hais) without a device: the
 leap-frog is reversible, one step equals its longhand form, eps = 0 is the mean-field bound, the estimate of Z is unbiased on
-a normalised target, and autograd agrees with central differences on every leaf."""
+a normalised target, and autograd agrees with central differences on every leaf, on and off the grid's nodes.  It also asserts,
+on the float64 restatement, that the cases of tests/test_gpu_hais.py are what they are there for: bridges off the grid's
+nodes, the four kinds of particle of the floor case (gated_cases.HAIS_FLOOR), and what float32 arithmetic alone costs on the
+cases that amplify rounding."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import gated_cases as gc
 import hais_restatement as hr
 from oracle import cmcd_oracle_torch as ot
 from oracle import prng
@@ -100,8 +104,21 @@ def test_estimate_of_z_is_unbiased_on_the_normalised_gmm():
 
 def test_autograd_agrees_with_central_differences_on_every_leaf():
     """float64, step 1e-6, the sum over 8 seeds on gmm with K = 4, L = 2: within 1e-5 of the leaf's largest entry."""
-    dim, K, L = 2, 4, 2
-    p_np, _ = _params(dim, K, L, 0.08, seed=1, sigma=2.0)
+    _central_differences(4, 2, None)
+
+
+def test_autograd_agrees_with_central_differences_off_the_grid_nodes():
+    """The same with K = 5 bridges on a grid of ngrid = 3 (four cells): every bridge interpolates (fractions 2/3, 1/3, 0, 2/3,
+    1/3 ... asserted), so autograd's mgridref_y gradient is itself pinned where the GPU cases of OFF_GRID use it."""
+    frac, _ = hr.fractions(5, 3)
+    assert ((frac > 0.05) & (frac < 0.95)).sum() >= 3
+    _central_differences(5, 2, 3)
+
+
+def _central_differences(K, L, ngrid):
+    dim = 2
+    p_np, _ = _params(dim, K, L, 0.08, seed=1, sigma=2.0, ngrid=ngrid)
+    assert p_np["mgridref_y"].shape == ((min(K, 32) if ngrid is None else ngrid) + 1,)
     seeds = np.arange(1, 9, dtype=np.int32)
     p = hr.to_torch(p_np)
     l, _ = hr.losses(seeds, p, dim, K, L, "gmm")
@@ -129,3 +146,128 @@ def test_autograd_agrees_with_central_differences_on_every_leaf():
                 vals.append(total(q))
             fd[k] = (vals[0] - vals[1]) / (2 * h)
         assert np.abs(fd - g).max() <= 1e-5 * np.abs(g).max(), (path, fd, g)
+
+
+# ------------------------------------------------------------------------------------------ the cases of tests/test_gpu_hais.py
+@pytest.mark.parametrize("K,ngrid,what", [(40, None, "one-and-two"), (8, 3, "several"), (5, 32, "mostly-empty"), (5, 3, "several")])
+def test_off_grid_cases_interpolate(K, ngrid, what):
+    """make_params(ngrid=) gives mgridref_y ngrid + 1 entries whatever K; the bridges then sit off the nodes: at least one
+    fraction inside (0.05, 0.95), and the cells are filled as the case's comment says.  The fractions are those of np.interp
+    on the float32 grids the library reads, and ot.betas_from_grid's betas are np.interp's."""
+    flat, un, fixed = hr.make_params(2, K, 1, 0.05, seed=K + 10, ngrid=ngrid)
+    p = hr.params_numpy(un, flat)
+    G = 32 if ngrid is None else ngrid
+    assert p["mgridref_y"].shape == (G + 1,) and p["gridref_x"].shape == (G + 2,) and p["target_x"].shape == (K,)
+    assert len(set(np.round(p["mgridref_y"], 6))) == G + 1         # non-uniform
+    frac, cell = hr.fractions(K, G)
+    inside = (frac > 0.05) & (frac < 0.95)
+    assert inside.any(), frac
+    # the library's own grids (float32) give the same cells and, within float32, the same fractions
+    gx, tx = p["gridref_x"], p["target_x"]
+    j = np.clip(np.searchsorted(gx, tx, side="right"), 1, G + 1)
+    lib_frac = (tx - gx[j - 1]) / (gx[j] - gx[j - 1])
+    ok = np.abs(lib_frac - frac) < 1e-5
+    wrapped = np.abs(lib_frac - frac - np.where(j > cell, -1.0, 1.0)) < 1e-5   # a bridge on a node may fall in either cell
+    assert (ok | ((j != cell) & wrapped)).all(), (lib_frac, frac)
+    assert (j == cell)[inside].all()
+    gy = np.concatenate([[0.0], np.cumsum(p["mgridref_y"]) / p["mgridref_y"].sum()])
+    betas = ot.betas_from_grid(torch.tensor(p["mgridref_y"]), K).numpy()
+    assert np.abs(betas - np.interp(tx, gx, gy)).max() <= 1e-6
+    per_cell = np.bincount(cell, minlength=G + 2)[1:]
+    if what == "one-and-two":
+        assert (per_cell == 1).any() and (per_cell == 2).any() and inside.sum() >= 3 * K // 4
+    elif what == "several":
+        assert (per_cell >= 2).sum() >= 1 and inside.sum() >= 3
+    else:
+        assert (per_cell == 0).sum() >= 28 and inside.sum() >= 3
+
+
+def test_trace_records_every_evaluation():
+    """K L + 1 entries, the first at z_0 and the last at z_K, log p unfloored; the float32 switch returns float32 and agrees."""
+    K, L = 3, 2
+    flat, un, fixed = hr.make_params(2, K, L, 0.1, seed=2, sigma=15.0, mean_scale=5.0)
+    p_np = hr.params_numpy(un, flat)
+    seeds = np.arange(1, 10, dtype=np.int32)
+    trace = {}
+    l, z = hr.forward(seeds, p_np, 2, K, L, "many_gmm", trace=trace)
+    assert len(trace["lp"]) == K * L + 1 == len(trace["z"])
+    assert np.array_equal(trace["z"][-1], z)
+    e0, _, _ = prng.particle_noise_uha(seeds, 2, K)
+    z0 = hr.z0_of(hr.to_torch(p_np, requires_grad=False), torch.tensor(e0.astype(np.float64))).numpy()
+    assert np.array_equal(trace["z"][0], z0)
+    for lp, zz in zip(trace["lp"], trace["z"]):
+        assert np.array_equal(lp, ot.logp_many_gmm_unfloored(torch.tensor(zz)).numpy())
+    l2, z2 = hr.forward(seeds, p_np, 2, K, L, "many_gmm")
+    assert np.array_equal(l, l2) and np.array_equal(z, z2)          # tracing changes nothing
+    l32, z32 = hr.forward(seeds, p_np, 2, K, L, "many_gmm", dtype=torch.float32)
+    assert l32.dtype == np.float32 and z32.dtype == np.float32
+    assert np.abs(l32 - l).max() <= 1e-3 * np.abs(l).max() and 0 < np.abs(z32 - z).max() <= 1e-3
+
+
+def _floor_case():
+    seeds, cat = gc.hais_floor_batch()
+    flat, un, fixed = gc.hais_floor_params()
+    c = gc.HAIS_FLOOR
+    return seeds, cat, hr.params_numpy(un, flat), (c["dim"], c["K"], c["L"])
+
+
+def test_floor_case_pool_and_batch():
+    """gated_cases.HAIS_FLOOR on the seeds 1 .. 2048: the guard band drops 8 (at most 2 %), the band-clear seeds fall into
+    118 / 6 / 1361 / 555 of the four categories, the ridge guard drops 339 more, and the batch is 16 / 4 / 5 / 8."""
+    seeds, near, ridge, cat = gc.hais_floor_pool()
+    print("band", int(near.sum()), "ridge", int((ridge & ~near).sum()),
+          {name: (int(((cat == k) & ~near).sum()), int(((cat == k) & ~near & ~ridge).sum())) for k, name in enumerate(gc.HAIS_FLOOR_CATEGORIES)})
+    assert near.mean() <= 0.02
+    assert int(near.sum()) == 8 and [int(((cat == k) & ~near).sum()) for k in range(4)] == [118, 6, 1361, 555]
+    assert not ridge[cat == 2].any()                               # no unfloored evaluation, no ridge
+    b_seeds, b_cat = gc.hais_floor_batch()
+    assert len(b_seeds) == 33 and (np.diff(b_seeds) > 0).all()
+    counts = [int((b_cat == k).sum()) for k in range(4)]
+    assert counts == list(gc.HAIS_FLOOR["take"])
+    assert counts[0] >= 8 and counts[1] >= 2 and counts[2] >= 2 and counts[3] >= 4
+    # the categories again, from the batch's own chain
+    _, _, p_np, (dim, K, L) = _floor_case()
+    trace = {}
+    l, _ = hr.forward(b_seeds, p_np, dim, K, L, "many_gmm", trace=trace)
+    lp = np.stack(trace["lp"])
+    fl = lp <= gc.FLOOR
+    assert (np.abs(lp - gc.FLOOR) > gc.DELTA * -gc.FLOOR).all()
+    assert np.array_equal(fl[:-1].any(0) & ~fl[-1], b_cat == 0)
+    assert np.array_equal(fl[-1] & ~fl.all(0), b_cat == 1)
+    assert np.array_equal(fl.all(0), b_cat == 2)
+    assert np.array_equal(~fl.any(0), b_cat == 3)
+    assert np.array_equal(np.isposinf(l), fl[-1]) and int(fl[-1].sum()) == 9
+    assert (gc.component_gap(np.stack(trace["z"]))[~fl] >= gc.RIDGE_NATS).all()
+
+
+def test_floor_case_gradient_is_finite_and_the_gate_moves_it():
+    """Nine losses are +inf and every leaf's gradient is finite and non-zero; on the finite-loss particles the unfloored
+    target's gradient differs on some leaf by more than SEPARATION = 10 x 2e-3 of the leaf's scale (measured: every leaf but
+    eta by 50 % or more, eta by 9 %)."""
+    seeds, cat, p_np, (dim, K, L) = _floor_case()
+    l, _, g = hr.bound_and_grad(seeds, p_np, dim, K, L, "many_gmm")
+    assert int(np.isposinf(l).sum()) == 9 and not np.isnan(l).any()
+    for path in hr.LEAVES:
+        assert np.isfinite(g[path]).all() and np.abs(g[path]).max() > 0, path
+    fin = np.isfinite(l)
+    g_true = hr.bound_and_grad(seeds[fin], p_np, dim, K, L, "many_gmm")[2]
+    g_open = hr.bound_and_grad(seeds[fin], p_np, dim, K, L, ot.logp_many_gmm_unfloored)[2]
+    sep = {path: float(np.abs(g_open[path] - g_true[path]).max() / np.abs(g_true[path]).max()) for path in hr.LEAVES}
+    print(sep)
+    assert max(sep.values()) > gc.SEPARATION
+    assert sum(v > gc.SEPARATION for v in sep.values()) == len(hr.LEAVES)
+
+
+def test_float32_alone_stays_a_tenth_of_the_bar_on_the_amplifying_cases():
+    """The restatement in float32 against float64, leaf by leaf, on the floor case and on eta = 0.99 (gmm, n = 37, K = 4,
+    L = 2 as tests/test_gpu_hais.py builds it): at or below 2e-4, a tenth of the GPU comparison's bar.  Measured: floor case
+    2.0e-7 (mgridref_y), eta = 0.99 4.4e-7 (eps), eta = 0 5.5e-7 (eta)."""
+    seeds, cat, p_np, (dim, K, L) = _floor_case()
+    gap = hr.float32_gap(seeds, p_np, dim, K, L, "many_gmm")
+    print("floor", gap)
+    assert max(gap.values()) <= gc.BAR / 10
+    for eta in (0.0, 0.99):
+        flat, un, fixed = hr.make_params(2, 4, 2, 0.05, eta=eta, seed=4 + 10 * 2, mean_scale=1.0, sigma=2.0)
+        gap = hr.float32_gap(np.arange(1, 38, dtype=np.int32), hr.params_numpy(un, flat), 2, 4, 2, "gmm")
+        print("eta", eta, gap)
+        assert max(gap.values()) <= gc.BAR / 10
