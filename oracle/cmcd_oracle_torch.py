@@ -170,10 +170,10 @@ def eps_table(eps0, K, schedule):
     return eps0 * torch.ones(K, dtype=eps0.dtype)
 
 
-def to_torch(params, requires_grad=True):
+def to_torch(params, requires_grad=True, dtype=torch.float64):
     if isinstance(params, dict):
-        return {k: to_torch(v, requires_grad) for k, v in params.items()}
-    t = torch.tensor(np.asarray(params, np.float64), dtype=torch.float64)
+        return {k: to_torch(v, requires_grad, dtype) for k, v in params.items()}
+    t = torch.tensor(np.asarray(params, np.float64), dtype=dtype)
     return t.requires_grad_(requires_grad)
 
 
@@ -195,7 +195,8 @@ def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, 
     z_{i+1}), under "lp" (log p before the many_gmm floor), "gp" / "gq" (grad log p / grad log q before any clipping) and
     "out" (the dds output before its clamp; one per network call).
     straight_through: names from GATES; the forward values stay what they are, the derivative is taken as if the named
-    gate were open — the gradient a kernel without that gate would return.  Test infrastructure only."""
+    gate were open — the gradient a kernel without that gate would return.  Test infrastructure only.
+    The arithmetic runs in the dtype of the leaves of `p` (to_torch: float64 unless asked otherwise)."""
     st = _gates(straight_through)
     if mode == "MCD_CAIS_UHA_sn":
         return losses_uha(seeds, p, dim, nbridges, arch, target_name, trace=trace, straight_through=st)
@@ -207,8 +208,9 @@ def losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule=None, 
         grad_clipping, eps_schedule = False, None
     logp_fn = TARGETS[target_name] if isinstance(target_name, str) else target_name   # or a log-density callable
     e0, noise = prng.particle_noise(np.asarray(seeds), dim, nbridges)
-    e0 = torch.tensor(e0.astype(np.float64))
-    noise = torch.tensor(noise.astype(np.float64))
+    dt = p["vd"]["mean"].dtype
+    e0 = torch.tensor(e0.astype(np.float64), dtype=dt)
+    noise = torch.tensor(noise.astype(np.float64), dtype=dt)
     vd, sn = p["vd"], p.get("sn")
     std = torch.exp(vd["logdiag"])
     betas = betas_from_grid(p["mgridref_y"], nbridges)
@@ -268,9 +270,10 @@ def losses_uha(seeds, p, dim, nbridges, arch, target_name, trace=None, straight_
     st = _gates(straight_through)
     logp_fn = TARGETS[target_name] if isinstance(target_name, str) else target_name
     e0, rho0, noise = prng.particle_noise_uha(np.asarray(seeds), dim, nbridges)
-    e0 = torch.tensor(e0.astype(np.float64))
-    rho = torch.tensor(rho0.astype(np.float64))
-    noise = torch.tensor(noise.astype(np.float64))
+    dt = p["vd"]["mean"].dtype
+    e0 = torch.tensor(e0.astype(np.float64), dtype=dt)
+    rho = torch.tensor(rho0.astype(np.float64), dtype=dt)
+    noise = torch.tensor(noise.astype(np.float64), dtype=dt)
     vd, sn = p["vd"], p["sn"]
     std = torch.exp(vd["logdiag"])
     betas = betas_from_grid(p["mgridref_y"], nbridges)
@@ -295,7 +298,7 @@ def losses_uha(seeds, p, dim, nbridges, arch, target_name, trace=None, straight_
         gp = _gate(gp, -1e2, 1e2, "clip" in st)
         return -1.0 * (beta * gp + (1.0 - beta) * gq)
 
-    one = torch.ones((), dtype=torch.float64)
+    one = torch.ones((), dtype=dt)
     z = std * e0 + vd["mean"]
     w = -log_q(z)
     w = w - log_kernel(rho, torch.zeros_like(rho), one)
@@ -319,11 +322,12 @@ def losses_uha(seeds, p, dim, nbridges, arch, target_name, trace=None, straight_
 
 
 def bound_and_grad(seeds, params_np, dim, nbridges, mode, arch, target_name, eps_schedule=None, grad_clipping=False,
-                   trace=None, straight_through=None):
+                   trace=None, straight_through=None, dtype=torch.float64):
     """value = var(losses, ddof=0) for MCD_CAIS_var_sn, mean(losses) otherwise; grads = d value / d leaf
     as a dict with the layout of `params_np` (what jax.grad(compute_bound_fn, 1) returns, leaf by leaf).
-    `trace` / `straight_through`: see `losses`."""
-    p = to_torch(params_np)
+    `trace` / `straight_through`: see `losses`.  `dtype = torch.float32` runs the same arithmetic in single precision: only to
+    measure what float32 alone costs on a case (the results still come back as float64 NumPy)."""
+    p = to_torch(params_np, dtype=dtype)
     l, z = losses(seeds, p, dim, nbridges, mode, arch, target_name, eps_schedule, grad_clipping, trace, straight_through)
     value = l.var(unbiased=False) if mode == "MCD_CAIS_var_sn" else l.mean()
     leaves = []
@@ -341,5 +345,5 @@ def bound_and_grad(seeds, params_np, dim, nbridges, mode, arch, target_name, eps
         d = grads
         for k in path[:-1]:
             d = d.setdefault(k, {})
-        d[path[-1]] = np.zeros(tuple(v.shape)) if g is None else g.detach().numpy()
-    return float(value.detach()), l.detach().numpy(), z.detach().numpy(), grads
+        d[path[-1]] = np.zeros(tuple(v.shape)) if g is None else g.detach().double().numpy()
+    return float(value.detach()), l.detach().double().numpy(), z.detach().double().numpy(), grads

@@ -28,7 +28,7 @@ def run_oracle(built, seeds, dtype=np.float64, reuse=True, lgcp_counts=None):
         eps_schedule=cfg["eps_schedule"], grad_clipping=cfg["grad_clipping"], dtype=dtype, reuse=reuse)
 
 
-def compare_losses(l_hip, l_ref, z_hip, z_ref, tag="", *, K, rel_max=None, z_max=None):
+def compare_losses(l_hip, l_ref, z_hip, z_ref, tag="", *, K, rel_max=None, z_max=None, bars=None):
     """Parity bar of SURVEY.md section 8c / BASELINE.md section 2 (float32 path vs float64 oracle) on all three outputs of
     compute_bound, `(mean, (losses, z))` (/root/reference/src/mcdboundingmachine.py:183-205):
       * identical set of +inf particles; no NaN;
@@ -38,7 +38,11 @@ def compare_losses(l_hip, l_ref, z_hip, z_ref, tag="", *, K, rel_max=None, z_max
       * z_K (finite particles): p99 of |z - z_ref| <= 1e-3 max(1, p99 |z_ref|), and for K <= 32 every element within 1e-3
         (scaled the same way).
     `K` = bridges of the chain (0 for the mean-field bound).  `rel_max` / `z_max` override the worst-particle bounds for a
-    case that needs a looser one: every such case is listed in DESIGN.md section 2 with its measured value."""
+    case that needs a looser one: every such case is listed in DESIGN.md section 2 with its measured value.  `bars`: the same
+    for the four other bounds, a dict with keys from "mean", "lnz" (each relative to max(1, |reference|)), "rel_p99" and "z_p99"
+    (relative to z_scale) replacing 1e-3, 1e-3, 5e-3 and 1e-3; under the same rule (tests/trained_cases.py)."""
+    bars = dict(bars or {})
+    assert set(bars) <= {"mean", "lnz", "rel_p99", "z_p99"}, bars
     l_hip = np.asarray(l_hip, np.float64)
     l_ref = np.asarray(l_ref, np.float64)
     z_hip = np.asarray(z_hip, np.float64).reshape(len(l_ref), -1)
@@ -58,11 +62,11 @@ def compare_losses(l_hip, l_ref, z_hip, z_ref, tag="", *, K, rel_max=None, z_max
     report = dict(n=len(l_ref), n_inf=int(inf_r.sum()), K=K, mean_err=mean_err, lnz_err=lnz_err,
                   rel_p50=float(np.median(rel)), rel_p99=float(np.quantile(rel, 0.99)), rel_max=float(rel.max()),
                   z_p99=float(np.quantile(zerr, 0.99)), z_max=float(zerr.max()), z_scale=z_scale, rel_bound=rel_bound)
-    assert mean_err <= 1e-3 * max(1.0, abs(l_ref[f].mean())), f"{tag}: {report}"
-    assert lnz_err <= 1e-3 * max(1.0, abs(orc.ln_z(l_ref))), f"{tag}: {report}"
-    assert report["rel_p99"] <= 5e-3, f"{tag}: {report}"
+    assert mean_err <= bars.get("mean", 1e-3) * max(1.0, abs(l_ref[f].mean())), f"{tag}: {report}"
+    assert lnz_err <= bars.get("lnz", 1e-3) * max(1.0, abs(orc.ln_z(l_ref))), f"{tag}: {report}"
+    assert report["rel_p99"] <= bars.get("rel_p99", 5e-3), f"{tag}: {report}"
     assert report["rel_max"] <= rel_bound, f"{tag}: worst particle: {report}"
-    assert report["z_p99"] <= 1e-3 * z_scale, f"{tag}: z: {report}"
+    assert report["z_p99"] <= bars.get("z_p99", 1e-3) * z_scale, f"{tag}: z: {report}"
     if short or z_max is not None:
         assert report["z_max"] <= (z_max if z_max is not None else 1e-3 * z_scale), f"{tag}: worst z element: {report}"
     return report

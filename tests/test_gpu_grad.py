@@ -89,6 +89,10 @@ def test_vargrad_matches_autograd(hip_lib, param_set, monkeypatch, name, n, over
 
 
 def _compare(name, over, un, g, g_ref, tol=2e-3):
+    """`tol`: the bar of every leaf, or {leaf name ("vd/mean", "sn/nn/0/0", ...): bar} for the leaves that have one of their
+    own (tests/trained_cases.py) — every other leaf keeps 2e-3."""
+    own = tol if isinstance(tol, dict) else {}
+    tol = 2e-3 if isinstance(tol, dict) else tol
     worst = {}
     for path, (off, shape) in un.layout.items():
         numel = max(1, int(np.prod(shape)))
@@ -97,7 +101,7 @@ def _compare(name, over, un, g, g_ref, tol=2e-3):
         worst["/".join(map(str, path))] = (float((a - r).abs().max()) / scale, scale)
         if float(r.abs().max()) == 0.0:
             assert float(a.abs().max()) == 0.0, f"{path}: expected exactly zero gradient"
-    bad = {k: v for k, v in worst.items() if v[0] > tol and v[1] > 1e-9}
+    bad = {k: v for k, v in worst.items() if v[0] > own.get(k.split("/", 1)[1], tol) and v[1] > 1e-9}
     print(name, over, {k: "%.1e" % v[0] for k, v in worst.items()})
     assert not bad, f"gradient mismatch (max abs err / max |ref|, max |ref|): {bad}"
     cos = float((g * g_ref).sum() / (g.norm() * g_ref.norm()))
