@@ -234,14 +234,6 @@ static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_
   return ok;
 }
 
-// many_gmm: target_consts = {scale, means[n_mixes][2]} (any other target: nothing to check here)
-static int check_many_gmm(const cmcd_desc& d, const float* target_consts, int64_t n_target) {
-  if (d.target == CMCD_TARGET_MANY_GMM &&
-      (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64))
-    return fail(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}%s");
-  return CMCD_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // the plan of one call: what runs (effective descriptor) and where it lives in the caller's workspace
 //   forward:     [forward tables + statistics records]
@@ -376,7 +368,7 @@ static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
   const bool uha = d.mode == CMCD_MODE_CAIS_UHA_SN;
 
   if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if ((rc = check_many_gmm(d.target, target_consts, n_target)) != CMCD_OK) return rc;
   if (d.target == CMCD_TARGET_LGCP && (!target_consts || n_target != D * D + D + 3))
     return fail(CMCD_ERR_BAD_ARG, "lgcp needs target_consts = {Kinv[d,d], counts[d], mu0, a, lognorm}%s");
 
@@ -480,7 +472,7 @@ static int chain_call_begin(const cmcd_desc& d, const cmcd_layout* lay, PlanKind
   int rc;
   if ((rc = make_plan(d, n, n_target, kind, false, p)) != CMCD_OK) return rc;
   if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if ((rc = check_many_gmm(d.target, target_consts, n_target)) != CMCD_OK) return rc;
   if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
   float* ws = static_cast<float*>(workspace);
   launch_prep(p.d, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
@@ -553,7 +545,7 @@ static int var_grad_impl(const cmcd_desc* desc, const cmcd_layout* lay, const in
   const cmcd_desc& d = *desc;
   if (d.target == CMCD_TARGET_LGCP && !kept)
     return fail(CMCD_ERR_UNSUPPORTED, "lgcp: call cmcd_bound_var_forward, then cmcd_bound_var_grad_kept on the same workspace%s");
-  if ((rc = check_many_gmm(d, target_consts, n_target)) != CMCD_OK) return rc;
+  if ((rc = check_many_gmm(d.target, target_consts, n_target)) != CMCD_OK) return rc;
   CallPlan p;
   if ((rc = make_plan(d, n, n_target, PLAN_VAR_GRAD, false, p)) != CMCD_OK) return rc;
   if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;

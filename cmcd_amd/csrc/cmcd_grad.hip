@@ -42,9 +42,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "cmcd_common.h"
-#include "cmcd_device.h"
-#include "cmcd_hip.h"
+#include "cmcd_tile.h"
 
 namespace cmcd {
 
@@ -231,21 +229,7 @@ __global__ __launch_bounds__(64 * NW, (WGLOBAL && T <= 4) ? 2 : 1) void grad_ker
       rows01(x0, a0, a1);
       rows01(x1, b0, b1);
       float nz[2 * Hh];
-#pragma unroll
-      for (int j0 = 0; j0 < Hh; j0 += 4) {
-        const int j = j0 + g;
-        uint32_t y0 = j, y1 = (Hh + j < D) ? Hh + j : 0;
-        threefry2x32(a0, a1, y0, y1);
-        uint32_t r0[4], r1[4];
-        rows0123(__float_as_uint(bits_to_normal(y0)), r0);
-        rows0123(__float_as_uint(bits_to_normal(y1)), r1);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (j0 + q < Hh) {
-            nz[j0 + q] = __uint_as_float(r0[q]);
-            nz[Hh + j0 + q] = __uint_as_float(r1[q]);
-          }
-      }
+      tile_normal<D>(a0, a1, g, nz);
 #pragma unroll
       for (int j = 0; j < D; ++j) {
         z[j] = qstd[j] * nz[j] + qmean[j];
@@ -572,35 +556,7 @@ __global__ __launch_bounds__(64 * NW, (WGLOBAL && T <= 4) ? 2 : 1) void grad_ker
         float nz[2 * Hh];
 #pragma unroll
         for (int j = 0; j < 2 * Hh; ++j) nz[j] = 0.f;
-        if (!ITEM) {
-        x0 = gb; x1 = 2 + gb;
-        threefry2x32(k0, k1, x0, x1);
-        uint32_t g0, g1, h0, h1;
-        rows01(x0, g0, g1);
-        rows01(x1, h0, h1);
-        constexpr int NB = 2 + Hh;
-#pragma unroll
-        for (int b0 = 0; b0 < NB; b0 += 4) {
-          const int b = b0 + g;
-          const bool is_split = b < 2;
-          const int jn = b - 2;
-          uint32_t y0 = is_split ? b : jn;
-          uint32_t y1 = is_split ? 2 + b : ((Hh + jn < D) ? Hh + jn : 0);
-          threefry2x32(is_split ? h0 : g0, is_split ? h1 : g1, y0, y1);
-          if (b0 == 0) rows01(y1, k0, k1);
-          uint32_t r0[4], r1[4];
-          rows0123(__float_as_uint(bits_to_normal(y0)), r0);
-          rows0123(__float_as_uint(bits_to_normal(y1)), r1);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int jj = b0 + q - 2;
-            if (jj >= 0 && jj < Hh) {
-              nz[jj] = __uint_as_float(r0[q]);
-              nz[Hh + jj] = __uint_as_float(r1[q]);
-            }
-          }
-        }
-        }
+        if (!ITEM) tile_chain_step<D>(k0, k1, g, nz);
         float sb = 0.f, se = 0.f, dn2 = 0.f;
 #pragma unroll
         for (int j = 0; j < D; ++j) {  // forward kernel of step e
@@ -1756,13 +1712,11 @@ int grad_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, c
   return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
 }
 
-typedef void (*ula_fn)(UlaGradArgs);
-static ula_fn pick_ula(const cmcd_desc& d) {
-  if (d.target == CMCD_TARGET_MANY_GMM && d.dim == 2) return ula_grad_kernel<CMCD_TARGET_MANY_GMM, 2>;
-  if (d.target == CMCD_TARGET_GMM && d.dim == 2) return ula_grad_kernel<CMCD_TARGET_GMM, 2>;
-  if (d.target == CMCD_TARGET_FUNNEL && d.dim == 10) return ula_grad_kernel<CMCD_TARGET_FUNNEL, 10>;
-  return nullptr;
-}
+struct UlaFamily {
+  typedef void (*fn)(UlaGradArgs);
+  template <int TARGET, int D> static fn get() { return ula_grad_kernel<TARGET, D>; }
+};
+static UlaFamily::fn pick_ula(const cmcd_desc& d) { return tile_pick_plain<UlaFamily>(d.target, d.dim); }
 bool ula_grad_available(const cmcd_desc& d) { return pick_ula(d) != nullptr; }
 static int64_t ula_det_floats(int64_t K4, int64_t ntiles) {
   const int64_t f = ntiles * 2 * K4;
@@ -1778,7 +1732,7 @@ int ula_grad_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& 
                     int64_t n_params, const float* ws_fwd, const float* traj, float* gws, float omega, float* grad,
                     void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  ula_fn fn = pick_ula(d);
+  UlaFamily::fn fn = pick_ula(d);
   if (!fn) return CMCD_ERR_UNSUPPORTED;
   const int64_t K4 = ((int64_t)d.nbridges + 3) & ~int64_t(3), ntiles = (n + 15) / 16;
   if (hipMemsetAsync(grad, 0, sizeof(float) * n_params, stream) != hipSuccess) return CMCD_ERR_HIP;

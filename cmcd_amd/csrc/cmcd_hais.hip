@@ -23,6 +23,10 @@
 // Mapping (cmcd_mfvi.hip's and ula_grad_kernel's): one wave per 16-particle tile, four tiles per 256-thread workgroup, lane (g, c)
 // = particle c; the four lanes of a particle share the target evaluation (Target<>::eval) and the Threefry blocks, and repeat
 // the rest.  z, r, rho, w and the key stay in registers for the whole chain.  One 5-double statistics record per tile.
+// The key split, the normal(key, (D,)) draw, the step of the key chain, the statistics record, many_gmm's constant staging and
+// the instance table are cmcd_tile.h's, shared with grad_kernel and the reverse and segment kernels (mfvi_kernel keeps inline
+// copies of its own, see the note above it); what is
+// here is the chain itself, its reverse sweep, the beta table and the reduction.
 //
 // What a gradient call keeps (hais_traj_kernel with `keep`), all [.][n][D] float32 in the workspace:
 //   pos  [K L + 1]  the position of every evaluation (pos[0] = z_0, pos[K L] = z_K)
@@ -37,9 +41,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "cmcd_common.h"
-#include "cmcd_device.h"
-#include "cmcd_hip.h"
+#include "cmcd_tile.h"
 
 namespace cmcd {
 
@@ -62,23 +64,6 @@ struct HaisArgs {
   int32_t K, L, n_mix;
   float omega;
 };
-
-// target constants as Target<>::eval expects them in LDS (mfvi_kernel's staging)
-template <int TARGET>
-__device__ __forceinline__ void hais_stage_target(const HaisArgs& a, float* lds_tgt) {
-  if (TARGET == CMCD_TARGET_MANY_GMM) {   // {scale, means} -> {1/scale, c2, n_mix bits, c0, means} (log2 units)
-    const float s = a.tc[0];
-    for (int idx = threadIdx.x; idx < 4 + 2 * a.n_mix; idx += blockDim.x) {
-      float v;
-      if (idx == 0) v = 1.0f / s;
-      else if (idx == 1) v = -0.5f * 1.44269504088896340736f / (s * s);
-      else if (idx == 2) v = __int_as_float(a.n_mix);
-      else if (idx == 3) v = 1.44269504088896340736f * (-2.0f * (logf(s) + kHalfLog2Pi) - logf((float)a.n_mix));
-      else v = a.tc[1 + (idx - 4)];
-      lds_tgt[idx] = v;
-    }
-  }
-}
 
 // cell of np.interp for abscissa x on the grid gx[0 .. G + 1]: searchsorted(gx, x, side = 'right') clipped to [1, G + 1]
 __device__ __forceinline__ int hais_cell(const float* gx, int G, float x) {
@@ -110,62 +95,6 @@ __device__ __forceinline__ void hais_form_betas(const HaisArgs& a, float* betas,
   __syncthreads();
 }
 
-// normal(key, (D,)): block j encrypts (j, Hh + j); the blocks are dealt to the four rows of the wave
-template <int D>
-__device__ __forceinline__ void hais_normal(uint32_t ka, uint32_t kb, int g, float (&nz)[2 * ((D + 1) / 2)]) {
-  constexpr int Hh = (D + 1) / 2;
-#pragma unroll
-  for (int j0 = 0; j0 < Hh; j0 += 4) {
-    const int j = j0 + g;
-    uint32_t y0 = j, y1 = (Hh + j < D) ? Hh + j : 0;
-    threefry2x32(ka, kb, y0, y1);
-    uint32_t r0[4], r1[4];
-    rows0123(__float_as_uint(bits_to_normal(y0)), r0);
-    rows0123(__float_as_uint(bits_to_normal(y1)), r1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (j0 + q < Hh) {
-        nz[j0 + q] = __uint_as_float(r0[q]);
-        nz[Hh + j0 + q] = __uint_as_float(r1[q]);
-      }
-  }
-}
-
-// one step of the key chain: (G, H) = split(gen); nz = normal(G, (D,)); gen = second(split(H)).  Lane row g computes block
-// (g & 1) of split(gen); the 2 + ceil(D / 2) blocks of split(H) and normal(G) are dealt to the four rows.
-template <int D>
-__device__ __forceinline__ void hais_chain_step(uint32_t& k0, uint32_t& k1, int g, float (&nz)[2 * ((D + 1) / 2)]) {
-  constexpr int Hh = (D + 1) / 2;
-  constexpr int NB = 2 + Hh;
-  const int gb = g & 1;
-  uint32_t x0 = gb, x1 = 2 + gb;
-  threefry2x32(k0, k1, x0, x1);
-  uint32_t g0, g1, h0, h1;
-  rows01(x0, g0, g1);
-  rows01(x1, h0, h1);
-#pragma unroll
-  for (int b0 = 0; b0 < NB; b0 += 4) {
-    const int b = b0 + g;
-    const bool is_split = b < 2;
-    const int jn = b - 2;   // block of normal(G): encrypts (jn, Hh + jn), pad counter 0
-    uint32_t y0 = is_split ? b : jn;
-    uint32_t y1 = is_split ? 2 + b : ((Hh + jn < D) ? Hh + jn : 0);
-    threefry2x32(is_split ? h0 : g0, is_split ? h1 : g1, y0, y1);
-    if (b0 == 0) rows01(y1, k0, k1);
-    uint32_t r0[4], r1[4];
-    rows0123(__float_as_uint(bits_to_normal(y0)), r0);
-    rows0123(__float_as_uint(bits_to_normal(y1)), r1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int jj = b0 + q - 2;
-      if (jj >= 0 && jj < Hh) {
-        nz[jj] = __uint_as_float(r0[q]);
-        nz[Hh + jj] = __uint_as_float(r1[q]);
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // forward chain
 // ------------------------------------------------------------------------------------------
@@ -174,7 +103,7 @@ __global__ __launch_bounds__(256) void hais_traj_kernel(HaisArgs a) {
   __shared__ __attribute__((aligned(16))) float lds_tgt[4 + 2 * 64];
   extern __shared__ __attribute__((aligned(16))) float lds_dyn[];   // betas[K], gy[ngrid + 2]
   float* betas = lds_dyn;
-  hais_stage_target<TARGET>(a, lds_tgt);
+  if (TARGET == CMCD_TARGET_MANY_GMM) tile_stage_many_gmm(a.tc, a.n_mix, lds_tgt);
   hais_form_betas(a, betas, lds_dyn + a.K);
   constexpr int Hh = (D + 1) / 2;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
@@ -188,13 +117,12 @@ __global__ __launch_bounds__(256) void hais_traj_kernel(HaisArgs a) {
 
   // key chain up to the first bridge
   const int gb = g & 1;
-  uint32_t x0 = gb, x1 = 2 + gb;
-  threefry2x32(0u, (uint32_t)seed, x0, x1);
-  uint32_t a0, a1, b0, b1;
+  uint32_t x0, x1, a0, a1, b0, b1;
+  tile_split(0u, (uint32_t)seed, gb, x0, x1);
   rows01(x0, a0, a1);
   rows01(x1, b0, b1);
   float nz[2 * Hh];
-  hais_normal<D>(a0, a1, g, nz);                   // z_0 = mean + std normal(A)
+  tile_normal<D>(a0, a1, g, nz);                   // z_0 = mean + std normal(A)
   float z[D], qmean[D], qiv[D], sm[D], iv[D], r[D], rho[D];
   float w = 0.f;
 #pragma unroll
@@ -209,23 +137,20 @@ __global__ __launch_bounds__(256) void hais_traj_kernel(HaisArgs a) {
     sm[j] = expf(a.params[a.lay.md + j]);
     iv[j] = 1.0f / (sm[j] * sm[j]);
   }
-  x0 = gb; x1 = 2 + gb;
-  threefry2x32(b0, b1, x0, x1);                    // C = first(split(B))
+  tile_split(b0, b1, gb, x0, x1);                  // C = first(split(B))
   uint32_t c0, c1;
   rows01(x0, c0, c1);
-  x0 = gb; x1 = 2 + gb;
-  threefry2x32(c0, c1, x0, x1);                    // (R, G') = split(C)
+  tile_split(c0, c1, gb, x0, x1);                  // (R, G') = split(C)
   uint32_t r0, r1, p0, p1;
   rows01(x0, r0, r1);
   rows01(x1, p0, p1);
-  hais_normal<D>(r0, r1, g, nz);                   // rho_prev = s normal(R)
+  tile_normal<D>(r0, r1, g, nz);                   // rho_prev = s normal(R)
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     r[j] = sm[j] * nz[j];
     rho[j] = r[j];
   }
-  x0 = gb; x1 = 2 + gb;
-  threefry2x32(p0, p1, x0, x1);                    // gen = second(split(G'))
+  tile_split(p0, p1, gb, x0, x1);                  // gen = second(split(G'))
   uint32_t k0, k1;
   rows01(x1, k0, k1);
   if (keep) {
@@ -266,7 +191,7 @@ __global__ __launch_bounds__(256) void hais_traj_kernel(HaisArgs a) {
     if (m == M) break;
     const float be = betas[i];
     if (l == 0) {
-      hais_chain_step<D>(k0, k1, g, nz);
+      tile_chain_step<D>(k0, k1, g, nz);
 #pragma unroll
       for (int j = 0; j < D; ++j) {
         rho[j] = eta * r[j] + ce * sm[j] * nz[j];
@@ -295,25 +220,7 @@ __global__ __launch_bounds__(256) void hais_traj_kernel(HaisArgs a) {
 #pragma unroll
     for (int j = 0; j < D; ++j) a.out_z[pD + j] = z[j];
   }
-  const bool use = valid && g == 0;
-  double cnt = (use && isfinite(loss)) ? 1.0 : 0.0;
-  double sum = use ? (double)loss : 0.0;
-  double sq = use ? (double)loss * (double)loss : 0.0;
-  double mx = use ? -(double)loss : -INFINITY;
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) {
-    cnt += __shfl_xor(cnt, o);
-    sum += __shfl_xor(sum, o);
-    sq += __shfl_xor(sq, o);
-    mx = fmax(mx, __shfl_xor(mx, o));
-  }
-  double ex = (use && mx > -INFINITY && mx < INFINITY) ? exp(-(double)loss - mx) : 0.0;
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) ex += __shfl_xor(ex, o);
-  if (lane == 0) {
-    double* o = a.partials + tile * CMCD_NSTATS;
-    o[0] = cnt; o[1] = sum; o[2] = sq; o[3] = mx; o[4] = ex;
-  }
+  tile_stats_record(loss, valid && g == 0, lane, a.partials + tile * CMCD_NSTATS);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -327,7 +234,7 @@ __global__ __launch_bounds__(256) void hais_grad_kernel(HaisArgs a) {
   __shared__ __attribute__((aligned(16))) float lds_tgt[4 + 2 * 64];
   extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
   float* betas = lds_dyn;
-  hais_stage_target<TARGET>(a, lds_tgt);
+  if (TARGET == CMCD_TARGET_MANY_GMM) tile_stage_many_gmm(a.tc, a.n_mix, lds_tgt);
   hais_form_betas(a, betas, lds_dyn + a.K);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
@@ -539,17 +446,14 @@ __global__ __launch_bounds__(256) void hais_reduce_kernel(HaisReduceArgs a) {
   }
 }
 
-typedef void (*hais_fn)(HaisArgs);
-static hais_fn pick_hais(int target, int dim, bool sweep) {
-  if (target == CMCD_TARGET_GMM && dim == 2) return sweep ? hais_grad_kernel<CMCD_TARGET_GMM, 2> : hais_traj_kernel<CMCD_TARGET_GMM, 2>;
-  if (target == CMCD_TARGET_MANY_GMM && dim == 2)
-    return sweep ? hais_grad_kernel<CMCD_TARGET_MANY_GMM, 2> : hais_traj_kernel<CMCD_TARGET_MANY_GMM, 2>;
-  if (target == CMCD_TARGET_FUNNEL && dim == 10)
-    return sweep ? hais_grad_kernel<CMCD_TARGET_FUNNEL, 10> : hais_traj_kernel<CMCD_TARGET_FUNNEL, 10>;
-  return nullptr;
-}
-
-static inline int64_t al4(int64_t x) { return (x + 3) & ~int64_t(3); }
+struct HaisTraj {
+  typedef void (*fn)(HaisArgs);
+  template <int TARGET, int D> static fn get() { return hais_traj_kernel<TARGET, D>; }
+};
+struct HaisSweep {
+  typedef void (*fn)(HaisArgs);
+  template <int TARGET, int D> static fn get() { return hais_grad_kernel<TARGET, D>; }
+};
 
 struct HaisWs {
   int64_t partials, pos, rho, rend, gpart, total;   // offsets in floats
@@ -586,7 +490,7 @@ int64_t cmcd_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges,
     fail_msg(CMCD_ERR_UNSUPPORTED, "UHA on lgcp is not implemented (no Hamiltonian AIS launch sequence for d = 1600)");
     return 0;
   }
-  if (!pick_hais(target, dim, false)) {
+  if (!tile_pick_plain<HaisTraj>(target, dim)) {
     fail_msg(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS kernel instance for this (target, dim)");
     return 0;
   }
@@ -603,7 +507,7 @@ int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t 
   if (n < 1 || n > (int64_t)1 << 31 || dim < 1) return fail_msg(CMCD_ERR_BAD_ARG, "n or dim out of range");
   if (target == CMCD_TARGET_LGCP)
     return fail_msg(CMCD_ERR_UNSUPPORTED, "UHA on lgcp is not implemented (no Hamiltonian AIS launch sequence for d = 1600)");
-  if (!pick_hais(target, dim, false))
+  if (!tile_pick_plain<HaisTraj>(target, dim))
     return fail_msg(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS kernel instance for this (target, dim)");
   if (!hais_shape_ok(nbridges, lfsteps, n))
     return fail_msg(CMCD_ERR_UNSUPPORTED, "nbridges above 4096 or nbridges * lfsteps above 2^24");
@@ -614,11 +518,7 @@ int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t 
         inside(lay->target_x, nbridges)))
     return fail_msg(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat");
   int n_mix = 0;
-  if (target == CMCD_TARGET_MANY_GMM) {
-    if (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64)
-      return fail_msg(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}");
-    n_mix = int((n_target - 1) / 2);
-  }
+  if (int rc = check_many_gmm(target, target_consts, n_target, &n_mix)) return rc;
   const HaisWs w = hais_ws(dim, nbridges, lfsteps, n, grad != nullptr);
   if (workspace_bytes < w.total * 4 || (reinterpret_cast<uintptr_t>(workspace) & 15))
     return fail_msg(CMCD_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
@@ -633,11 +533,11 @@ int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t 
   ha.lay = *lay; ha.n = n; ha.K = nbridges; ha.L = lfsteps; ha.n_mix = n_mix; ha.omega = omega;
   const unsigned blocks = (unsigned)((tiles + 3) / 4);
   const size_t lds = sizeof(float) * ((size_t)nbridges + (size_t)lay->ngrid + 2);
-  hipLaunchKernelGGL(pick_hais(target, dim, false), dim3(blocks), dim3(256), lds, stream, ha);
+  hipLaunchKernelGGL(tile_pick_plain<HaisTraj>(target, dim), dim3(blocks), dim3(256), lds, stream, ha);
   int rc = launch_finalize(partials, (int32_t)tiles, out_stats, stream_);
   if (rc != CMCD_OK) return rc;
   if (grad) {
-    hipLaunchKernelGGL(pick_hais(target, dim, true), dim3(blocks), dim3(256), lds, stream, ha);
+    hipLaunchKernelGGL(tile_pick_plain<HaisSweep>(target, dim), dim3(blocks), dim3(256), lds, stream, ha);
     HaisReduceArgs ra{params, ha.gpart, grad, *lay, tiles, n_params, nbridges, dim};
     const size_t rlds = sizeof(float) * (3 * (size_t)nbridges + 2 * ((size_t)lay->ngrid + 2));
     hipLaunchKernelGGL(hais_reduce_kernel, dim3(1), dim3(256), rlds, stream, ra);

@@ -1,7 +1,9 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip (both through cmcd_tile.h, which holds what
-// the two share), cmcd_resample.hip and cmcd_sinkhorn.hip.  Not included by the other translation units: their seams are in
-// cmcd_common.h, which the stored counter figures are hashed over (bench.py: kernel_sources_sha).
+// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip, cmcd_resample.hip and cmcd_sinkhorn.hip,
+// plus the two host helpers every entry point shares (al4, check_many_gmm).  cmcd_reverse.hip, cmcd_segment.hip, cmcd_grad.hip,
+// cmcd_mfvi.hip and cmcd_hais.hip include it through cmcd_tile.h, which holds the wave-per-tile pieces they share.  The seams of
+// the translation units that do not include it (the coop, lgcp, uha, bptt and opt files) are in cmcd_common.h, which the stored
+// counter figures are hashed over (bench.py: kernel_sources_sha).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +19,20 @@ int fail(int code, const char* fmt, const char* a = "", long long b = 0);
     hipError_t e_ = (expr);                                                                    \
     if (e_ != hipSuccess) return fail(CMCD_ERR_HIP, "HIP error: %s (code %lld)", hipGetErrorString(e_), (long long)e_); \
   } while (0)
+
+// workspace blocks start on 16 bytes: a float count rounded up to a multiple of four
+inline int64_t al4(int64_t x) { return (x + 3) & ~int64_t(3); }
+
+// many_gmm takes target_consts = {scale, means[n_mixes][2]} with at most 64 mixtures (the block the kernels stage into LDS); any
+// other target: nothing to check here.  n_mix (nullable) receives the number of mixtures, 0 for another target.
+inline int check_many_gmm(int target, const float* target_consts, int64_t n_target, int* n_mix = nullptr) {
+  if (n_mix) *n_mix = 0;
+  if (target != CMCD_TARGET_MANY_GMM) return CMCD_OK;
+  if (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64)
+    return fail(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}%s");
+  if (n_mix) *n_mix = int((n_target - 1) / 2);
+  return CMCD_OK;
+}
 
 // cmcd_kernels.hip.  The launchers that return void leave their launch status to the caller's hipGetLastError.
 // `d` is the effective descriptor of the call (cmcd_api.hip: CallPlan).

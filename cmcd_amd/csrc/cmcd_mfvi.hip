@@ -6,15 +6,15 @@
 // Under the reparameterisation z = mean + std e:  log q(z) = -|e|^2/2 - sum logdiag - const, so
 //   d loss / d mean_j = -grad_j log p(z),     d loss / d logdiag_j = -1 - grad_j log p(z) std_j e_j.
 // One wave per 16-particle tile (same lane layout and key chain as the trajectory kernels: the z this
-// kernel draws for a seed is the z_0 cmcd_bound_forward draws for it); per-tile statistics and gradient
-// rows, merged in a fixed order.  lgcp (d = 1600) goes through the skinny-GEMM path of cmcd_lgcp.hip.
+// kernel draws for a seed is the z_0 cmcd_bound_forward and cmcd_hais_bound_grad draw for it); per-tile
+// statistics and gradient rows, merged in a fixed order.  lgcp (d = 1600) goes through the skinny-GEMM path
+// of cmcd_lgcp.hip.  The instance table, al4 and the many_gmm check are the shared ones (cmcd_tile.h,
+// cmcd_host.h); the kernel's own pieces stay inline, see the note above it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "cmcd_common.h"
-#include "cmcd_device.h"
-#include "cmcd_hip.h"
+#include "cmcd_tile.h"
 
 namespace cmcd {
 
@@ -31,6 +31,11 @@ struct MfviArgs {
   float omega;
 };
 
+// mfvi_kernel keeps its inline copies of cmcd_tile.h's pieces (tile_stage_many_gmm, tile_split, tile_normal, tile_stats_record):
+// on the helpers it kept its registers and its bits, but the mean-field gradient call on many_gmm with 15 000 particles left the
+// previous build's timing spread, 52.6 us -> 53.7 / 55.0 us in two processes against 52.6 / 52.6 and a spread of 0.3 us
+// (profiles/r14_tile_plain_ab.txt, section 5), and the rule for a kernel put on a helper sends such a kernel back (cmcd_tile.h).
+// A change to the draw or the record is made here AND there; tests/test_gpu_hais.py's zero-step-size cases hold the two draws together.
 template <int TARGET, int D>
 __global__ __launch_bounds__(256) void mfvi_kernel(MfviArgs a) {
   __shared__ __attribute__((aligned(16))) float lds_tgt[4 + 2 * 64];
@@ -154,15 +159,10 @@ __global__ void mfvi_reduce_kernel(MfviReduceArgs a) {
   else a.grad[a.o_logdiag + (j - a.D)] = v;
 }
 
-typedef void (*mfvi_fn)(MfviArgs);
-static mfvi_fn pick_mfvi(int target, int dim) {
-  if (target == CMCD_TARGET_GMM && dim == 2) return mfvi_kernel<CMCD_TARGET_GMM, 2>;
-  if (target == CMCD_TARGET_MANY_GMM && dim == 2) return mfvi_kernel<CMCD_TARGET_MANY_GMM, 2>;
-  if (target == CMCD_TARGET_FUNNEL && dim == 10) return mfvi_kernel<CMCD_TARGET_FUNNEL, 10>;
-  return nullptr;
-}
-
-static inline int64_t al4(int64_t x) { return (x + 3) & ~int64_t(3); }
+struct MfviFamily {
+  typedef void (*fn)(MfviArgs);
+  template <int TARGET, int D> static fn get() { return mfvi_kernel<TARGET, D>; }
+};
 
 }  // namespace cmcd
 
@@ -173,7 +173,7 @@ extern "C" {
 int64_t cmcd_mfvi_workspace_bytes(int32_t target, int32_t dim, int64_t n) {
   if (n < 1 || dim < 1) return 0;
   if (target == CMCD_TARGET_LGCP) return lgcp_mfvi_workspace_floats(dim, n, true) * 4;
-  if (!pick_mfvi(target, dim)) {
+  if (!tile_pick_plain<MfviFamily>(target, dim)) {
     fail_msg(CMCD_ERR_UNSUPPORTED, "no mean-field VI kernel instance for this (target, dim)");
     return 0;
   }
@@ -215,13 +215,9 @@ int cmcd_mfvi_bound_grad(int32_t target, int32_t dim, int64_t off_mean, int64_t 
     return hipGetLastError() == hipSuccess ? CMCD_OK : fail_msg(CMCD_ERR_HIP, "launch failed");
   }
 
-  mfvi_fn fn = pick_mfvi(target, dim);
+  MfviFamily::fn fn = tile_pick_plain<MfviFamily>(target, dim);
   int n_mix = 0;
-  if (target == CMCD_TARGET_MANY_GMM) {
-    if (!target_consts || n_target < 3 || (n_target - 1) % 2 != 0 || (n_target - 1) / 2 > 64)
-      return fail_msg(CMCD_ERR_BAD_ARG, "many_gmm needs target_consts = {scale, means[n_mixes<=64][2]}");
-    n_mix = int((n_target - 1) / 2);
-  }
+  if (int rc = check_many_gmm(target, target_consts, n_target, &n_mix)) return rc;
   const int64_t tiles = (n + 15) / 16;
   double* partials = reinterpret_cast<double*>(ws);
   float* gpart = ws + al4(tiles * CMCD_NSTATS * 2);

@@ -1,19 +1,39 @@
-// The wave-per-tile chain machinery that cmcd_reverse.hip and cmcd_segment.hip share (included by nothing else): the score
-// network on 16 particles per wave, a key split and one step of the key chain, the statistics butterflies, the instance table
-// and the launch.  Each kernel file keeps its chain: direction, what opens and what closes a step, how it
-// enters and leaves.
+// The wave-per-tile pieces that more than one kernel file uses: the score network on 16 particles per wave, the key split, the
+// normal(key, (D,)) draw and one step of the key chain, the statistics butterflies and the whole record of a tile, many_gmm's
+// constant staging, the two instance tables and the launch.  Each kernel file keeps its chain: direction, what opens and what
+// closes a step, how it enters and leaves.
 //
-// This is the SECOND copy of that machinery, and a named one: traj_kernel (cmcd_kernels.hip) holds the first, with its debug
-// outputs and ablation probes inside the same code, and cmcd_kernels.hip is hashed for the stored counter figures (bench.py:
-// kernel_sources_sha).  Folding traj_kernel in is a separate decision.  Until then a change to the network evaluation or the key
-// chain is made here AND there; the segment's forward-call test and the reverse parity cases fail when one is forgotten.
+// Who includes it and what it takes:
+//   cmcd_reverse.hip, cmcd_segment.hip  tile_eval_net, tile_split, tile_chain_step, the two butterflies, tile_pick, tile_launch
+//   cmcd_hais.hip    hais_traj_kernel: tile_split, tile_normal, tile_chain_step, tile_stats_record; both kernels:
+//                    tile_stage_many_gmm; tile_pick_plain
+//   cmcd_mfvi.hip    tile_pick_plain (mfvi_kernel itself stays on inline copies, below)
+//   cmcd_grad.hip    grad_kernel's whole-chain local-gradient instances: tile_normal, tile_chain_step; ula_grad_kernel's table:
+//                    tile_pick_plain
 //
-// What is here is what could move WITHOUT changing a kernel's machine code (tools/probes/device_asm_diff.py, CHANGELOG round 12).
-// The LDS staging, q's constants and log q, grad log q with the clips, the z_0 draw, the two ends of a step and the head of the
-// statistics record stayed in the two kernels: as helpers each of them compiled to other code (another register allocation over
-// the whole kernel, other scratch sizes on the funnel geffner instances), for reasons that have nothing to do with what they
-// compute — a helper is simplified on its own before it is inlined, and one that reads blockDim.x no longer folds it to the
-// launch's uniform workgroup size.
+// The copies that remain, and why.  A change to the network evaluation, the draw or the key chain is made here AND there; the
+// segment's forward-call test, the reverse parity cases and tests/test_gpu_hais.py's zero-step-size cases fail when one is
+// forgotten.
+//   traj_kernel (cmcd_kernels.hip) and coop_kernel (cmcd_coop.hip) hold the first copies, with their debug outputs and ablation
+//     probes inside the same code; both files are hashed for the stored counter figures (bench.py: kernel_sources_sha).
+//   uha_traj_kernel and uha_coop_kernel (cmcd_uha.hip): its draw_normal carries the capture hooks, the cooperative kernel has a
+//     split Threefry of its own, and replacing only the two statistics tails by tile_stats_record changed the body of all 40
+//     instances for about 36 lines less.  A separate decision.
+//   reverse_traj_kernel and segment_traj_kernel keep inline the LDS staging, q's constants and log q, grad log q with the clips,
+//     the z_0 draw, the two ends of a step and the head of the statistics record: as helpers each of them compiled to other code
+//     (another register allocation over the whole kernel, other scratch sizes on the funnel geffner instances), for reasons that
+//     have nothing to do with what they compute — a helper is simplified on its own before it is inlined, and one that reads
+//     blockDim.x no longer folds it to the launch's uniform workgroup size.  Their device code is byte-identical to the build
+//     before the header existed (tools/probes/device_asm_diff.py, CHANGELOG round 12) and stays so.
+//   grad_kernel's prologue splits (cmcd_grad.hip) and ula_grad_kernel were not touched.
+//   mfvi_kernel (cmcd_mfvi.hip) keeps its staging, split, draw and statistics record inline: on tile_stage_many_gmm, tile_split,
+//     tile_normal and tile_stats_record it kept its registers (39 / 55 / 58 VGPRs, no scratch, 8 waves per SIMD) and its bits, but
+//     the mean-field gradient call on many_gmm with 15 000 particles went from 52.6 us to 53.7 / 55.0 us in two processes against
+//     a spread of 0.3 us over the previous build's windows (profiles/r14_tile_plain_ab.txt, section 5).
+// The network-free kernels do not keep their bytes on the helpers (hais_traj_kernel and the ten whole-chain local-gradient
+// instances of grad_kernel compile to other code; hais_grad_kernel does not).  Their bar: no more scratch, no occupancy step lost,
+// bit-identical results, the previous build's timing spread (CHANGELOG round 16, profiles/r14_tile_plain_device_asm.txt,
+// profiles/r14_tile_plain_ab.txt); a kernel that misses it keeps its inline copy and is named here with the numbers.
 //
 // Mapping: one wave owns 16 particles, lane (g, c) holds particle c and the hidden units {16 t + 4 g + r}; layer 2 on
 // v_mfma_f32_16x16x4_f32 with the packed W2 A fragments streamed from LDS, layers 1 and 3 on the VALU from the w1z / w3t tables,
@@ -153,6 +173,27 @@ __device__ __forceinline__ void tile_split(uint32_t k0, uint32_t k1, int gb, uin
   threefry2x32(k0, k1, x0, x1);
 }
 
+// normal(key, (D,)): block j encrypts (j, Hh + j), pad counter 0; the blocks are dealt to the four rows of the wave
+template <int D>
+__device__ __forceinline__ void tile_normal(uint32_t ka, uint32_t kb, int g, float (&nz)[2 * ((D + 1) / 2)]) {
+  constexpr int Hh = (D + 1) / 2;
+#pragma unroll
+  for (int j0 = 0; j0 < Hh; j0 += 4) {
+    const int j = j0 + g;
+    uint32_t y0 = j, y1 = (Hh + j < D) ? Hh + j : 0;
+    threefry2x32(ka, kb, y0, y1);
+    uint32_t r0[4], r1[4];
+    rows0123(__float_as_uint(bits_to_normal(y0)), r0);
+    rows0123(__float_as_uint(bits_to_normal(y1)), r1);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (j0 + q < Hh) {
+        nz[j0 + q] = __uint_as_float(r0[q]);
+        nz[Hh + j0 + q] = __uint_as_float(r1[q]);
+      }
+  }
+}
+
 // one step of the key chain: (G, H) = split(gen); nz = normal(G, (D,)); gen = second(split(H)).  Lane row g computes block
 // (g & 1) of split(gen); the 2 + ceil(D / 2) blocks of split(H) and normal(G) are dealt to the four rows (traj_kernel's).
 template <int D>
@@ -216,6 +257,38 @@ __device__ __forceinline__ void tile_stats_butterfly(double& ex) {
   for (int o = 1; o < 16; o <<= 1) ex += __shfl_xor(ex, o);
 }
 
+// the whole record of a tile over l := loss: {finite count, sum, sum of squares, max of -l, sum exp(-l - max)} -> out5, by lane 0.
+// `use`: this lane holds a particle of the batch and is the one of its four lanes that counts (lane row 0).
+__device__ __forceinline__ void tile_stats_record(float loss, bool use, int lane, double* out5) {
+  double cnt = (use && isfinite(loss)) ? 1.0 : 0.0;
+  double sm = use ? (double)loss : 0.0;
+  double sq = use ? (double)loss * (double)loss : 0.0;
+  double mx = use ? -(double)loss : -INFINITY;
+  tile_stats_butterfly(cnt, sm, sq, mx);
+  double ex = (use && mx > -INFINITY && mx < INFINITY) ? exp(-(double)loss - mx) : 0.0;
+  tile_stats_butterfly(ex);
+  if (lane == 0) {
+    out5[0] = cnt; out5[1] = sm; out5[2] = sq; out5[3] = mx; out5[4] = ex;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// many_gmm's constants as Target<>::eval expects them in LDS, by the whole workgroup: {scale, means} as handed to the C ABI ->
+// {1/scale, c2, n_mix bits, c0, means} (log2 units).  The caller keeps its `if (TARGET == CMCD_TARGET_MANY_GMM)` and its barrier.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void tile_stage_many_gmm(const float* tc, int n_mix, float* lds_tgt) {
+  const float s = tc[0];
+  for (int idx = threadIdx.x; idx < 4 + 2 * n_mix; idx += blockDim.x) {
+    float v;
+    if (idx == 0) v = 1.0f / s;
+    else if (idx == 1) v = -0.5f * 1.44269504088896340736f / (s * s);
+    else if (idx == 2) v = __int_as_float(n_mix);
+    else if (idx == 3) v = 1.44269504088896340736f * (-2.0f * (logf(s) + kHalfLog2Pi) - logf((float)n_mix));
+    else v = tc[1 + (idx - 4)];
+    lds_tgt[idx] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host: instance table and launch.  Family supplies `fn` and `get<TARGET, ARCH, D, T>()`, the kernel instance.
 // ------------------------------------------------------------------------------------------
@@ -248,6 +321,16 @@ static typename Family::fn tile_pick(const cmcd_desc& d, int T) {
     if (T == 4) return Family::template get<CMCD_TARGET_FUNNEL, CMCD_ARCH_GEFFNER, 10, 4>();
     if (T == 9) return Family::template get<CMCD_TARGET_FUNNEL, CMCD_ARCH_GEFFNER, 10, 9>();
   }
+  return nullptr;
+}
+
+// the instances of the network-free wave-per-tile kernels (mean-field, Hamiltonian AIS, MCD_ULA's sweep): the same three
+// (target, dim) pairs.  Family supplies `fn` and `get<TARGET, D>()`.
+template <class Family>
+static typename Family::fn tile_pick_plain(int target, int dim) {
+  if (target == CMCD_TARGET_GMM && dim == 2) return Family::template get<CMCD_TARGET_GMM, 2>();
+  if (target == CMCD_TARGET_MANY_GMM && dim == 2) return Family::template get<CMCD_TARGET_MANY_GMM, 2>();
+  if (target == CMCD_TARGET_FUNNEL && dim == 10) return Family::template get<CMCD_TARGET_FUNNEL, 10>();
   return nullptr;
 }
 

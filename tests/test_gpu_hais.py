@@ -10,7 +10,7 @@ cases, whose q is wide enough (forward) or far enough out (gated_cases.HAIS_FLOO
 Which gradient case reaches what in cmcd_hais.hip: n = 145 / 133 (10 / 9 tiles) run hais_grad_kernel in three workgroups, the
 last with two (three) idle waves, and the eight-wide loop of hais_reduce_kernel once plus its remainder loop; K = 40, (K, ngrid)
 = (8, 3) and (5, 32) put the bridges off the grid's nodes (frac inside (0, 1), cells with several bridges and with none);
-the floor case runs the lp > -1e4 gate of eval_hess; n_mixes = 17 the generic component loops behind hais_stage_target;
+the floor case runs the lp > -1e4 gate of eval_hess; n_mixes = 17 the generic component loops behind tile_stage_many_gmm;
 n_total the omega of the C call."""
 import functools
 import math
@@ -129,7 +129,7 @@ def test_forward_many_gmm_with_a_floored_end_point(hip_lib):
 
 @pytest.mark.parametrize("n_mixes", [7, 17, 64])
 def test_forward_many_gmm_with_other_mixture_sizes(hip_lib, n_mixes):
-    """config.n_mixes != 40 takes the generic component loops of pass1 / pass2 behind hais_stage_target (64: the library's
+    """config.n_mixes != 40 takes the generic component loops of pass1 / pass2 behind tile_stage_many_gmm (64: the library's
     maximum), as tests/test_gpu_parity.py::test_many_gmm_with_other_mixture_sizes does for the older modes."""
     n, K, L = 37, 4, 2
     l_ref, z_ref, _ = reference("many_gmm", K, L, n, n_mixes=n_mixes)
@@ -350,6 +350,27 @@ def test_zero_step_size_is_the_mean_field_bound(hip_lib, name):
     assert float((losses - l0).abs().max()) <= 1e-6 and float((z - z0).abs().max()) <= 1e-6
     _, (l1, z1) = hais.compute_bound(seeds, flat, un, (dim, 0, 1), target_of(name))      # nbridges = 0 is forwarded
     assert torch.equal(l1, l0) and torch.equal(z1, z0)
+
+
+@pytest.mark.parametrize("name", ["gmm", "funnel"])
+def test_zero_step_size_keeps_the_bits_of_the_mean_field_draw(hip_lib, name):
+    """hais_traj_kernel draws z_0 through cmcd_tile.h (tile_split, tile_normal), mfvi_kernel through the inline copy it keeps
+    (the note above it in cmcd_mfvi.hip): the two must stay one draw.  With eps = 0 the leap-frog adds eps r / s^2 = 0 to z at
+    every step, so the end point of the chain is z_0 = mean + std normal(A) as the mean-field call forms it for the same seeds
+    and q: the same bits, on 33 particles (two full tiles and a one-lane tile), K = 2, L = 1, under a q with every leaf
+    non-trivial.  The build in which both kernels had private copies satisfied this bit for bit as well
+    (profiles/r14_tile_plain_ab.txt, section 3), so nothing is allowed here."""
+    dim, _, sigma, mean_scale = TARGETS[name]
+    seeds = dev(np.arange(1, 34))
+    flat, un, fixed = hr.make_params(dim, 2, 1, 0.0, seed=12, device="cuda", mean_scale=mean_scale, sigma=sigma)
+    assert float(flat[un.offset("eps")]) == 0.0 and fixed == (dim, 2, 1)
+    _, (_, z) = hais.compute_bound(seeds, flat, un, fixed, target_of(name))
+    _, (_, z0) = bm.compute_bound(seeds, flat, un, (dim, 0, 1), target_of(name))       # cmcd_mfvi_bound_grad
+    torch.cuda.synchronize()
+    assert z.shape == (33, dim) and bool(torch.isfinite(z0).all()) and float(z0.std(dim=0).min()) > 0
+    print(name, "entries whose bits differ:", int((z.view(torch.int32) != z0.view(torch.int32)).sum()),
+          "max |z difference|", float((z - z0).abs().max()))
+    assert torch.equal(z.view(torch.int32), z0.view(torch.int32))
 
 
 def test_same_bits_forward_gradient_repeat_capture_and_batch_composition(hip_lib):

@@ -418,3 +418,29 @@ def test_reverse_and_segment_instances_keep_their_scratch_sizes(reverse_asm, seg
             sym = "_ZN4cmcd19%s_traj_kernelILi%dELi%dELi%dELi%dEEEvNS_%sE" % ((name,) + inst + (args,))
             _, tail = _kernel_whole(lines, sym)
             assert _scratch(tail) == TILE_SCRATCH[name].get(inst, 0), (name, inst, _scratch(tail))
+
+
+# ------------------------------------------------------------- r16: the network-free tile kernels on cmcd_tile.h's helpers
+# (target, D): gmm 0 / funnel 1 / many_gmm 2 -> VGPRs in the build of the commit before cmcd_hais.hip was put on the helpers
+# 
+HAIS_VGPRS = {(0, 2): (71, 76), (2, 2): (89, 72), (1, 10): (143, 221)}       # (hais_traj_kernel, hais_grad_kernel)
+MFVI_VGPRS = {(0, 2): 39, (1, 10): 55, (2, 2): 58}
+
+
+def test_hais_and_mfvi_instances_stay_within_their_registers_without_scratch(tmp_path_factory):
+    """r16: the Hamiltonian AIS forward kernel takes the z_0 draw, the key-chain step, the statistics record and the many_gmm
+    staging from cmcd_tile.h and compiles to other code than with its inline copies, so the bar is the resources and not the
+    bytes: no instance uses scratch, none needs more VGPRs than before.  The sweep and the mean-field kernel (which keeps its
+    inline copies) are held to the same figures."""
+    from cmcd_amd import build
+    hais = _asm(tmp_path_factory, "cmcd_hais.hip", build.EXTRA_FLAGS.get("cmcd_hais.hip", []))
+    mfvi = _asm(tmp_path_factory, "cmcd_mfvi.hip", build.EXTRA_FLAGS.get("cmcd_mfvi.hip", []))
+    for inst, (traj, sweep) in HAIS_VGPRS.items():
+        for kern, bound in (("hais_traj_kernel", traj), ("hais_grad_kernel", sweep)):
+            _, tail = _kernel_whole(hais, "_ZN4cmcd16%sILi%dELi%dEEEvNS_8HaisArgsE" % ((kern,) + inst))
+            assert _scratch(tail) == 0, (kern, inst, _scratch(tail))
+            assert _vgprs(tail) <= bound, (kern, inst, _vgprs(tail), bound)
+    for inst, bound in MFVI_VGPRS.items():
+        _, tail = _kernel_whole(mfvi, "_ZN4cmcd11mfvi_kernelILi%dELi%dEEEvNS_8MfviArgsE" % inst)
+        assert _scratch(tail) == 0, (inst, _scratch(tail))
+        assert _vgprs(tail) <= bound, (inst, _vgprs(tail), bound)

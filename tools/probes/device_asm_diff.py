@@ -3,7 +3,8 @@ code is checked with (CHANGELOG rounds 7 and 12).
   python tools/probes/device_asm_diff.py <tree A> <tree B> [file.hip ...]      (default: every .hip of either tree's csrc)
 Each file is compiled with the command of tests/test_isa_properties.py::_asm plus its tree's build.EXTRA_FLAGS.  Per kernel (a
 symbol with an .amdhsa_kernel block) two things are compared: the function from its label to .Lfunc_end, with the function number
-taken out of the local labels (it counts the functions of the file), and the .amdhsa_kernel ... .end_amdhsa_kernel block.  A kernel
+taken out of the local labels and of the loop comments that name them (it counts the functions of the file, so it moves when
+the instances are emitted in another order), and the .amdhsa_kernel ... .end_amdhsa_kernel block.  A kernel
 that differs is named with its register, scratch, LDS and occupancy lines from both trees.  Exit status 1 on any difference."""
 import importlib.util
 import os
@@ -14,7 +15,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-LOCAL = re.compile(r"\.L(BB|func_begin|func_end|tmp|JTI)\d+")
+LOCAL = re.compile(r"(\.L(?:BB|func_begin|func_end|tmp|JTI)|Header=BB|Loop BB)\d+")   # the labels and the loop comments that name them
 RESOURCES = ("NumSgprs", "NumVgprs", "NumAgprs", "TotalNumVgprs", "ScratchSize", "LDSByteSize", "Occupancy")
 
 
@@ -48,7 +49,7 @@ def kernels(lines):
         block_end = next(k for k in range(i, len(lines)) if ".end_amdhsa_kernel" in lines[k])
         start = next(k for k, m in enumerate(lines) if m.startswith(name + ":"))
         end = next(k for k in range(start + 1, len(lines)) if lines[k].startswith(".Lfunc_end"))
-        body = [LOCAL.sub(lambda m: ".L" + m.group(1), m) for m in lines[start:end + 1]]
+        body = [LOCAL.sub(lambda m: m.group(1), m) for m in lines[start:end + 1]]
         notes = [m.strip() for m in lines[end:end + 40] if any(("; %s:" % r) in m for r in RESOURCES)]
         res[name] = (body, lines[i:block_end + 1], notes)
     return res
