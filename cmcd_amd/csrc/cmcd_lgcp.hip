@@ -76,7 +76,7 @@ struct StepEpi {         // evaluation i at z_i: closes step i-1, opens step i (
   const float* factor;       // factor_sn (device scalar)
   uint32_t* gen;             // [kMP][2]      gen key of the chain (advanced by column block 0's extra wave)
   uint32_t* gkey;            // [2][kMP][2]   G_i, parity-buffered by i: read [i & 1], written [(i + 1) & 1]
-  uint32_t* gktab;           // [K][n_total][2] every G_i of every particle (the VarGrad sweep redraws the noise from it)
+  uint32_t* gktab;           // [K][n_total][2] every G_i of every particle (no reader since r18; kept with the layout)
   float* wslot;              // [ncb][kMP]    running sum over closed steps of (bk - fk) on this block's columns
   float* fkslot;             // [ncb][kMP]    forward-kernel log-density of the open step on this block's columns
   float* lpslot;             // [ncb][kMP]    log p(z_K) on this block's columns (i = K)
@@ -141,7 +141,6 @@ struct LgcpAdjArgs {
   int M, D, K, e, grad_clipping;
   float omega;               // weight of every particle's loss (reparameterised gradient of the mean)
   const float* omega_vec;    // [n] VarGrad: weight of particle p's LOG-WEIGHT (cmcd_vargrad_weights), or nullptr
-  const uint32_t* gktab;     // [K][n][2] noise keys of the forward pass (VarGrad: z_{e+1} - mean = sigma eps_e, exactly)
   int ula;                   // 0: CAIS; 1: MCD_ULA (no network); 2: MCD_ULA_sn (network in the backward kernel only)
   int bptt;                  // 1: gradient through the trajectory (lambda recursion); 0: z detached (mcd_cais_var.py:59,79)
   int nslab = kSplit;        // slabs of kr / sn to sum: kSplit (recomputed by the split-K GEMM) or 1 (kept by the forward)
@@ -238,16 +237,11 @@ __device__ __forceinline__ void lgcp_adj_elem(const LgcpAdjArgs& a, int p, int j
     }
     if (e < K) {   // forward kernel of step e
       const float uf = -1.0f * (be * gp + (1.0f - be) * gq);
-      float df = (znv[j] - z) + ee * (uf + fsn * s);      // z_{e+1} - (z - ee uf - ee s), same ordering
-      if (!bptt) {
-        // the weights omega_p sum to zero and |df|^2 / (4 eps^2) is ~1e5 per particle: the float32 difference above loses
-        // the digits that survive the cancellation.  z_{e+1} = mean + sigma eps_e, so redraw eps_e (mcd_cais.py:66-67)
-        const int H = (D + 1) / 2, jj = j < H ? j : j - H;
-        const uint32_t* gk = a.gktab + ((int64_t)e * a.n + a.base + p) * 2;
-        uint32_t y0 = jj, y1 = (H + jj < D) ? H + jj : 0;
-        threefry2x32(gk[0], gk[1], y0, y1);
-        df = a.sched[8 * e + 2] * bits_to_normal(j < H ? y0 : y1);
-      }
+      const float df = (znv[j] - z) + ee * (uf + fsn * s);      // z_{e+1} - (z - ee uf - ee s), same ordering
+      // z detached: the weights omega_p sum to zero and |df|^2 / (4 eps^2) is ~1e5 per particle, against the backward kernel's
+      // r^2 / (4 eps^2) of the next evaluation.  Both must come from the same stored states: df redrawn as sigma eps_e leaves
+      // out the rounding of z_{e+1} at its store, which r = z_e - z_{e+1} + .. carries, and 2 df (that rounding) / (4 eps^2)
+      // does not cancel (r18: 5e-3 of d / d eps at eps = 2e-3, 5e-2 where the entry is small; 2e-4 / 2e-3 with the difference)
       const float nsig = df * (0.5f / ee);
       // cotangent of the kernel's mean: lambda_{e+1} when z_{e+1} = mean + noise carries the gradient on; with z detached
       // the density log N(z_{e+1}; mean, sigma) itself: d loss / d mean = +df / sigma^2
@@ -1833,46 +1827,52 @@ __global__ void lgcp_transpose_kernel(const float* __restrict__ src, float* __re
   }
 }
 
-// gbeta / geps / d factor_sn from the adjoint step's per-workgroup partials: one wave per evaluation e, fixed order
+// gbeta / geps / d factor_sn from the adjoint step's per-workgroup partials: one wave per schedule entry, fixed order.
+// Entry k takes what evaluation k gives through its forward kernel (t[3], t[4]) and evaluation k + 1 through its backward
+// kernel (t[0], t[1], t[2]).  The sums run in float64 and the two halves meet before anything is rounded: with z detached
+// the weights sum to zero, sum omega r^2 and sum omega df^2 are each ~1e5 eps^2 above what they leave, and 1 / (4 eps^2)
+// multiplies the rounding of a float32 sum (r05: 4e-4 of d / d eps between two groupings of the same particles at eps = 2e-3).
 struct LgcpAdjRedArgs {
   const float* part;     // [K+1][slots][8]
   const float* sched;
-  float* gbeta_lo;       // [K+1] contribution of evaluation e to entry e-1
-  float* geps_lo;
-  float* gbeta_hi;       // [K+1] contribution of evaluation e to entry e
-  float* geps_hi;
+  float* gbeta;          // [K]
+  float* geps;           // [K]
   float* gfac_e;         // [K+1]
   int K, slots;
 };
 
+__device__ __forceinline__ double wave_sum64d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 __global__ __launch_bounds__(64) void lgcp_adj_reduce_kernel(LgcpAdjRedArgs a) {
   const int e = blockIdx.x, lane = threadIdx.x;
-  float t[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool entry = e < a.K;                      // block K only has evaluation K's share of d factor_sn
+  double t[6] = {0., 0., 0., 0., 0., 0.}, u[3] = {0., 0., 0.};
   for (int sl = lane; sl < a.slots; sl += 64) {
     const float* o = a.part + ((int64_t)e * a.slots + sl) * 8;
 #pragma unroll
-    for (int q = 0; q < 6; ++q) t[q] += o[q];
+    for (int q = 0; q < 6; ++q) t[q] += (double)o[q];
+    if (entry) {
+      const float* n = a.part + ((int64_t)(e + 1) * a.slots + sl) * 8;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) u[q] += (double)n[q];
+    }
   }
 #pragma unroll
-  for (int q = 0; q < 6; ++q) t[q] = wave_sum64(t[q]);
+  for (int q = 0; q < 6; ++q) t[q] = wave_sum64d(t[q]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) u[q] = wave_sum64d(u[q]);
   if (lane == 0) {
-    const float pe = e > 0 ? a.sched[8 * (e - 1) + 1] : 1.f, ee = e < a.K ? a.sched[8 * e + 1] : 1.f;
-    const float inv2e = 0.5f / pe;
-    a.gbeta_lo[e] = e > 0 ? pe * t[0] : 0.f;
-    a.geps_lo[e] = e > 0 ? t[1] - t[2] * inv2e * inv2e : 0.f;            // t[2] = sum omega r^2
-    a.gbeta_hi[e] = e < a.K ? ee * t[3] : 0.f;
-    a.geps_hi[e] = e < a.K ? t[4] : 0.f;
-    a.gfac_e[e] = t[5];
+    a.gfac_e[e] = (float)t[5];
+    if (entry) {
+      const double ee = (double)a.sched[8 * e + 1], inv2e = 0.5 / ee;
+      a.gbeta[e] = (float)(ee * (t[3] + u[0]));
+      a.geps[e] = (float)(t[4] + u[1] - u[2] * inv2e * inv2e);          // u[2] = sum omega r^2
+    }
   }
-}
-
-// gbeta[k] = hi[k] + lo[k + 1]  (two addends: order-free), same for geps
-__global__ void lgcp_adj_combine_kernel(const float* lo_b, const float* hi_b, const float* lo_e, const float* hi_e, float* gbeta,
-                                        float* geps, int K) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= K) return;
-  gbeta[k] = hi_b[k] + lo_b[k + 1];
-  geps[k] = hi_e[k] + lo_e[k + 1];
 }
 
 // C[Ma][Nb] (ldc) += sum_r A[r][Ma]^T B[r][Nb]: contraction over the (K+1) n stored rows on the matrix cores.
@@ -1974,7 +1974,8 @@ struct LgcpGradWs {
   int64_t bops, wt3p, wt2p, wt1p;              // keep: packed dO | v | da2 | da1 operands and packed W3^T, W2^T, W1[:D]^T
   int64_t DO;                                  // [(K+1) n][D]
   int64_t S, S2, gbeta, geps, gfac, gb2;       // tables (gfac: [K+1] per-evaluation terms)
-  int64_t adjpart, gb_lo, ge_lo, gb_hi, ge_hi; // adjoint step partial sums and their per-evaluation reductions
+  int64_t adjpart, gb_lo, ge_lo, gb_hi, ge_hi; // adjoint step partial sums; the four [K+1] slots are unused since the reduction
+                                               // forms gbeta / geps itself (kept: the workspace layout is unchanged)
   int64_t counters;                            // arrival counters of the side stream's fused GEMMs (ints)
   int64_t zero_lo, zero_hi;                    // range to clear per call
   LgcpFwdSet fs[2];
@@ -2188,7 +2189,7 @@ int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, in
         aa.gmu_acc = gws + g.gmu_acc; aa.glam_acc = gws + g.glam_acc; aa.part = gws + g.adjpart;
         aa.DObig = gws + g.DO; aa.lay = lay; aa.n = n; aa.base = base;
         aa.M = M; aa.D = D; aa.K = K; aa.e = ev; aa.grad_clipping = d.grad_clipping; aa.omega = omega;
-        aa.ula = ula; aa.omega_vec = omega_vec; aa.gktab = reinterpret_cast<const uint32_t*>(ws + w.gktab); aa.bptt = bptt ? 1 : 0; aa.var_mode = d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0;
+        aa.ula = ula; aa.omega_vec = omega_vec; aa.bptt = bptt ? 1 : 0; aa.var_mode = d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0;
         if (nskb) { aa.dOp = dOp; aa.vp = vp; }
         return aa;
       };
@@ -2306,11 +2307,8 @@ int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, in
   }
   {
     const int slots = (int)(n * cbD);
-    LgcpAdjRedArgs ra{gws + g.adjpart, ws + sw.sched, gws + g.gb_lo, gws + g.ge_lo, gws + g.gb_hi, gws + g.ge_hi, gws + g.gfac,
-                      K, slots};
+    LgcpAdjRedArgs ra{gws + g.adjpart, ws + sw.sched, gws + g.gbeta, gws + g.geps, gws + g.gfac, K, slots};
     hipLaunchKernelGGL(lgcp_adj_reduce_kernel, dim3(K + 1), dim3(64), 0, stream, ra);
-    hipLaunchKernelGGL(lgcp_adj_combine_kernel, dim3((K + 255) / 256), dim3(256), 0, stream, gws + g.gb_lo, gws + g.gb_hi,
-                       gws + g.ge_lo, gws + g.ge_hi, gws + g.gbeta, gws + g.geps, K);
   }
   if (net)
     hipLaunchKernelGGL(lgcp_colsum_kernel, dim3(1), dim3(256), 0, stream, gws + g.gfac, (int64_t)(K + 1), 1, 1, grad + lay.g_factor, 1.0f, 0);

@@ -74,8 +74,10 @@ def make_logp_lgcp(flat_bin_counts, m=40):
     counts = torch.tensor(t.counts)
 
     def logp(z):
+        # the constants in the dtype of z (bound_and_grad(dtype=torch.float32)); at float64 `.to` returns the same tensors
+        k, c = kinv.to(z.dtype), counts.to(z.dtype)
         r = z - t.mu0
-        return -0.5 * ((r @ kinv) * r).sum(-1) + (z * counts - t.a * torch.exp(z)).sum(-1) + t.lognorm
+        return -0.5 * ((r @ k) * r).sum(-1) + (z * c - t.a * torch.exp(z)).sum(-1) + t.lognorm
     return logp
 
 

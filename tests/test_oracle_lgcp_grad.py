@@ -1,0 +1,146 @@
+"""tests/lgcp_grad_cases.py from the restatement alone (no GPU): each case is what its header says, the float32 gap behind every
+bar is the stored one, the block cuts tile every leaf once, the float32 switch of the lgcp log-density left the float64 results
+alone, and two independent statements of the same gradient agree (the sharding contract tests/test_gpu_lgcp_grad.py uses)."""
+import numpy as np
+import pytest
+import torch
+
+import lgcp_grad_cases as lc
+from helpers import lgcp_counts_fixture
+from oracle import cmcd_oracle_torch as ot
+
+
+def test_cases_are_what_their_header_says():
+    assert len(set(lc.IDS)) == len(lc.IDS) and set(lc.PASSES) == set(lc.IDS) == set(lc.stored_gaps())
+    for cid, mode, n, K, form, over in lc.CASES:
+        assert 1 <= K <= 3 and 1 <= n <= 129 and form in (0, 3), cid
+        assert lc.PASSES[cid] == lc.passes_of(n) and sum(lc.PASSES[cid]) == n, cid
+        assert over.get("eps_schedule") != "linear" or K > 1, cid
+    kind = lambda cid: [lc.gemm_of(m) for m in lc.PASSES[cid]]
+    assert kind("n16") == ["nsk"] and kind("n17") == ["merged"] and kind("n20") == ["merged"] and kind("n21") == ["split-k"]
+    assert kind("n33") == ["split-k", "nsk"] and kind("n52") == ["split-k", "merged"] and len(kind("n65")) == 3
+    assert len(kind("n129")) == 5 > 4                                             # one more pass than the forward has lanes
+    for fam in ("var-", "ulasn-", "uha-"):                                        # the merged instance in every family
+        assert any(kind(c) [-1] == "merged" for c in lc.IDS if c.startswith(fam)), fam
+    assert {lc.case_by_id(c)[3] for c in ("n21", "n129", "rc-n21", "uha-n52")} == {1}
+    widths = {c: lc.D + lc.case_by_id(c)[5].get("emb_dim", 20) for c in lc.IDS}
+    assert widths["w1612-21"] == 1612 and 1612 % 16 and 1612 % 128 and -(-1612 // 16) == 101
+    assert widths["w1670-5"] > 1664 >= widths["n20"]                               # 16 kNskChunks: lgcp_nsk_ok
+    assert {lc.case_by_id(c)[4] for c in lc.IDS if c.startswith("rc-")} == {3}
+
+
+@pytest.mark.parametrize("param_set", lc.PARAM_SETS)
+@pytest.mark.parametrize("cid", lc.IDS)
+def test_float32_gap_is_the_stored_one(cid, param_set):
+    """Re-measures `float32_gap` and holds the golden record to it: a listed block within 1.5 x of its stored gap (both ways where
+    the gap sets the bar), an unlisted one below 1.5 x LISTED, every bar at least FACTOR x the gap, the losses and z within a
+    quarter of compare_losses' 1e-3, the named tiny / zero blocks the same, and no more than MAX_LOST of the blocks lost."""
+    case = lc.case_by_id(cid)
+    gap, stored = lc.float32_gap(case, param_set), lc.stored_gap(case, param_set)
+    worst = sorted(gap["blocks"].items(), key=lambda kv: -kv[1])[:3]
+    print(cid, param_set, "loss %.2e z %.2e" % (gap["loss"], gap["z"]), "worst blocks", [(k, "%.1e" % v) for k, v in worst])
+    assert gap["tiny"] == stored["tiny"] and gap["zero"] == stored["zero"]
+    assert gap["loss"] <= 1.5 * stored["loss"] and gap["z"] <= 1.5 * stored["z"]
+    assert stored["loss"] <= lc.QUARTER * 1e-3 and stored["z"] <= lc.QUARTER * 1e-3
+    bar, lost = lc.bars(case, param_set)
+    assert set(stored["blocks"]) <= set(gap["blocks"])
+    for name, g in gap["blocks"].items():
+        s = stored["blocks"].get(name)
+        if s is None:
+            assert g <= 1.5 * lc.LISTED, (name, g)
+            assert bar(name) == lc.BAR
+            continue
+        assert s > lc.LISTED and g <= 1.5 * s, (name, g, s)
+        if s > lc.QUARTER * lc.BAR:                 # the gap sets the bar (or loses the block): not overstated either
+            assert s <= 1.5 * g, (name, g, s)
+        if name not in lost:
+            assert s <= lc.QUARTER * bar(name) and (bar(name) == lc.BAR or bar(name) == lc.FACTOR * s), (name, s, bar(name))
+    nblocks = len(gap["blocks"]) + len(gap["zero"])
+    assert len(lost) <= lc.MAX_LOST * nblocks, (lost, nblocks)
+
+
+@pytest.mark.parametrize("cid", ["n20", "w1612-21", "w1604", "w1670-5", "n33", "ula-n6", "uha-n16"])
+def test_block_cuts_tile_each_leaf_exactly_once(cid):
+    b = lc.build(lc.case_by_id(cid), "sparse", device="cpu")
+    numel = b["params_flat"].numel()
+    bl = lc.blocks(b["unflatten"], np.arange(numel, dtype=np.float64))
+    names = [name for name, _, _ in bl]
+    assert len(set(names)) == len(names)
+    hit = np.zeros(numel, np.int64)
+    for _, a, covers in bl:
+        assert a.size > 0
+        if covers:
+            np.add.at(hit, a.reshape(-1).astype(np.int64), 1)
+    assert hit.min() == 1 == hit.max()
+    whole = {name: a for name, a, covers in bl if not covers}
+    assert set(whole) == {"vd.mean", "vd.logdiag"} and all(a.size == lc.D for a in whole.values())
+    if cid != "ula-n6":
+        emb = b["unflatten"].shape("sn", "emb")[1]
+        rows = 2 * lc.D if cid.startswith("uha") else lc.D
+        by = dict((n, a) for n, a, _ in bl)
+        assert by["W1.emb.cols"].shape == (emb, rows) and by["W1.state.lastcols"].shape == (rows, emb)
+        assert by["W2.lastcols"].shape == (rows + emb, emb) and by["W3.last64"].shape == (rows + emb, 64)
+        assert by["b3.last64"].shape == (64,) and by["vd.mean[1536:1600]"].shape == (64,)
+
+
+def test_float64_results_did_not_change_with_the_float32_switch():
+    """make_logp_lgcp casts its two constant tensors to the dtype of z; at float64 every result keeps its bits (against the
+    log-density as it stood before the cast, written out here)."""
+    from oracle.targets import Lgcp
+    t = Lgcp(lgcp_counts_fixture())
+    kinv, counts = torch.tensor(t.kinv), torch.tensor(t.counts)
+
+    def before(z):
+        r = z - t.mu0
+        return -0.5 * ((r @ kinv) * r).sum(-1) + (z * counts - t.a * torch.exp(z)).sum(-1) + t.lognorm
+    for cid in ("n16", "var-n17"):
+        case = lc.case_by_id(cid)
+        new = lc.reference(case, "dense")
+        old = lc.run_restatement(case, "dense", logp=before)
+        assert new[0] == old[0]
+        for a, r in zip(new[1:], old[1:]):
+            assert a.dtype == np.float64 and np.array_equal(a, r)
+    with pytest.raises(RuntimeError):               # what the switch is for: the old form cannot run at float32
+        lc.run_restatement(lc.case_by_id("n1"), "dense", dtype=torch.float32, logp=before)
+
+
+@pytest.mark.parametrize("cid", ["n33", "ulasn-n33", "uha-n33"])
+def test_gradient_of_the_mean_is_the_share_weighted_sum_of_its_shards(cid):
+    """bound_and_grad over 33 seeds == 21 / 33 of the call on seeds[:21] + 12 / 33 of the call on seeds[21:]: what n_total asks
+    of the device (each shard scaled by 1 / n_total instead of 1 / its own n)."""
+    case = lc.case_by_id(cid)
+    seeds = lc.seeds_of(case)
+    _, l, z, g = lc.reference(case, "dense")
+    _, la, za, ga = lc.run_restatement(case, "dense", seeds=seeds[:21])
+    _, lb, zb, gb = lc.run_restatement(case, "dense", seeds=seeds[21:])
+    assert np.array_equal(np.concatenate([la, lb]), l) and np.array_equal(np.concatenate([za, zb]), z)
+    s = (21.0 * ga + 12.0 * gb) / 33.0
+    assert np.abs(g).max() > 0
+    assert np.abs(s - g).max() <= 1e-12 * np.abs(g).max()
+
+
+def test_vargrad_is_autograd_of_the_variance_of_the_concatenated_shard_losses():
+    """MCD_CAIS_var_sn: the gradient of var(losses) over 33 seeds == autograd of var(cat(losses of seeds[:21], losses of
+    seeds[21:])): the weights 2 (l_p - mean) / n_total need the merged statistics (stats_total), not a shard's own."""
+    case = lc.case_by_id("var-n33")
+    b = lc.build(case, "dense", device="cpu")
+    dim, K, mode, spec = b["params_fixed"]
+    seeds = lc.seeds_of(case)
+    p = ot.to_torch(lc.oracle_params_of(b))
+    logp = ot.make_logp_lgcp(lgcp_counts_fixture())
+    parts = [ot.losses(s, p, dim, K, mode, spec.arch, logp, b["cfg"]["eps_schedule"], b["cfg"]["grad_clipping"])[0]
+             for s in (seeds[:21], seeds[21:])]
+    value = torch.cat(parts).var(unbiased=False)
+    un = b["unflatten"]
+    _, _, _, g = lc.reference(case, "dense")
+    checked = 0
+    for path, leaf in ((("vd", "mean"), p["vd"]["mean"]), (("vd", "logdiag"), p["vd"]["logdiag"]), (("eps",), p["eps"]),
+                       (("sn", "nn", 2, 1), p["sn"]["b3"]), (("sn", "emb"), p["sn"]["emb"]),
+                       (("sn", "nn", 0, 0), p["sn"]["W1"])):
+        (got,) = torch.autograd.grad(value, leaf, retain_graph=True)
+        off = un.offset(*path)
+        want = g[off:off + got.numel()]
+        assert np.abs(want).max() > 0
+        assert np.abs(got.numpy().reshape(-1) - want).max() <= 1e-10 * np.abs(want).max(), path
+        checked += 1
+    assert checked == 6
