@@ -666,6 +666,69 @@ int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t
   return rc != CMCD_OK ? fail(rc, "gradient launch failed%s") : CMCD_OK;
 }
 
+// LDVI (cmcd_ldvi.hip).  The caller's descriptor with what the mode fixes: the network and its tables are those of
+// CMCD_MODE_CAIS_UHA_SN on the geffner net (same workspace plan, same prep launch); without a network the schedule tables and
+// target constants of CMCD_MODE_ULA.  Order of refusals: descriptor / lgcp / dds / the descriptor's own checks / instance /
+// K, then (entry point) pointers, n, layout, target constants, workspace.
+static int ldvi_desc(const cmcd_desc* desc, int32_t use_net, cmcd_desc& e) {
+  if (!desc) return fail(CMCD_ERR_BAD_ARG, "null desc%s");
+  if (desc->target == CMCD_TARGET_LGCP)
+    return fail(CMCD_ERR_UNSUPPORTED, "LDVI (MCD_U_a-lp[-sn]) on lgcp is not implemented (no launch sequence for d = 1600)%s");
+  if (use_net && desc->arch != CMCD_ARCH_GEFFNER)
+    return fail(CMCD_ERR_UNSUPPORTED, "LDVI (MCD_U_a-lp-sn): nn_arch dds is not implemented (geffner only)%s");
+  e = *desc;
+  e.mode = use_net ? CMCD_MODE_CAIS_UHA_SN : CMCD_MODE_ULA;
+  if (!use_net) e.arch = CMCD_ARCH_DDS;   // MCD_ULA's placeholder: no network
+  e.eps_schedule = CMCD_EPS_CONST;
+  e.grad_clipping = 0;
+  e.reserved = 0;
+  int rc = check_desc(&e);
+  if (rc != CMCD_OK) return rc;
+  int HP = 0;
+  hidden_width(e, HP);
+  if (!ldvi_available(e, HP / 16, use_net != 0))
+    return fail(CMCD_ERR_UNSUPPORTED, "no LDVI kernel instance for this (target, dim, width=%s%lld)", "", HP);
+  if (e.nbridges > 4096) return fail(CMCD_ERR_UNSUPPORTED, "LDVI: nbridges above 4096%s");
+  return CMCD_OK;
+}
+
+int64_t cmcd_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n, int32_t with_grad) {
+  cmcd_desc e;
+  CallPlan p;
+  if (ldvi_desc(desc, use_net, e) != CMCD_OK || n < 1 || n > (int64_t)1 << 31) return 0;
+  if (make_plan(e, n, 0, PLAN_FORWARD, true, p) != CMCD_OK) return 0;
+  return (align4(p.fwd) + (with_grad ? ldvi_grad_floats(e, p.w.HP, n, use_net != 0) : 0)) * 4;
+}
+
+int cmcd_ldvi_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, int32_t use_net, const int32_t* seeds, int64_t n,
+                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target, float omega,
+                         void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z, double* out_stats,
+                         float* grad, void* stream_) {
+  cmcd_desc e;
+  int rc = ldvi_desc(desc, use_net, e);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !seeds || !params || !workspace || !out_loss || !out_z || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  if (!layout_inside(e, *lay, n_params) || lay->gamma < 0 || lay->gamma >= n_params)
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(e.target, target_consts, n_target)) != CMCD_OK) return rc;
+  CallPlan p, q;   // the layout is this call's, the demand is the size query's (many_gmm: the largest target block)
+  if ((rc = make_plan(e, n, n_target, PLAN_FORWARD, false, p)) != CMCD_OK) return rc;
+  if ((rc = make_plan(e, n, 0, PLAN_FORWARD, true, q)) != CMCD_OK) return rc;
+  const int64_t gfl = grad ? ldvi_grad_floats(e, p.w.HP, n, use_net != 0) : 0;
+  if ((rc = check_workspace(workspace, workspace_bytes, (align4(q.fwd) + gfl) * 4)) != CMCD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  launch_prep(e, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(e, *lay, n, n_params, n_target));
+  rc = ldvi_launch(e, *lay, p.w, use_net != 0, seeds, n, params, n_params, ws, ws + align4(p.fwd), omega, out_loss, out_z, grad,
+                   stream);
+  if (rc != CMCD_OK) return rc;
+  launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
 int cmcd_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,
                          void* stream_) {
   if (!loss || !stats || !omega || n < 1 || n_total < n) return fail(CMCD_ERR_BAD_ARG, "bad argument%s");

@@ -67,6 +67,16 @@ bool segment_available(const cmcd_desc& d, int T);
 int segment_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, int32_t k0, int32_t k1, float* z, float* wpath,
                    uint32_t* key, float* lg, hipStream_t stream);
 
+// cmcd_ldvi.hip: LDVI (MCD_U_a-lp-sn / MCD_U_a-lp, include/cmcd_hip.h: cmcd_ldvi_bound_grad), one wave per 16-particle tile.
+// `d` is the effective descriptor whose tables launch_prep left in ws (use_net: CMCD_MODE_CAIS_UHA_SN on the geffner net;
+// otherwise CMCD_MODE_ULA: schedule tables and target constants only).  The forward chain leaves one statistics record per tile
+// at ws + w.partials; with `grad` non-null it keeps its states in gws (ldvi_grad_floats floats) and the gradient launches follow.
+bool ldvi_available(const cmcd_desc& d, int T, bool use_net);
+int64_t ldvi_grad_floats(const cmcd_desc& d, int HP, int64_t n, bool use_net);
+int ldvi_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, bool use_net, const int32_t* seeds, int64_t n,
+                const float* params, int64_t n_params, float* ws, float* gws, float omega, float* out_loss, float* out_z,
+                float* grad, hipStream_t stream);
+
 // cmcd_resample.hip: importance statistics + systematic resampling, one workgroup per group of n / groups rows, one launch.
 // The group is walked in chunks of kResampleChunk rows with a float64 running sum carried between them.
 constexpr int kResampleChunk = 1024;

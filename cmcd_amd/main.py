@@ -219,6 +219,23 @@ def main(config):
             dim=dim, nbridges=config.nbridges, eta=config.init_eta, eps=config.init_eps, lfsteps=config.lfsteps,
             vdparams=vdparams_init, trainable=trainable, device=device)
         grad_and_loss, loss_fn = hais.grad_and_loss, hais.compute_bound
+    elif config.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp"):             # LDVI and its network-free sibling (cmcd_amd.ldvi)
+        from . import ldvi
+        if world > 1:
+            raise NotImplementedError("boundmode %s runs on one GPU: its particles are not sharded over ranks" % config.boundmode)
+        trainable = ("eta", "gamma")                                       # main.py:137-146 (eta is not read by this mode)
+        if config.train_eps:
+            trainable += ("eps",)
+        if config.train_vi:
+            trainable += ("vd",)
+        if config.train_betas:
+            trainable += ("mgridref_y",)
+        say(f"Params being trained : {trainable}")
+        params_flat, unflatten, params_fixed = ldvi.initialize(
+            dim=dim, nbridges=config.nbridges, vdparams=vdparams_init, eta=config.init_eta, eps=config.init_eps,
+            gamma=config.init_gamma, trainable=trainable, mode=config.boundmode, emb_dim=config.emb_dim, nlayers=config.nlayers,
+            nn_arch=config.nn_arch, device=device)
+        grad_and_loss, loss_fn = ldvi.grad_and_loss, ldvi.compute_bound
     elif "MCD" in config.boundmode:
         trainable = ("eta", "gamma")
         if config.train_eps:

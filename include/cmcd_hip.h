@@ -349,6 +349,42 @@ int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t 
                          void* workspace, int64_t workspace_bytes,
                          float* out_loss, float* out_z, double* out_stats, float* grad /* nullable: forward only */, void* stream);
 
+/* ---- LDVI: config.boundmode = "MCD_U_a-lp-sn" (use_net = 1) and its network-free sibling "MCD_U_a-lp" (use_net = 0),
+ * /root/reference/src/mcd_under_lp_a.py:6-87 reached through mcd_utils.py:83-120 from mcdboundingmachine.py:126-179; bound and
+ * reparameterised gradient.  Per seed, with eta = gamma eps, sigma = sqrt(2 eta), gU(z, b) = -(b grad log p(z) +
+ * (1 - b) grad log q(z)) (plain jax.grad(U): no clip) and eps the scalar parameter, constant over the bridges:
+ *   (A, B) = split(PRNGKey(seed));  z = mean + exp(logdiag) normal(A);  w = -log q(z)           mcdboundingmachine.py:151-157
+ *   C = first(split(B));  (R, G') = split(C);  rho = normal(R);  w -= log N(rho; 0, 1)          mcd_under_lp_a.py:66-71
+ *   gen = second(split(G'));  beta = interp(target_x, gridref_x, [0, cumsum(mgridref_y) / sum(mgridref_y)])
+ *   for i = 0 .. nbridges-1:
+ *     (G, H) = split(gen);  n_i = normal(G);  gen = second(split(H))                             :32,60
+ *     m_f = rho (1 - eta);  rho' = m_f + sigma n_i                                               :28-33
+ *     rho'' = rho' - eps/2 gU(z, beta_i);  z' = z + eps rho'';  rho_new = rho'' - eps/2 gU(z', beta_i)   :35-37
+ *     m_b = rho' (1 - eta) + 2 eta s([z; rho'], i)      (the old z; use_net = 0: no s term)      :41-51
+ *     w += log N(rho; m_b, sigma) - log N(rho'; m_f, sigma);  (z, rho) = (z', rho_new)           :54-61
+ *   w += log N(rho; 0, 1) + log p(z);  loss = -w                                                 :85, mcdboundingmachine.py:178
+ * The network is the one of CMCD_MODE_CAIS_UHA_SN (built with rho_dim = dim: geffner width 2 dim + emb_dim); there is no
+ * network in the forward kernel and one evaluation per bridge.  grad log p(z') closes bridge i and opens bridge i + 1:
+ * nbridges + 1 target evaluations per particle.  many_gmm's floor: grad log p = 0 where floored, loss = +inf when z_K is.
+ * desc: dim, nbridges, arch, emb_dim, target, ngrid are read; mode, eps_schedule, grad_clipping and reserved are IGNORED (the
+ * function body has neither a schedule nor a clip argument).  layout: the leaves of cmcd_layout, gamma included; use_net = 0
+ * reads vd, eps, gamma and mgridref_y only.  The leaf `eta` of the reference's tree is not read by this mode (gradient 0).
+ * out_loss / out_z / out_stats as cmcd_bound_forward.  grad (nullable: forward only) [n_params], overwritten: omega * sum_n
+ * d loss_n / d {vd.mean, vd.logdiag, eps, gamma, mgridref_y, sn}, zeros elsewhere; omega = 1 / N_total.  The positions and
+ * momenta do not depend on the network, so d / d sn is local per (particle, bridge) with the cotangent
+ * -omega (rho - m_b) on s; only vd, eps, gamma and mgridref_y take a reverse sweep, which is network-free.  The forward call
+ * and the gradient call return the same loss bits, repeated calls the same gradient bits (per-item and per-tile slots summed
+ * in a fixed order, no floating-point atomics).  A gradient call keeps 4 nbridges + 2 rows of n dim floats in the workspace
+ * (z_0..z_K, rho_0..rho_K, rho'_i and rho_i - m_b,i).  Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward.
+ * Instances: gmm, many_gmm (dim 2) on geffner widths up to 64 (emb_dim <= 60; README: 20), funnel (dim 10) on widths 65 .. 80
+ * (emb_dim 45 .. 60; README: 48); use_net = 0: the same three (target, dim).  lgcp ("lgcp" in the message), dds and every other
+ * width: CMCD_ERR_UNSUPPORTED, and 0 from the size query.  nbridges <= 4096, ngrid <= 32. */
+int64_t cmcd_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n, int32_t with_grad);
+int cmcd_ldvi_bound_grad(const cmcd_desc* desc, const cmcd_layout* layout, int32_t use_net, const int32_t* seeds, int64_t n,
+                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target, float omega,
+                         void* workspace, int64_t workspace_bytes,
+                         float* out_loss, float* out_z, double* out_stats, float* grad /* nullable: forward only */, void* stream);
+
 /* ---- Optimiser step of the training loop (/root/reference/src/opt.py:14-35,100-116) fused into one launch:
  * g = clip(grad, +-clip); Adam moments (optax.adam: bias correction 1 - b^step, eps outside the root);
  * params += -lr * m_hat / (sqrt(v_hat) + eps); projection of the listed ranges (opt.py:14-24);

@@ -78,13 +78,16 @@ if cfg.pretrain_mfvi:
     print("Done training initial parameters, got ELBO %.2f.  (%.2f ms/iter)" % (elbo_init, (time.time() - t) / cfg.mfvi_iters * 1e3))
 vdparams_init = {k: v.detach().cpu().clone() for k, v in unflatten(flat)[0]["vd"].items()}
 
-# 2. the annealed machine: Hamiltonian AIS (boundmode UHA, cmcd_amd.hais) or one of the MCD modes
+# 2. the annealed machine: Hamiltonian AIS (boundmode UHA, cmcd_amd.hais), LDVI (MCD_U_a-lp[-sn], cmcd_amd.ldvi) or one of the MCD modes
+LDVI = cfg.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp")
 if cfg.boundmode == "UHA":
     from cmcd_amd import hais
     if WORLD > 1:
         raise NotImplementedError("boundmode UHA runs on one GPU: its particles are not sharded over ranks")
     trainable = ("eta",)
 elif "MCD" in cfg.boundmode:
+    if LDVI and WORLD > 1:
+        raise NotImplementedError("boundmode %s runs on one GPU: its particles are not sharded over ranks" % cfg.boundmode)
     trainable = ("eta", "gamma")
 else:
     raise NotImplementedError("Mode %s not implemented." % cfg.boundmode)
@@ -99,6 +102,12 @@ if cfg.boundmode == "UHA":
     flat, unflatten, fixed = hais.initialize(dim=dim, nbridges=cfg.nbridges, eta=cfg.init_eta, eps=cfg.init_eps,
                                              lfsteps=cfg.lfsteps, vdparams=vdparams_init, trainable=trainable, device="cuda")
     grad_and_loss, loss_fn = hais.grad_and_loss, hais.compute_bound
+elif LDVI:
+    from cmcd_amd import ldvi
+    flat, unflatten, fixed = ldvi.initialize(dim=dim, nbridges=cfg.nbridges, vdparams=vdparams_init, eps=cfg.init_eps,
+                                             trainable=trainable, mode=cfg.boundmode, emb_dim=cfg.emb_dim, nn_arch=cfg.nn_arch,
+                                             device="cuda")
+    grad_and_loss, loss_fn = ldvi.grad_and_loss, ldvi.compute_bound
 else:
     flat, unflatten, fixed = mcdbm.initialize(dim=dim, nbridges=cfg.nbridges, vdparams=vdparams_init, eps=cfg.init_eps,
                                               trainable=trainable, mode=cfg.boundmode, emb_dim=cfg.emb_dim,
