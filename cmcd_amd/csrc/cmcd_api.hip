@@ -239,10 +239,11 @@ static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_
 //   forward:     [forward tables + statistics records]
 //   reverse:     the forward layout (same tables, one statistics record per 16-particle tile); overdamped modes, no lgcp
 //   segment:     the forward layout again (bridges [k0, k1) from a caller-supplied state); overdamped modes, no lgcp
+//   segment-uha: the same for MCD_CAIS_UHA_sn (the state carries the momentum); that mode only, no lgcp
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
 // ------------------------------------------------------------------------------------------
-enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT };
+enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT, PLAN_SEGMENT_UHA };
 
 struct CallPlan {
   cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
@@ -292,6 +293,14 @@ static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKin
     if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "chain segments have no lgcp kernel%s");
     if (!segment_available(d, p.w.T))
       return fail(CMCD_ERR_UNSUPPORTED, "no segment kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    return CMCD_OK;
+  }
+  if (kind == PLAN_SEGMENT_UHA) {
+    if (d.mode != CMCD_MODE_CAIS_UHA_SN)
+      return fail(CMCD_ERR_UNSUPPORTED, "cmcd_bound_segment_uha is MCD_CAIS_UHA_sn's segment call (the overdamped modes have cmcd_bound_segment)%s");
+    if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "chain segments have no lgcp kernel%s");
+    if (!segment_uha_available(d, p.w.T))
+      return fail(CMCD_ERR_UNSUPPORTED, "no 2nd-order segment kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
     return CMCD_OK;
   }
 
@@ -508,14 +517,15 @@ static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
   return chain_call_end(ta, out_stats, stream);
 }
 
-// bridges [k0, k1) of the forward chain from the state (z, wpath, key); seeds are read when k0 == 0 (cmcd_segment.hip)
+// bridges [k0, k1) of the forward chain from the state (z, wpath, key); seeds are read when k0 == 0 (cmcd_segment.hip).
+// uha: the 2nd-order chain from (z, rho, wpath, key) (cmcd_segment_uha.hip)
 static int segment_impl(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0, int32_t k1, const int32_t* seeds, int64_t n,
                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
-                        int64_t workspace_bytes, float* z, float* wpath, uint32_t* key, float* out_lg, double* out_stats,
-                        void* stream_) {
+                        int64_t workspace_bytes, float* z, float* rho, float* wpath, uint32_t* key, float* out_lg,
+                        double* out_stats, void* stream_, bool uha) {
   int rc = check_desc(desc);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !params || !workspace || !z || !wpath || !key || !out_lg || !out_stats)
+  if (!lay || !params || !workspace || !z || (uha && !rho) || !wpath || !key || !out_lg || !out_stats)
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
   if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
   if (k0 < 0 || k0 >= k1 || k1 > desc->nbridges)
@@ -524,10 +534,12 @@ static int segment_impl(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   CallPlan p;
   TrajArgs ta;
-  if ((rc = chain_call_begin(*desc, lay, PLAN_SEGMENT, seeds, n, params, n_params, target_consts, n_target, workspace,
-                             workspace_bytes, nullptr, nullptr, stream, p, ta)) != CMCD_OK) return rc;
-  snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_traj_kernel");
-  if ((rc = segment_launch(p.d, p.w, ta, k0, k1, z, wpath, key, out_lg, stream)) != CMCD_OK) return rc;
+  if ((rc = chain_call_begin(*desc, lay, uha ? PLAN_SEGMENT_UHA : PLAN_SEGMENT, seeds, n, params, n_params, target_consts, n_target,
+                             workspace, workspace_bytes, nullptr, nullptr, stream, p, ta)) != CMCD_OK) return rc;
+  snprintf(g_kernel_name, sizeof(g_kernel_name), uha ? "segment_uha_kernel" : "segment_traj_kernel");
+  rc = uha ? segment_uha_launch(p.d, p.w, ta, k0, k1, z, rho, wpath, key, out_lg, stream)
+           : segment_launch(p.d, p.w, ta, k0, k1, z, wpath, key, out_lg, stream);
+  if (rc != CMCD_OK) return rc;
   return chain_call_end(ta, out_stats, stream);
 }
 
@@ -628,7 +640,17 @@ int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0
                        void* workspace, int64_t workspace_bytes, float* z_inout, float* wpath_inout, uint32_t* key_inout,
                        float* out_lg, double* out_stats, void* stream_) {
   return segment_impl(desc, lay, k0, k1, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
-                      z_inout, wpath_inout, key_inout, out_lg, out_stats, stream_);
+                      z_inout, nullptr, wpath_inout, key_inout, out_lg, out_stats, stream_, false);
+}
+
+int64_t cmcd_segment_uha_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_SEGMENT_UHA); }
+
+int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0, int32_t k1, const int32_t* seeds, int64_t n,
+                           const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                           void* workspace, int64_t workspace_bytes, float* z_inout, float* rho_inout, float* wpath_inout,
+                           uint32_t* key_inout, float* out_lg, double* out_stats, void* stream_) {
+  return segment_impl(desc, lay, k0, k1, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
+                      z_inout, rho_inout, wpath_inout, key_inout, out_lg, out_stats, stream_, true);
 }
 
 int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,

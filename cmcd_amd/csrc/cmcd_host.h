@@ -1,6 +1,6 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip, cmcd_resample.hip and cmcd_sinkhorn.hip,
-// plus the two host helpers every entry point shares (al4, check_many_gmm).  cmcd_reverse.hip, cmcd_segment.hip, cmcd_grad.hip,
+// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip, cmcd_segment_uha.hip, cmcd_resample.hip and cmcd_sinkhorn.hip,
+// plus the two host helpers every entry point shares (al4, check_many_gmm).  cmcd_reverse.hip, cmcd_segment[_uha].hip, cmcd_grad.hip,
 // cmcd_mfvi.hip and cmcd_hais.hip include it through cmcd_tile.h, which holds the wave-per-tile pieces they share.  The seams of
 // the translation units that do not include it (the coop, lgcp, uha, bptt and opt files) are in cmcd_common.h, which the stored
 // counter figures are hashed over (bench.py: kernel_sources_sha).
@@ -66,6 +66,14 @@ int reverse_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, co
 bool segment_available(const cmcd_desc& d, int T);
 int segment_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, int32_t k0, int32_t k1, float* z, float* wpath,
                    uint32_t* key, float* lg, hipStream_t stream);
+
+// cmcd_segment_uha.hip: the same for MCD_CAIS_UHA_sn, whose particle state carries the momentum: bridges [k0, k1) of the 2nd-order
+// forward chain from (z, rho, wpath, key), one wave per 16-particle tile.  lg receives log gamma_k1(z) + log N(rho; 0, I).  The
+// instances of uha_traj_kernel (dds 64; geffner on 2 / 4 / 5 / 9 neuron tiles); none for the other modes and lgcp.  Its launch
+// sizes LDS for a first layer with 2 dim input rows, with tile_launch's waves-per-workgroup rule.
+bool segment_uha_available(const cmcd_desc& d, int T);
+int segment_uha_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, int32_t k0, int32_t k1, float* z, float* rho,
+                       float* wpath, uint32_t* key, float* lg, hipStream_t stream);
 
 // cmcd_ldvi.hip: LDVI (MCD_U_a-lp-sn / MCD_U_a-lp, include/cmcd_hip.h: cmcd_ldvi_bound_grad), one wave per 16-particle tile.
 // `d` is the effective descriptor whose tables launch_prep left in ws (use_net: CMCD_MODE_CAIS_UHA_SN on the geffner net;

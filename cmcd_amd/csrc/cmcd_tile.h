@@ -5,6 +5,7 @@
 //
 // Who includes it and what it takes:
 //   cmcd_reverse.hip, cmcd_segment.hip  tile_eval_net, tile_split, tile_chain_step, the two butterflies, tile_pick, tile_launch
+//   cmcd_segment_uha.hip  tile_split, tile_normal, tile_chain_step, tile_stats_record (network and launch: its own, below)
 //   cmcd_hais.hip    hais_traj_kernel: tile_split, tile_normal, tile_chain_step, tile_stats_record; both kernels:
 //                    tile_stage_many_gmm; tile_pick_plain
 //   cmcd_mfvi.hip    tile_pick_plain (mfvi_kernel itself stays on inline copies, below)
@@ -19,6 +20,11 @@
 //   uha_traj_kernel and uha_coop_kernel (cmcd_uha.hip): its draw_normal carries the capture hooks, the cooperative kernel has a
 //     split Threefry of its own, and replacing only the two statistics tails by tile_stats_record changed the body of all 40
 //     instances for about 36 lines less.  A separate decision.
+//   segment_uha_kernel (cmcd_segment_uha.hip) and the LDVI kernels (cmcd_ldvi.hip) each hold a copy of cmcd_uha.hip's
+//     net_pre_z / net_eval_rho (the network on [z; rho]): that file is hashed, so the two functions cannot move here.  The segment
+//     kernel also has a launch of its own (W1 has 2 D input rows: one more D * HP block of LDS than tile_launch sizes for) and an
+//     instance table of its own (uha_pick's: geffner on 5 neuron tiles as well); tests/test_gpu_smc_uha.py's forward-call test
+//     fails when its copy drifts.
 //   reverse_traj_kernel and segment_traj_kernel keep inline the LDS staging, q's constants and log q, grad log q with the clips,
 //     the z_0 draw, the two ends of a step and the head of the statistics record: as helpers each of them compiled to other code
 //     (another register allocation over the whole kernel, other scratch sizes on the funnel geffner instances), for reasons that

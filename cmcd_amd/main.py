@@ -61,7 +61,7 @@ def get_config():
     #                             its main.py always uses (main.py:148-159); only MCD_CAIS_UHA_sn reads gamma
     c.compute_w2 = True         # extra: --noconfig.compute_w2 skips the Sinkhorn W2 block of main.py:248-271 (test harness)
     c.compute_eubo = True       # extra: --noconfig.compute_eubo skips the reverse-chain diagnostics (EUBO, reverse ln Z / ESS)
-    c.smc_eval = False          # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc: resampling between bridges)
+    c.smc_eval = False          # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc / smc_uha: resampling between bridges)
     # fields of the reference's config this driver accepts so that its README command lines run unchanged, but whose
     # only legal value here is the default (dds nets are 64-wide, the lgcp posterior is un-whitened, 40 mixtures
     # unless n_mixes says otherwise) or that configure subsystems left out (NICE, W&B, the cluster launcher)
@@ -293,10 +293,15 @@ def main(config):
 
         say_reverse(params_flat, final_elbo, final_ln_Z)
     # SMC evaluation (no analogue in the reference): the same chain with the groups resampled between bridges when their ESS drops
+    # (MCD_CAIS_UHA_sn: the state carries the momentum, cmcd_amd.smc_uha; same driver, same result dict)
     smc_on = (config.smc_eval and rank == 0 and config.model in ("funnel", "gmm", "many_gmm") and
-              config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn"))
+              config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn"))
     if smc_on:
-        from . import sinkhorn, smc
+        from . import sinkhorn
+        if config.boundmode == "MCD_CAIS_UHA_sn":
+            from . import smc_uha as smc
+        else:
+            from . import smc
 
         def say_smc(p, prefix=""):
             G = config.n_input_dist_seeds

@@ -67,7 +67,8 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     L = _lib.lib()
     nbytes = mcdbm._nbytes(plan, "cmcd_segment_workspace_bytes", n)
     if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no segment kernel for this configuration")
+        hint = " — MCD_CAIS_UHA_sn: cmcd_amd.smc_uha (the state with momentum)" if params_fixed[2] == "MCD_CAIS_UHA_sn" else ""
+        raise NotImplementedError((_lib.last_error() or "no segment kernel for this configuration") + hint)
     ws = mcdbm._workspace(dev_index, device, stream, capturing, nbytes, "seg")
     mcdbm._prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
     consts = log_prob.consts_on(device)

@@ -236,6 +236,52 @@ int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* layout, int32_t
                        float* z_inout /*[n*dim]*/, float* wpath_inout /*[n]*/, uint32_t* key_inout /*[n*2]*/,
                        float* out_lg /*[n]*/, double* out_stats /*[5]*/, void* stream);
 
+/* ---- The same for MCD_CAIS_UHA_sn (2nd-order CMCD), whose particle state carries the momentum: bridges [k0, k1) from
+ * (z, rho, wpath, key); the Python driver is cmcd_amd.smc_uha, the float64 restatement tests/smc_uha_restatement.py.
+ * Schedules (cos^2, always), the clip of grad log p at 1e2, the network s([z; rho], i) and q are those of cmcd_bound_forward
+ * for the same (desc, layout, params) in mode CMCD_MODE_CAIS_UHA_SN — the same prep tables.  With eta_i = gamma eps_i,
+ * sigma_i = sqrt(2 eta_i) and gU(z, b) = -(b clip(grad log p(z), +-1e2) + (1 - b) grad log q(z)), particle p runs
+ *   k0 == 0:  (A, B) = split(PRNGKey(seed));  z_0 = mean + std normal(A);  C = first(split(B));  (R, G') = split(C);
+ *             rho_0 = normal(R);  gen_0 = second(split(G'))   (one more split in front of gen_0 than the overdamped chain);
+ *             wpath = -log q(z_0) - log N(rho_0; 0, I)
+ *   k0  > 0:  z = z_inout[p], rho = rho_inout[p], wpath = wpath_inout[p], gen = key_inout[p]   (the forward chain's gen_k0)
+ *   for i = k0 .. k1-1, the forward call's bridge i, unchanged:
+ *             m_f = rho (1 - eta_i) - 2 eta_i s([z; rho], i);   rho' = m_f + sigma_i xi_i,  xi_i = normal(first(split(gen)))
+ *             rho'' = rho' - eps_i gU(z, beta_i) / 2;  z' = z + eps_i rho'';  rho_new = rho'' - eps_i gU(z', beta_i) / 2
+ *             m_b = rho' (1 - eta_i) + 2 eta_i s([z; rho'], i)                       (the old z, the same index i)
+ *             wpath += log N(rho; m_b, sigma_i) - log N(rho'; m_f, sigma_i);   (z, rho) <- (z', rho_new);
+ *             gen <- second(split(second(split(gen))))
+ *   lg = log gamma_k1(z) + log N(rho; 0, I):  gamma_K = p;  0 < k < K:  log gamma_k = beta_{k-1} log p + (1 - beta_{k-1}) log q
+ *             (step k-1 uses beta_{k-1} at both leap-frog ends, as the overdamped step does at both of its kernels)
+ *   out:  z_inout[p] = z, rho_inout[p] = rho, wpath_inout[p] = wpath, key_inout[p] = gen_k1, out_lg[p] = lg;
+ *         out_stats[5] = the statistics of cmcd_bound_forward over l := -(wpath + lg).
+ * log p = -inf (the many_gmm floor) gives lg = -inf whatever beta and rho are, never 0 * inf; a NaN stays NaN.  The momentum's
+ * density is part of lg on purpose: -(wpath + lg) is the loss of a chain stopped at k1 (at k1 == nbridges the loss
+ * cmcd_bound_forward returns); the leap-frog is a volume-preserving bijection of (z, rho), so exp(wpath + lg) is a proper
+ * weight for gamma_k1(z) N(rho; 0, I) whatever the network is; and a resampling stage restarts its offspring with
+ * wpath = -lg[ancestor] exactly as for the overdamped state.  A caller that resamples moves z AND rho with the same
+ * ancestors and leaves key_inout alone (keys belong to the slot).
+ * The kernel is ONE runtime-bounded rotated loop m = k0 .. k1 with a single site that evaluates (log p, grad log p,
+ * grad log q) at z_m: for m > k0 it closes step m - 1 (rho = rho'' - eps_{m-1} ub / 2), for m < k1 it opens step m, at
+ * m == k1 it forms lg; the two network evaluations of a step stay inside the step.  So [0, k) then [k, K) returns the BITS
+ * of [0, K) in z, rho, wpath, lg and the key, at the price of one extra target evaluation per cut.
+ *   0 <= k0 < k1 <= nbridges, else CMCD_ERR_BAD_ARG;  seeds[n] int32 [device] is read when k0 == 0 (null there:
+ *   CMCD_ERR_BAD_ARG) and may be null otherwise.  z_inout[n*dim], rho_inout[n*dim], wpath_inout[n], out_lg[n] float32,
+ *   key_inout[n*2] uint32, out_stats[5] float64, all [device].
+ * Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward; workspace of cmcd_segment_uha_workspace_bytes (0
+ * where the call is unsupported).  Every call runs the prep launch.  One kernel form (one wave per 16-particle tile) on gmm,
+ * funnel (dim 10) and many_gmm with the nets of the forward call's wave-per-tile 2nd-order kernel (dds 64; geffner on 2 / 4 /
+ * 5 / 9 neuron tiles); the overdamped modes (they have cmcd_bound_segment), lgcp and other widths: CMCD_ERR_UNSUPPORTED.
+ * No cooperative form, no reverse-time chain, no LDVI / UHA-boundmode segments. */
+int64_t cmcd_segment_uha_workspace_bytes(const cmcd_desc* desc, int64_t n);
+int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* layout, int32_t k0, int32_t k1,
+                           const int32_t* seeds /* k0 == 0; else nullable */, int64_t n,
+                           const float* params, int64_t n_params,
+                           const float* target_consts, int64_t n_target,
+                           void* workspace, int64_t workspace_bytes,
+                           float* z_inout /*[n*dim]*/, float* rho_inout /*[n*dim]*/, float* wpath_inout /*[n]*/,
+                           uint32_t* key_inout /*[n*2]*/, float* out_lg /*[n]*/, double* out_stats /*[5]*/, void* stream);
+
 /* (Measurement and diagnostic hooks — kernel-time events, the PRNG capture of the parity tests, the probes' switches — are NOT
  * part of this boundary: they are declared in include/cmcd_hip_diag.h and compiled out of the library by
  * -DCMCD_NO_DIAG_HOOKS; a deployment binds nothing of them.) */

@@ -142,8 +142,14 @@ def evaluate(p, tag):
             tag, r["eubo"], r["reverse_ln_Z"], r["reverse_ess"], r["reverse_ess_std"], cfg.n_samples,
             100.0 * r["reverse_ess_frac"], e, r["eubo"]))
 
-    if cfg.smc_eval and x_tgt is not None:      # (same modes and targets as the reverse chain)
-        from cmcd_amd import resample, sinkhorn, smc
+    # (the modes and targets of the reverse chain, and MCD_CAIS_UHA_sn through cmcd_amd.smc_uha: the state with momentum)
+    smc_uha_on = len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and cfg.boundmode == "MCD_CAIS_UHA_sn"
+    if cfg.smc_eval and (x_tgt is not None or smc_uha_on):
+        from cmcd_amd import resample, sinkhorn
+        if smc_uha_on:
+            from cmcd_amd import smc_uha as smc
+        else:
+            from cmcd_amd import smc
         G = cfg.n_input_dist_seeds
         out = smc.smc_bound(eval_seeds, p, unflatten, fixed, log_prob_model, eps_schedule=cfg.eps_schedule,
                             grad_clipping=cfg.grad_clipping, groups=G, seed=cfg.seed)
