@@ -90,6 +90,12 @@ def lib():
             C.POINTER(Desc), C.POINTER(Layout), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p]
+        L.cmcd_reverse_uha_workspace_bytes.restype = C.c_int64
+        L.cmcd_reverse_uha_workspace_bytes.argtypes = [C.POINTER(Desc), C.c_int64]
+        L.cmcd_bound_reverse_uha.restype = C.c_int
+        L.cmcd_bound_reverse_uha.argtypes = [
+            C.POINTER(Desc), C.POINTER(Layout), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmcd_stats_merge.restype = C.c_int
         L.cmcd_stats_merge.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32,
                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]

@@ -240,10 +240,11 @@ static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_
 //   reverse:     the forward layout (same tables, one statistics record per 16-particle tile); overdamped modes, no lgcp
 //   segment:     the forward layout again (bridges [k0, k1) from a caller-supplied state); overdamped modes, no lgcp
 //   segment-uha: the same for MCD_CAIS_UHA_sn (the state carries the momentum); that mode only, no lgcp
+//   reverse-uha: the forward layout once more (the reverse-time chain of MCD_CAIS_UHA_sn); that mode only, no lgcp
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
 // ------------------------------------------------------------------------------------------
-enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT, PLAN_SEGMENT_UHA };
+enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT, PLAN_SEGMENT_UHA, PLAN_REVERSE_UHA };
 
 struct CallPlan {
   cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
@@ -301,6 +302,14 @@ static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKin
     if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "chain segments have no lgcp kernel%s");
     if (!segment_uha_available(d, p.w.T))
       return fail(CMCD_ERR_UNSUPPORTED, "no 2nd-order segment kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    return CMCD_OK;
+  }
+  if (kind == PLAN_REVERSE_UHA) {
+    if (d.mode != CMCD_MODE_CAIS_UHA_SN)
+      return fail(CMCD_ERR_UNSUPPORTED, "cmcd_bound_reverse_uha is MCD_CAIS_UHA_sn's reverse chain (the overdamped modes have cmcd_bound_reverse)%s");
+    if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain has no lgcp kernel%s");
+    if (!reverse_uha_available(d, p.w.T))
+      return fail(CMCD_ERR_UNSUPPORTED, "no 2nd-order reverse-chain kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
     return CMCD_OK;
   }
 
@@ -498,22 +507,25 @@ static int chain_call_end(const TrajArgs& ta, double* out_stats, hipStream_t str
   return CMCD_OK;
 }
 
-// the reverse-time chain: x[n][dim] target draws -> out_w, out_z0, statistics over l := w (cmcd_reverse.hip)
+// the reverse-time chain: x[n][dim] target draws -> out_w, out_z0, statistics over l := w (cmcd_reverse.hip).
+// uha: the 2nd-order chain, which also returns the end momentum out_rho0 (cmcd_reverse_uha.hip)
 static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, const float* x, int64_t n,
                         const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
-                        int64_t workspace_bytes, float* out_w, float* out_z0, double* out_stats, void* stream_) {
+                        int64_t workspace_bytes, float* out_w, float* out_z0, float* out_rho0, double* out_stats, void* stream_,
+                        bool uha) {
   int rc = check_desc(desc);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_stats)
+  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || (uha && !out_rho0) || !out_stats)
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
   if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   CallPlan p;
   TrajArgs ta;
-  if ((rc = chain_call_begin(*desc, lay, PLAN_REVERSE, seeds, n, params, n_params, target_consts, n_target, workspace,
-                             workspace_bytes, out_w, out_z0, stream, p, ta)) != CMCD_OK) return rc;
-  snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_traj_kernel");
-  if ((rc = reverse_launch(p.d, p.w, ta, x, stream)) != CMCD_OK) return rc;
+  if ((rc = chain_call_begin(*desc, lay, uha ? PLAN_REVERSE_UHA : PLAN_REVERSE, seeds, n, params, n_params, target_consts, n_target,
+                             workspace, workspace_bytes, out_w, out_z0, stream, p, ta)) != CMCD_OK) return rc;
+  snprintf(g_kernel_name, sizeof(g_kernel_name), uha ? "reverse_uha_kernel" : "reverse_traj_kernel");
+  rc = uha ? reverse_uha_launch(p.d, p.w, ta, x, out_rho0, stream) : reverse_launch(p.d, p.w, ta, x, stream);
+  if (rc != CMCD_OK) return rc;
   return chain_call_end(ta, out_stats, stream);
 }
 
@@ -630,7 +642,17 @@ int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* lay, const int3
                        void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, double* out_stats,
                        void* stream_) {
   return reverse_impl(desc, lay, seeds, x, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_w,
-                      out_z0, out_stats, stream_);
+                      out_z0, nullptr, out_stats, stream_, false);
+}
+
+int64_t cmcd_reverse_uha_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_REVERSE_UHA); }
+
+int cmcd_bound_reverse_uha(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, const float* x, int64_t n,
+                           const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                           void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, float* out_rho0,
+                           double* out_stats, void* stream_) {
+  return reverse_impl(desc, lay, seeds, x, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_w,
+                      out_z0, out_rho0, out_stats, stream_, true);
 }
 
 int64_t cmcd_segment_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_SEGMENT); }

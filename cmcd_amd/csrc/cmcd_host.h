@@ -1,6 +1,6 @@
 // Host-side seams between cmcd_api.hip (the C ABI: validation, workspace plan, kernel selection) and cmcd_kernels.hip (the prep,
-// trajectory and merge kernels with their launchers), cmcd_reverse.hip, cmcd_segment.hip, cmcd_segment_uha.hip, cmcd_resample.hip and cmcd_sinkhorn.hip,
-// plus the two host helpers every entry point shares (al4, check_many_gmm).  cmcd_reverse.hip, cmcd_segment[_uha].hip, cmcd_grad.hip,
+// trajectory and merge kernels with their launchers), cmcd_reverse[_uha].hip, cmcd_segment[_uha].hip, cmcd_resample.hip and cmcd_sinkhorn.hip,
+// plus the two host helpers every entry point shares (al4, check_many_gmm).  cmcd_reverse[_uha].hip, cmcd_segment[_uha].hip, cmcd_grad.hip,
 // cmcd_mfvi.hip and cmcd_hais.hip include it through cmcd_tile.h, which holds the wave-per-tile pieces they share.  The seams of
 // the translation units that do not include it (the coop, lgcp, uha, bptt and opt files) are in cmcd_common.h, which the stored
 // counter figures are hashed over (bench.py: kernel_sources_sha).
@@ -74,6 +74,14 @@ int segment_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, in
 bool segment_uha_available(const cmcd_desc& d, int T);
 int segment_uha_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, int32_t k0, int32_t k1, float* z, float* rho,
                        float* wpath, uint32_t* key, float* lg, hipStream_t stream);
+
+// cmcd_reverse_uha.hip: the reverse-time chain of MCD_CAIS_UHA_sn (target draws x[n][dim] through the backward momentum kernels and
+// the inverted leap-frogs), one wave per 16-particle tile.  ta.out_loss receives w, ta.out_z the end state z_0, rho0 the end
+// momentum, ta.partials one statistics record per tile over l := w.  The instances and the launch rule of segment_uha_launch; none
+// for the other modes and lgcp.
+bool reverse_uha_available(const cmcd_desc& d, int T);
+int reverse_uha_launch(const cmcd_desc& d, const WsLayout& w, const TrajArgs& ta, const float* x, float* rho0,
+                       hipStream_t stream);
 
 // cmcd_ldvi.hip: LDVI (MCD_U_a-lp-sn / MCD_U_a-lp, include/cmcd_hip.h: cmcd_ldvi_bound_grad), one wave per 16-particle tile.
 // `d` is the effective descriptor whose tables launch_prep left in ws (use_net: CMCD_MODE_CAIS_UHA_SN on the geffner net;

@@ -6,6 +6,7 @@
 // Who includes it and what it takes:
 //   cmcd_reverse.hip, cmcd_segment.hip  tile_eval_net, tile_split, tile_chain_step, the two butterflies, tile_pick, tile_launch
 //   cmcd_segment_uha.hip  tile_split, tile_normal, tile_chain_step, tile_stats_record (network and launch: its own, below)
+//   cmcd_reverse_uha.hip  the same four (network and launch: its own, below)
 //   cmcd_hais.hip    hais_traj_kernel: tile_split, tile_normal, tile_chain_step, tile_stats_record; both kernels:
 //                    tile_stage_many_gmm; tile_pick_plain
 //   cmcd_mfvi.hip    tile_pick_plain (mfvi_kernel itself stays on inline copies, below)
@@ -25,6 +26,9 @@
 //     kernel also has a launch of its own (W1 has 2 D input rows: one more D * HP block of LDS than tile_launch sizes for) and an
 //     instance table of its own (uha_pick's: geffner on 5 neuron tiles as well); tests/test_gpu_smc_uha.py's forward-call test
 //     fails when its copy drifts.
+//   reverse_uha_kernel (cmcd_reverse_uha.hip) holds the third copy of the pair, as rev_pre_z / rev_eval_rho (copied from
+//     seg_pre_z / seg_eval_rho), with a launch and an instance table that repeat segment_uha_launch's and segment_uha_pick's;
+//     tests/test_gpu_reverse_uha.py's parity cases (all five widths and dds) fail when its copy drifts.
 //   reverse_traj_kernel and segment_traj_kernel keep inline the LDS staging, q's constants and log q, grad log q with the clips,
 //     the z_0 draw, the two ends of a step and the head of the statistics record: as helpers each of them compiled to other code
 //     (another register allocation over the whole kernel, other scratch sizes on the funnel geffner instances), for reasons that

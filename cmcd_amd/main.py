@@ -275,15 +275,20 @@ def main(config):
     say("Importance weights behind ln Z: ESS %.1f (+- %.1f) of %d samples per group (%.1f %%)." % (
         ess["ess"], ess["ess_std"], config.n_samples, 100.0 * ess["ess_frac"]))
     # The other half of the diagnostics (no analogue in the reference): exact target draws through the backward kernels.
+    # (MCD_CAIS_UHA_sn: the chain carries a momentum, cmcd_amd.reverse_uha; same line, same diagnostics on w)
     reverse = (config.compute_eubo and sample_from_target_fn is not None and rank == 0 and
-               config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn"))
+               config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn"))
     if reverse:
         from .model_handler import exact_target_draws
+        if config.boundmode == "MCD_CAIS_UHA_sn":
+            from . import reverse_uha as rev
+        else:
+            rev = mcdbm
         x_tgt = torch.from_numpy(exact_target_draws(config.model, sample_from_target_fn, 3, n, dim)).to(device)   # (seeds 1, 2: the W2 block)
 
         def say_reverse(p, forward_elbo, forward_ln_Z, prefix=""):
-            w, _, _ = mcdbm.bound_reverse(eval_seeds, x_tgt, p, unflatten, params_fixed, log_prob_model,
-                                          eps_schedule=config.eps_schedule, grad_clipping=config.grad_clipping)
+            w = rev.bound_reverse(eval_seeds, x_tgt, p, unflatten, params_fixed, log_prob_model,
+                                  eps_schedule=config.eps_schedule, grad_clipping=config.grad_clipping)[0]
             r = utils.log_reverse_diagnostics(w.view(config.n_input_dist_seeds, config.n_samples), log_prefix=prefix)
             say("Reverse chain%s: EUBO %.2f, reverse ln Z %.2f, reverse ESS %.1f (+- %.1f) of %d (%.1f %%); ln Z bracket "
                 "[ELBO %.2f, EUBO %.2f], forward ln Z %.2f." % (

@@ -1,0 +1,64 @@
+"""The reverse-time chain of 2nd-order CMCD (`MCD_CAIS_UHA_sn`): `mcdboundingmachine.bound_reverse` for the mode it refuses.
+
+`bound_reverse` is ONE call of libcmcd_hip.so (cmcd_bound_reverse_uha, csrc/cmcd_reverse_uha.hip): exact target draws `x[n, dim]`
+get a fresh momentum and are pushed through the backward momentum kernels and the inverted leap-frogs of the trained sampler, with
+the noise of `seeds[n]`.  w is the functional `bound_forward` returns as -loss in this mode, on a path drawn from
+p(z_K) N(rho_K) prod B_i: mean(w) is the EUBO (with the forward call's ELBO a bracket of ln Z), exp(-w) are the importance weights
+of the reverse estimate of 1 / Z (`utils.log_reverse_diagnostics`, `resample.importance_stats` on w).  Nothing here reads a device
+value back to the host, so the call can be captured into a graph.  The reference has no counterpart; the arithmetic is written out
+in include/cmcd_hip.h and restated in float64 NumPy in tests/reverse_uha_restatement.py.  No CPU fallback.
+
+Not here: a reverse chain for LDVI and the UHA boundmode, lgcp, a cooperative kernel form, sharding."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from . import mcdboundingmachine as mcdbm
+
+__all__ = ["bound_reverse", "compute_reverse_bound"]
+
+MODE = "MCD_CAIS_UHA_sn"
+
+
+def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """`x[n, dim]`, draws from the target, through the reverse-time chain of `MCD_CAIS_UHA_sn` with the noise of `seeds[n]`.
+    Returns (w[N] f32, z0[N, dim] f32, rho0[N, dim] f32, stats[5] f64), all device tensors, enqueued asynchronously on the current
+    stream; the statistics are taken over l := w.  A non-finite row of x gives w = +inf (its z0 / rho0 rows are meaningless).
+    gmm / funnel / many_gmm only (NotImplementedError otherwise; the overdamped modes: `mcdboundingmachine.bound_reverse`).
+    eps_schedule / grad_clipping are accepted for the signature and ignored, as by the forward call of this mode."""
+    plan = mcdbm._plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    seeds, n = mcdbm._inputs(seeds, params_flat)
+    device = params_flat.device
+    dim = params_fixed[0]
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
+        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, dim):
+        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {dim}]")
+    L = _lib.lib()
+    here = mcdbm._stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    dev_index, stream, capturing = here
+    nbytes = mcdbm._nbytes(plan, "cmcd_reverse_uha_workspace_bytes", n)
+    if nbytes <= 0:
+        raise NotImplementedError(_lib.last_error() or "no 2nd-order reverse-chain kernel for this configuration")
+    ws = mcdbm._workspace(dev_index, device, stream, capturing, nbytes, "rev_uha")
+    mcdbm._prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
+    consts = log_prob.consts_on(device)
+    w, z0, stats = mcdbm._outputs(n, dim, device)
+    rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
+    _lib.check(L.cmcd_bound_reverse_uha(
+        C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
+        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(), stats.data_ptr(), stream))
+    return w, z0, rho0, stats
+
+
+def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E[w] >= ln Z, the upper half of the bracket whose lower half is
+    -compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
+    w, z0, _, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                    eps_schedule=eps_schedule, grad_clipping=grad_clipping)
+    return (stats[1] / w.numel()).to(torch.float32), (w, z0)

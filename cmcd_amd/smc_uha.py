@@ -13,8 +13,8 @@ one.  Segments compose bit for bit.  `resample_stage` moves z AND rho with the s
 captured into a graph.  The reference has no counterpart; the arithmetic is restated in float64 NumPy in
 tests/smc_uha_restatement.py.  No CPU fallback.
 
-Not here: segments for LDVI and the UHA boundmode, a reverse-time chain for the momentum modes, lgcp, the cooperative kernel forms,
-sharding."""
+Not here: segments for LDVI and the UHA boundmode, lgcp, the cooperative kernel forms, sharding.  (The reverse-time chain of this
+mode: cmcd_amd.reverse_uha.)"""
 import ctypes as C
 
 import torch

@@ -186,8 +186,8 @@ int cmcd_bound_forward_prepared(const cmcd_desc* desc, const cmcd_layout* lay,
  * meaningless): the EUBO of such a batch is +inf, never NaN.
  * Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward; workspace of cmcd_reverse_workspace_bytes (0 where
  * the call is unsupported).  One kernel form (one wave per 16-particle tile) for the overdamped modes on gmm, funnel (dim 10)
- * and many_gmm with the nets cmcd_bound_forward's wave-per-tile kernel is built for; MCD_CAIS_UHA_sn, lgcp and other widths:
- * CMCD_ERR_UNSUPPORTED. */
+ * and many_gmm with the nets cmcd_bound_forward's wave-per-tile kernel is built for; lgcp and other widths:
+ * CMCD_ERR_UNSUPPORTED, and so is MCD_CAIS_UHA_sn here: its reverse chain carries a momentum and is cmcd_bound_reverse_uha, below. */
 int64_t cmcd_reverse_workspace_bytes(const cmcd_desc* desc, int64_t n);
 int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* layout,
                        const int32_t* seeds, const float* x, int64_t n,
@@ -272,7 +272,7 @@ int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* layout, int32_t
  * where the call is unsupported).  Every call runs the prep launch.  One kernel form (one wave per 16-particle tile) on gmm,
  * funnel (dim 10) and many_gmm with the nets of the forward call's wave-per-tile 2nd-order kernel (dds 64; geffner on 2 / 4 /
  * 5 / 9 neuron tiles); the overdamped modes (they have cmcd_bound_segment), lgcp and other widths: CMCD_ERR_UNSUPPORTED.
- * No cooperative form, no reverse-time chain, no LDVI / UHA-boundmode segments. */
+ * No cooperative form, no LDVI / UHA-boundmode segments.  (The reverse-time chain of this mode: cmcd_bound_reverse_uha.) */
 int64_t cmcd_segment_uha_workspace_bytes(const cmcd_desc* desc, int64_t n);
 int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* layout, int32_t k0, int32_t k1,
                            const int32_t* seeds /* k0 == 0; else nullable */, int64_t n,
@@ -281,6 +281,56 @@ int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* layout, int
                            void* workspace, int64_t workspace_bytes,
                            float* z_inout /*[n*dim]*/, float* rho_inout /*[n*dim]*/, float* wpath_inout /*[n]*/,
                            uint32_t* key_inout /*[n*2]*/, float* out_lg /*[n]*/, double* out_stats /*[5]*/, void* stream);
+
+/* ---- The reverse-time chain of MCD_CAIS_UHA_sn (2nd-order CMCD): draws from the TARGET, a fresh momentum, and then the backward
+ * momentum kernels and the INVERTED leap-frogs of the sampler; cmcd_bound_reverse for the mode it refuses.  The Python mirror is
+ * cmcd_amd.reverse_uha, the float64 restatement tests/reverse_uha_restatement.py.  No analogue in the reference; the arithmetic
+ * is its forward chain's (mcd_under_lp_a_cais.py:41-113, mcdboundingmachine.py:126-179) walked the other way.  Schedules (cos^2,
+ * always), the clip of grad log p at 1e2 (always), gamma, the network s([z; rho], i) and q are those of cmcd_bound_forward for
+ * the same (desc, layout, params) in mode CMCD_MODE_CAIS_UHA_SN — the same prep tables.  With eta_i = gamma eps_i,
+ * sigma_i = sqrt(2 eta_i) and gU(z, b) = -(b clip(grad log p(z), +-1e2) + (1 - b) grad log q(z)), particle p runs
+ *   z_K = x_p;  rho_K = normal(R);  w = log p(z_K) + log N(rho_K; 0, I)
+ *   for i = K-1 .. 0:
+ *             rho'' = rho_{i+1} + eps_i gU(z_{i+1}, beta_i) / 2        (the leap-frog of bridge i, inverted: undo the second
+ *             z_i   = z_{i+1} - eps_i rho''                              half-kick, the drift, then the first half-kick)
+ *             rho'  = rho'' + eps_i gU(z_i, beta_i) / 2
+ *             m_b   = rho' (1 - eta_i) + 2 eta_i s([z_i; rho'], i)      (backward kernel: z_i, the SAME index i)
+ *             rho_i = m_b + sigma_i xi_r,  r = K-1-i
+ *             m_f   = rho_i (1 - eta_i) - 2 eta_i s([z_i; rho_i], i)
+ *             w    += log N(rho_i; m_b, sigma_i) - log N(rho'; m_f, sigma_i)
+ *   w -= log q(z_0) + log N(rho_0; 0, I)
+ * so w is the functional cmcd_bound_forward returns as -loss in this mode, on a path drawn from p(z_K) N(rho_K) prod B_i.  The
+ * leap-frog is a volume-preserving bijection: no Jacobian term.  E[w] >= ln Z (the EUBO: with the forward call's ELBO it
+ * brackets ln Z), and exp(-w) are the importance weights of the reverse estimate of 1 / Z.  The densities are evaluated at the
+ * z_i the inverted leap-frog produces; whether a float32 forward leap-frog from (z_i, rho') lands on (z_{i+1}, rho_{i+1})
+ * again does not enter w.
+ * Key chain: the forward call's for this mode without its first draw.  (_, B) = split(PRNGKey(seed));  C = first(split(B));
+ * (R, G') = split(C);  rho_K = normal(R, (dim,)) — the key the forward chain spends on rho_0;  gen_0 = second(split(G'));
+ * reverse step r: (G, H) = split(gen), xi_r = normal(G, (dim,)), gen = second(split(H)).
+ *   x[n*dim] float32 [device], seeds[n] int32 [device]  ->  out_w[n], out_z0[n*dim] = z_0, out_rho0[n*dim] = rho_0
+ *   [device, float32], out_stats[5] [device, float64] = the statistics of cmcd_bound_forward over l := w:
+ *   EUBO = out_stats[1] / n;  reverse ln Z = -(out_stats[3] + log out_stats[4] - log n).
+ * A particle whose x row holds a non-finite entry, or whose w comes out NaN, gets w = +inf (weight 0; its z_0 and rho_0 rows
+ * are meaningless): the EUBO of such a batch is +inf, never NaN; the other particles of its tile keep their bits.
+ * The kernel is ONE rotated loop m = K .. 0 with a single site that evaluates (log p, grad log p, grad log q) at z_m: for
+ * m < K it closes the inverse leap-frog of bridge m, and the two network evaluations (same z_m, same row m: the z part of the
+ * first layer is formed once) and both densities follow; for m > 0 it opens bridge m - 1; at m == K it gives log p(z_K).
+ * K + 1 target evaluations and 2 K network evaluations, the forward kernel's count.
+ * Null seeds, x or output pointer, n < 1: CMCD_ERR_BAD_ARG; a short or misaligned workspace: CMCD_ERR_WORKSPACE.
+ * Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward; workspace of cmcd_reverse_uha_workspace_bytes
+ * (= cmcd_workspace_bytes; 0 where the call is unsupported).  Every call runs the prep launch (there is no prepared-table
+ * form).  One kernel form (one wave per 16-particle tile) on gmm, funnel (dim 10) and many_gmm with the nets of the forward
+ * call's wave-per-tile 2nd-order kernel (dds 64; geffner on 2 / 4 / 5 / 9 neuron tiles); the overdamped modes (they have
+ * cmcd_bound_reverse), lgcp and other widths: CMCD_ERR_UNSUPPORTED, decided on the host before any device work.
+ * No cooperative form, no reverse chain for LDVI or the UHA boundmode. */
+int64_t cmcd_reverse_uha_workspace_bytes(const cmcd_desc* desc, int64_t n);
+int cmcd_bound_reverse_uha(const cmcd_desc* desc, const cmcd_layout* layout,
+                           const int32_t* seeds, const float* x, int64_t n,
+                           const float* params, int64_t n_params,
+                           const float* target_consts, int64_t n_target,
+                           void* workspace, int64_t workspace_bytes,
+                           float* out_w /*[n]*/, float* out_z0 /*[n*dim]*/, float* out_rho0 /*[n*dim]*/,
+                           double* out_stats /*[5]*/, void* stream);
 
 /* (Measurement and diagnostic hooks — kernel-time events, the PRNG capture of the parity tests, the probes' switches — are NOT
  * part of this boundary: they are declared in include/cmcd_hip_diag.h and compiled out of the library by

@@ -121,8 +121,12 @@ else:
 x_tgt = None
 res_sampler = res[2] if len(res) > 2 else None
 if len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and \
-        cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn"):
+        cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn"):
     from cmcd_amd.model_handler import exact_target_draws
+    if cfg.boundmode == "MCD_CAIS_UHA_sn":      # the chain carries a momentum: its own call, same diagnostics on w
+        from cmcd_amd import reverse_uha as rev
+    else:
+        rev = mcdbm
     x_tgt = torch.from_numpy(exact_target_draws(cfg.model, res[2], 3, cfg.n_samples * cfg.n_input_dist_seeds, dim)).cuda()
 
 
@@ -135,8 +139,8 @@ def evaluate(p, tag):
     print("%s: ESS %.1f (+- %.1f) of %d samples per group (%.1f %%)" % (tag, ess["ess"], ess["ess_std"], cfg.n_samples,
                                                                      100.0 * ess["ess_frac"]))
     if x_tgt is not None:      # exact target draws through the backward kernels: the upper half of the ln Z bracket
-        w, _, _ = mcdbm.bound_reverse(eval_seeds, x_tgt, p, unflatten, fixed, log_prob_model, eps_schedule=cfg.eps_schedule,
-                                      grad_clipping=cfg.grad_clipping)
+        w = rev.bound_reverse(eval_seeds, x_tgt, p, unflatten, fixed, log_prob_model, eps_schedule=cfg.eps_schedule,
+                              grad_clipping=cfg.grad_clipping)[0]
         r = utils.log_reverse_diagnostics(w.view(cfg.n_input_dist_seeds, cfg.n_samples))
         print("%s: EUBO %.4f   reverse ln Z %.4f   reverse ESS %.1f (+- %.1f) of %d (%.1f %%)   ln Z bracket [%.4f, %.4f]" % (
             tag, r["eubo"], r["reverse_ln_Z"], r["reverse_ess"], r["reverse_ess_std"], cfg.n_samples,
