@@ -129,6 +129,12 @@ def lib():
         L.cmcd_hais_bound_grad.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HaisLayout), C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmcd_hais_lgcp_workspace_bytes.restype = C.c_int64
+        L.cmcd_hais_lgcp_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+        L.cmcd_hais_lgcp_bound_grad.restype = C.c_int
+        L.cmcd_hais_lgcp_bound_grad.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HaisLayout), C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmcd_ldvi_workspace_bytes.restype = C.c_int64
         L.cmcd_ldvi_workspace_bytes.argtypes = [C.POINTER(Desc), C.c_int32, C.c_int64, C.c_int32]
         L.cmcd_ldvi_bound_grad.restype = C.c_int

@@ -37,6 +37,9 @@
 // per-tile partial {d mean[D], d logdiag[D], d md[D], d eps, d eta, d beta[K]} goes to a slot of its own with plain stores;
 // hais_reduce_kernel (one workgroup) sums the tiles in a fixed order and carries d beta through the interpolation and the
 // normalised cumulative sum into mgridref_y.  No float atomics: repeated calls return the same bits.
+//
+// lgcp (d = 1600) does not fit this mapping (a particle's state in registers): cmcd_hais_lgcp.hip runs the same arithmetic as one
+// launch per target evaluation, behind cmcd_hais_lgcp_bound_grad; the entry points here keep refusing it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -487,7 +490,7 @@ extern "C" {
 int64_t cmcd_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int32_t with_grad) {
   if (!hais_shape_ok(nbridges, lfsteps, n) || dim < 1) return 0;
   if (target == CMCD_TARGET_LGCP) {
-    fail_msg(CMCD_ERR_UNSUPPORTED, "UHA on lgcp is not implemented (no Hamiltonian AIS launch sequence for d = 1600)");
+    fail_msg(CMCD_ERR_UNSUPPORTED, "UHA on lgcp is not served by this entry point: use cmcd_hais_lgcp_bound_grad (cmcd_hais_lgcp.hip)");
     return 0;
   }
   if (!tile_pick_plain<HaisTraj>(target, dim)) {
@@ -506,7 +509,7 @@ int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t 
   if (nbridges < 1 || lfsteps < 1) return fail_msg(CMCD_ERR_BAD_ARG, "nbridges and lfsteps must be >= 1");
   if (n < 1 || n > (int64_t)1 << 31 || dim < 1) return fail_msg(CMCD_ERR_BAD_ARG, "n or dim out of range");
   if (target == CMCD_TARGET_LGCP)
-    return fail_msg(CMCD_ERR_UNSUPPORTED, "UHA on lgcp is not implemented (no Hamiltonian AIS launch sequence for d = 1600)");
+    return fail_msg(CMCD_ERR_UNSUPPORTED, "UHA on lgcp is not served by this entry point: use cmcd_hais_lgcp_bound_grad (cmcd_hais_lgcp.hip)");
   if (!tile_pick_plain<HaisTraj>(target, dim))
     return fail_msg(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS kernel instance for this (target, dim)");
   if (!hais_shape_ok(nbridges, lfsteps, n))

@@ -5,7 +5,8 @@
 `initialize` is `boundingmachine.initialize` (the reference's parameter tree: `vd`, `eps`, `eta`, `md`, `mgridref_y`, the two
 grids); `compute_bound` / `grad_and_loss` have the signatures `opt.run` and `utils.sample` expect, with
 `params_fixed = (dim, nbridges, lfsteps)`.  `nbridges = 0` is the mean-field bound and goes to `boundingmachine`.  There is no
-CPU fallback; lgcp has no kernel (NotImplementedError)."""
+CPU fallback; lgcp (d = 1600) runs through `cmcd_amd.hais_lgcp`, a launch sequence with entry points of its own, and is refused here
+(NotImplementedError)."""
 import torch
 
 from . import _lib

@@ -7,7 +7,7 @@
 
 Flag names, defaults and the `--config.x value` / `--config.x=value` / `--noconfig.x` forms follow
 /root/reference/src/configs/base.py:77-155 (ml_collections + absl).  Left out: W&B, plotting, the inference-gym rows of the lr table.  `UHA` (Hamiltonian AIS, the reference's default
-boundmode) runs through cmcd_amd.hais on one GPU; modes outside it, the overdamped family and 2nd-order CMCD (`MCD_CAIS_UHA_sn`)
+boundmode) runs through cmcd_amd.hais (lgcp: cmcd_amd.hais_lgcp) on one GPU; modes outside it, the overdamped family and 2nd-order CMCD (`MCD_CAIS_UHA_sn`)
 raise NotImplementedError exactly like the library.  Under torchrun the particles of every iteration are sharded over the
 ranks (parallel.make_sharded_grad_and_loss)."""
 import os
@@ -202,9 +202,12 @@ def main(config):
     vdparams_init = {k: v.detach().cpu().clone() for k, v in unflatten(params_flat)[0]["vd"].items()}
 
     if config.boundmode == "UHA":                                          # main.py:115-136
-        # Hamiltonian AIS (cmcd_amd.hais).  The reference writes `trainable = "eta"`, a str, and its `trainable + ("eps",)` raises
+        # Hamiltonian AIS (cmcd_amd.hais; lgcp: cmcd_amd.hais_lgcp).  The reference writes `trainable = "eta"`, a str, and its `trainable + ("eps",)` raises
         # TypeError with its own default flags; the tuple below is what it means.
-        from . import hais
+        if config.model == "lgcp":      # d = 1600: the launch sequence of cmcd_amd.hais_lgcp, same interface
+            from . import hais_lgcp as hais
+        else:
+            from . import hais
         if world > 1:
             raise NotImplementedError("boundmode UHA runs on one GPU: its particles are not sharded over ranks")
         trainable = ("eta",)

@@ -427,8 +427,8 @@ int cmcd_mfvi_bound_grad(int32_t target, int32_t dim, int64_t off_vd_mean, int64
  * call and the gradient call return the same loss bits, repeated calls the same gradient bits (per-tile slots summed in a
  * fixed order, no floating-point atomics).  A gradient call keeps (nbridges L + 1) + (2 nbridges + 1) rows of n dim floats in the
  * workspace.  Ownership, stream, no-host-sync and capture rules as cmcd_bound_forward.
- * Targets: gmm, many_gmm (dim 2), funnel (dim 10); lgcp and every other (target, dim): CMCD_ERR_UNSUPPORTED, and 0 from the
- * size query.  nbridges <= 4096, ngrid <= 1024, eta < 1. */
+ * Targets: gmm, many_gmm (dim 2), funnel (dim 10); lgcp (it has entry points of its own, cmcd_hais_lgcp_bound_grad below) and
+ * every other (target, dim): CMCD_ERR_UNSUPPORTED, and 0 from the size query.  nbridges <= 4096, ngrid <= 1024, eta < 1. */
 typedef struct cmcd_hais_layout {          /* offsets (in floats) of the leaves inside params_flat */
   int64_t vd_mean, vd_logdiag;             /* [dim] each                                      */
   int64_t eps, eta;                        /* scalars                                         */
@@ -444,6 +444,28 @@ int cmcd_hais_bound_grad(int32_t target, int32_t dim, int32_t nbridges, int32_t 
                          const float* target_consts, int64_t n_target, float omega,
                          void* workspace, int64_t workspace_bytes,
                          float* out_loss, float* out_z, double* out_stats, float* grad /* nullable: forward only */, void* stream);
+
+/* ---- UHA on lgcp (dim = 1600): the arithmetic of the UHA block above, unchanged (key chain, refresh, opening half kick,
+ * L - 1 full kicks, closing half kick, weight term, nbridges L + 1 target evaluations, no clip, eps the scalar leaf, betas from
+ * mgridref_y), on the target log p(z) = counts . z - a sum e^z - 1/2 (z - mu0)^T K^-1 (z - mu0) + lognorm, as a launch sequence
+ * (cmcd_amd/csrc/cmcd_hais_lgcp.hip): one launch per target evaluation, the product with K^-1 on the matrix cores and the whole
+ * leap-frog step in its epilogue; the reverse sweep is again one launch and one product per evaluation.
+ * target_consts = {Kinv[dim, dim], counts[dim], mu0, a, lognorm} (cmcd_amd.lgcp.lgcp_constants), 16-byte aligned; n_target must be
+ * dim * dim + dim + 3.  layout, seeds, params, omega, out_loss / out_z / out_stats and grad as cmcd_hais_bound_grad: grad (nullable:
+ * forward only) [n_params], overwritten: omega * sum_n d loss_n / d {vd.mean, vd.logdiag, eps, eta, md, mgridref_y}, zeros
+ * elsewhere.  The forward call and the gradient call return the same loss and z bits, repeated calls the same gradient bits
+ * (slots summed in a fixed order, no floating-point atomics).  Every launch goes on `stream`; no host synchronisation, no
+ * allocation, capturable.  Workspace per particle: 5 rows of dim floats, 2 nbridges + 2 key words and 100 slots; a gradient call
+ * additionally keeps 2 (nbridges L + 1) + 2 nbridges + 1 rows of n dim floats (the position and its product with K^-1 of every
+ * evaluation, the refreshed momentum of every bridge, the momentum between the bridges) and 8 rows of sweep state.
+ * dim = 1600 only; every other dim: CMCD_ERR_UNSUPPORTED, and 0 from the size query (with the error text set).
+ * nbridges <= 4096, nbridges * lfsteps <= 2^24, n <= 2^20 (CMCD_ERR_UNSUPPORTED above), ngrid <= 1024, eta < 1. */
+int64_t cmcd_hais_lgcp_workspace_bytes(int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int32_t with_grad);
+int cmcd_hais_lgcp_bound_grad(int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* layout,
+                              const int32_t* seeds, int64_t n, const float* params, int64_t n_params,
+                              const float* target_consts, int64_t n_target, float omega,
+                              void* workspace, int64_t workspace_bytes,
+                              float* out_loss, float* out_z, double* out_stats, float* grad /* nullable: forward only */, void* stream);
 
 /* ---- LDVI: config.boundmode = "MCD_U_a-lp-sn" (use_net = 1) and its network-free sibling "MCD_U_a-lp" (use_net = 0),
  * /root/reference/src/mcd_under_lp_a.py:6-87 reached through mcd_utils.py:83-120 from mcdboundingmachine.py:126-179; bound and

@@ -81,7 +81,10 @@ vdparams_init = {k: v.detach().cpu().clone() for k, v in unflatten(flat)[0]["vd"
 # 2. the annealed machine: Hamiltonian AIS (boundmode UHA, cmcd_amd.hais), LDVI (MCD_U_a-lp[-sn], cmcd_amd.ldvi) or one of the MCD modes
 LDVI = cfg.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp")
 if cfg.boundmode == "UHA":
-    from cmcd_amd import hais
+    if cfg.model == "lgcp":      # d = 1600: the launch sequence of cmcd_amd.hais_lgcp, same interface
+        from cmcd_amd import hais_lgcp as hais
+    else:
+        from cmcd_amd import hais
     if WORLD > 1:
         raise NotImplementedError("boundmode UHA runs on one GPU: its particles are not sharded over ranks")
     trainable = ("eta",)
