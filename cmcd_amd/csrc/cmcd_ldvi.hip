@@ -24,9 +24,9 @@
 // network; without a network: CMCD_MODE_ULA, schedule tables and target constants only).
 //
 // What a gradient call keeps, all [.][n][D] float32: z_0..z_K | rho_0..rho_K | rho'_0..rho'_{K-1} | (rho_i - m_b,i)_{i<K}.
-// Launches of a gradient call: prep, ldvi_traj_kernel, finalize, [ldvi_net_grad_kernel], ldvi_sweep_kernel, ldvi_reduce_kernel,
-// then cmcd_grad.hip's particle-independent tails (d eps and d mgridref_y from the per-bridge tables; the embedding table, b1 and
-// W1[2 d:] from the per-bridge sums S / S2).  Every partial goes to a slot of its own with plain stores and is summed in a fixed
+// Launches of a gradient call: prep, ldvi_traj_kernel, ldvi_zero_kernel, [ldvi_net_grad_kernel], ldvi_sweep_kernel,
+// ldvi_reduce_kernel, then cmcd_grad.hip's particle-independent tails (d eps and d mgridref_y from the per-bridge tables; the
+// embedding table, b1 and W1[2 d:] from the per-bridge sums S / S2), finalize.  Every partial goes to a slot of its own with plain stores and is summed in a fixed
 // order: no float atomics, repeated calls return the same bits.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -788,6 +788,16 @@ __global__ __launch_bounds__(256) void ldvi_reduce_kernel(LdviReduceArgs a) {
   }
 }
 
+// grad[n_grad] and gtab[n_gtab] start from zero.  A launch, not two hipMemsetAsync: captured into a graph those become memset
+// nodes, and from the second replay on a gradient call replayed behind other work of its stream returned garbage in the
+// entries the zeroed part of gtab feeds (d eps, the last embedding row, b1, W1[2 d:]); kernel nodes replay in order.
+__global__ __launch_bounds__(256) void ldvi_zero_kernel(float* grad, int64_t n_grad, float* gtab, int64_t n_gtab) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_grad + n_gtab; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < n_grad) grad[i] = 0.f;
+    else gtab[i - n_grad] = 0.f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------
@@ -879,8 +889,11 @@ int ldvi_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, b
   }
   if (!grad) return hipGetLastError() == hipSuccess ? CMCD_OK : fail(CMCD_ERR_HIP, "LDVI launch failed%s");
 
-  CMCD_HIP_CHECK(hipMemsetAsync(grad, 0, sizeof(float) * n_params, stream));
-  CMCD_HIP_CHECK(hipMemsetAsync(gws + g.gtab, 0, sizeof(float) * g.gtab_floats, stream));
+  {
+    const int64_t zeros = n_params + g.gtab_floats, blocks = (zeros + 255) / 256;
+    hipLaunchKernelGGL(ldvi_zero_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, grad, n_params,
+                       gws + g.gtab, g.gtab_floats);
+  }
   if (use_net) {
     ldvi_fn item = ldvi_item_fn(d, T);
     if (!item) return fail(CMCD_ERR_UNSUPPORTED, "no LDVI network-gradient instance for this (dim, width=%s%lld)", "", HP);

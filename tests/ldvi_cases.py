@@ -15,6 +15,25 @@ Shapes, the smallest at which each mechanism can go wrong:
   funnel              d = 10, emb 48 (68 wide: 5 tiles), K = 4, n = 17
   many-floor          many_gmm, K = 8, under a q wide enough that some end points are floored; seeds from 1 .. 64 by the band guard
   nonet               `MCD_U_a-lp` on gmm, n = 33
+Past the edges of those ten (the item kernel runs min(K x tiles, 512) one-wave workgroups, workgroup b walks the items b, b + 512,
+.. into one slab; the forward kernel takes 1 wave per workgroup up to 1024 tiles, 4 up to 8192, 8 beyond):
+  gmm-slabs           K = 40 (gmm-k40's parameters), n = 208: 13 tiles x 40 = 520 items, slabs 0 .. 7 take two items (the second
+                      one of another bridge AND another tile), 504 take one
+  gmm-slabs-k33       K = 33, n = 257: 17 tiles (the last with one particle) x 33 = 561 items, no multiple of the tile count; the
+                      one-particle tile is the second item of three slabs
+  funnel-slabs        d = 10 on 5 neuron tiles, K = 64, n = 129: 9 tiles (the last with one particle) x 64 = 576 items
+  gmm-w29 / w44 / w64 emb 29 / 40 / 60, n = 17: the 4-tile instances at 33 wide (one unit in tile 3, tile 4 all padding), 44 wide (a
+                      whole padded tile) and 64 wide (exact fit)
+  many-w64            many_gmm, emb 60, K = 8: the 4-tile instances on the third target; seeds from 1 .. 40 by the band guard
+  funnel-w65 / w80    the funnel's parameters with emb 45 / 60: 5 tiles with one unit in the last; exact fit
+  funnel-n1/n16/n65   the funnel case at one lane, one full tile, a second sweep workgroup with one live wave
+  many-n33            many_gmm, emb 20, K = 8 at the default sigma: the gradient away from the floor regime; band guard on 1 .. 40
+  funnel-nonet,       `MCD_U_a-lp` on the funnel (K = 4, n = 17) and on many_gmm (K = 8, band guard on 1 .. 40): the two
+  many-nonet          network-free (trajectory, sweep) instances besides gmm's
+  gmm-nw4             K = 1, n = 16 400: 1025 tiles -> 4 waves per forward workgroup, 257 workgroups, the last with one live wave;
+                      1025 items: one slab of three, 511 of two
+  gmm-nw8             K = 1, n = 131 088: 8193 tiles -> 8 waves per workgroup, 1025 workgroups, the last with one live wave; 16 to
+                      17 items per slab
 """
 import functools
 import json
@@ -38,14 +57,31 @@ BAND = 500.0        # no evaluation's log p this close to the floor: float32 mov
                     # on the CPU: the float32 restatement's log p stays within BAND / 10 of the float64 one on every kept seed)
 
 _GMM = dict(config="gmm_n300_k8", over={}, mode="MCD_U_a-lp-sn")
+_FUNNEL = dict(config="funnel_n300_k64", over=dict(nbridges=4, init_eps=0.05, init_gamma=4.0), mode="MCD_U_a-lp-sn", n=17)
+# many_gmm at ordinary parameters (the configuration's own sigma): seeds from 1 .. `scan` by the band guard
+_MANY = dict(config="many_gmm_n2000_k256_dds", mode="MCD_U_a-lp-sn", n=None, scan=40,
+             over=dict(nn_arch="geffner", emb_dim=20, nbridges=8, init_eps=0.05, init_gamma=2.0))
+SCAN = 64           # the seeds 1 .. SCAN a band-guarded case selects from, unless the case says `scan`
 CASES = {
     **{f"gmm-n{n}": dict(_GMM, n=n) for n in (1, 16, 17, 33, 65)},
     "gmm-k1": dict(_GMM, over=dict(nbridges=1), n=17),
     "gmm-k40": dict(_GMM, over=dict(nbridges=40, init_eps=0.02), n=17),
-    "funnel": dict(config="funnel_n300_k64", over=dict(nbridges=4, init_eps=0.05, init_gamma=4.0), mode="MCD_U_a-lp-sn", n=17),
+    "funnel": dict(_FUNNEL),
     "many-floor": dict(config="many_gmm_n2000_k256_dds", mode="MCD_U_a-lp-sn", n=None,
                        over=dict(nn_arch="geffner", emb_dim=20, nbridges=8, init_eps=0.2, init_gamma=2.0, init_sigma=100.0)),
     "nonet": dict(_GMM, mode="MCD_U_a-lp", n=33),
+    "gmm-slabs": dict(_GMM, over=dict(nbridges=40, init_eps=0.02), n=208),
+    "gmm-slabs-k33": dict(_GMM, over=dict(nbridges=33), n=257),
+    "funnel-slabs": dict(_FUNNEL, over=dict(nbridges=64, init_eps=0.01, init_gamma=4.0), n=129),
+    **{cid: dict(_GMM, over=dict(emb_dim=e), n=17) for cid, e in (("gmm-w29", 29), ("gmm-w44", 40), ("gmm-w64", 60))},
+    "many-w64": dict(_MANY, over=dict(_MANY["over"], emb_dim=60)),
+    **{f"funnel-w{20 + e}": dict(_FUNNEL, over=dict(_FUNNEL["over"], emb_dim=e)) for e in (45, 60)},
+    **{f"funnel-n{n}": dict(_FUNNEL, n=n) for n in (1, 16, 65)},
+    "many-n33": dict(_MANY),
+    "funnel-nonet": dict(_FUNNEL, mode="MCD_U_a-lp"),
+    "many-nonet": dict(_MANY, mode="MCD_U_a-lp"),
+    "gmm-nw4": dict(_GMM, over=dict(nbridges=1), n=16400),
+    "gmm-nw8": dict(_GMM, over=dict(nbridges=1), n=131088),
 }
 SHARED = "gmm-n33"   # the case the bit-identity, shard, subset and training tests run on
 
@@ -67,12 +103,13 @@ def params_of(case_id):
 
 
 @functools.lru_cache(maxsize=None)
-def floor_scan():
-    """many-floor on seeds 1 .. 64 -> (seeds, losses, log p before the floor at the K + 1 evaluations [K + 1, 64])."""
-    p, (dim, K, _, _), model = params_of("many-floor")
-    seeds = np.arange(1, 65, dtype=np.int32)
+def floor_scan(case_id="many-floor"):
+    """A band-guarded case on the seeds 1 .. scan it selects from (64 unless the case says otherwise)
+    -> (seeds, losses, log p before the floor at the K + 1 evaluations [K + 1, scan])."""
+    p, (dim, K, mode, _), model = params_of(case_id)
+    seeds = np.arange(1, CASES[case_id].get("scan", SCAN) + 1, dtype=np.int32)
     trace = {}
-    l, _ = lr.forward(seeds, p, dim, K, model, trace=trace)
+    l, _ = lr.forward(seeds, p, dim, K, model, use_sn=mode == "MCD_U_a-lp-sn", trace=trace)
     return seeds, l, np.stack(trace["lp"])
 
 
@@ -81,7 +118,7 @@ def seeds_of(case_id):
     n = CASES[case_id]["n"]
     if n is not None:
         return np.arange(1, n + 1, dtype=np.int32)
-    seeds, _, lp = floor_scan()
+    seeds, _, lp = floor_scan(case_id)
     keep = (np.abs(lp - FLOOR) > BAND).all(0)     # the band guard: no evaluation that float32 could take across the floor
     return seeds[keep]
 

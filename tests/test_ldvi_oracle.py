@@ -198,6 +198,167 @@ def test_floor_case_claims():
     assert np.abs(np.stack(trace["lp"]) - lp[:, m]).max() <= lc.BAND / 10
 
 
+# ------------------------------------------------------------------------------------------ the cases past the first ten
+MAX_SLABS = 512      # kLdviMaxSlabs of cmcd_amd/csrc/cmcd_ldvi.hip: the item kernel's workgroups = slabs of partials
+
+# id: (tiles, items, {items per slab: slabs})
+SLAB_CLAIMS = {
+    "gmm-slabs": (13, 520, {2: 8, 1: 504}),
+    "gmm-slabs-k33": (17, 561, {2: 49, 1: 463}),
+    "funnel-slabs": (9, 576, {2: 64, 1: 448}),
+    "gmm-nw4": (1025, 1025, {3: 1, 2: 511}),
+    "gmm-nw8": (8193, 8193, {17: 1, 16: 511}),
+}
+# id: (width, its own tile count, the instance it runs on)
+WIDTH_CLAIMS = {
+    "gmm-w29": (33, 3, 4), "gmm-w44": (44, 3, 4), "gmm-w64": (64, 4, 4), "many-w64": (64, 4, 4),
+    "funnel-w65": (65, 5, 5), "funnel-w80": (80, 5, 5), "funnel-slabs": (68, 5, 5), "funnel-n65": (68, 5, 5),
+    "gmm-slabs": (24, 2, 2), "many-n33": (24, 2, 2),
+}
+# id: (waves per forward workgroup, forward workgroups, live waves of the last one)
+WAVE_CLAIMS = {"gmm-slabs": (1, 13, 1), "gmm-nw4": (4, 257, 1), "gmm-nw8": (8, 1025, 1)}
+NEW_CASES = ("gmm-slabs", "gmm-slabs-k33", "funnel-slabs", "gmm-w29", "gmm-w44", "gmm-w64", "many-w64", "funnel-w65", "funnel-w80",
+             "funnel-n1", "funnel-n16", "funnel-n65", "many-n33", "funnel-nonet", "many-nonet", "gmm-nw4", "gmm-nw8")
+EARLIER_CASES = ("funnel", "gmm-k1", "gmm-k40", "gmm-n1", "gmm-n16", "gmm-n17", "gmm-n33", "gmm-n65", "many-floor", "nonet")
+
+
+def _tiles(case_id):
+    return (len(lc.seeds_of(case_id)) + 15) // 16
+
+
+def _slab_walk(items):
+    """-> (nslabs, the items each workgroup walks: b, b + nslabs, ..)."""
+    nslabs = min(items, MAX_SLABS)
+    return nslabs, [list(range(b, items, nslabs)) for b in range(nslabs)]
+
+
+def _instance(dim, T):
+    """The neuron tiles of the instance a width of T tiles runs on (cmcd_api.hip: hidden_width; cmcd_ldvi.hip: ldvi_traj_pick)."""
+    padded = 2 if T <= 2 else (4 if T <= 4 else (5 if T <= 5 else None))      # hidden_width's rounding
+    return padded if padded in {2: (2, 4), 10: (5,)}[dim] else None         # the instances ldvi_traj_pick has for this dimension
+
+
+def _nw(tiles):
+    return 1 if tiles <= 1024 else (4 if tiles <= 8192 else 8)     # ldvi_launch
+
+
+def test_the_table_is_the_ten_earlier_cases_and_the_seventeen_new_ones():
+    assert sorted(lc.CASES) == sorted(NEW_CASES + EARLIER_CASES) and len(NEW_CASES) == 17
+    # the largest item count of the earlier ten is 80: every workgroup of theirs handles one item
+    assert max(_tiles(c) * lc.params_of(c)[1][1] for c in EARLIER_CASES) == 80
+    expect_n = {"gmm-slabs": 208, "gmm-slabs-k33": 257, "funnel-slabs": 129, "gmm-w29": 17, "gmm-w44": 17, "gmm-w64": 17,
+                "funnel-w65": 17, "funnel-w80": 17, "funnel-n1": 1, "funnel-n16": 16, "funnel-n65": 65, "funnel-nonet": 17,
+                "gmm-nw4": 16400, "gmm-nw8": 131088}
+    for cid, n in expect_n.items():
+        assert np.array_equal(lc.seeds_of(cid), np.arange(1, n + 1)), cid
+    expect_k = {"gmm-slabs": 40, "gmm-slabs-k33": 33, "funnel-slabs": 64, "many-w64": 8, "funnel-w65": 4, "funnel-w80": 4,
+                "funnel-n1": 4, "funnel-n16": 4, "funnel-n65": 4, "many-n33": 8, "funnel-nonet": 4, "many-nonet": 8, "gmm-nw4": 1,
+                "gmm-nw8": 1, "gmm-w29": 8, "gmm-w44": 8, "gmm-w64": 8}
+    for cid, K in expect_k.items():
+        assert lc.params_of(cid)[1][1] == K, cid
+    # gmm-slabs and gmm-k40 are the same parameters (the in-between call of the GPU test runs both)
+    assert torch.equal(lc.build("gmm-slabs")["params_flat"], lc.build("gmm-k40")["params_flat"])
+    # the funnel's n- and width-cases are the funnel case's parameters but for the width
+    for cid in ("funnel-n1", "funnel-n16", "funnel-n65"):
+        assert torch.equal(lc.build(cid)["params_flat"], lc.build("funnel")["params_flat"])
+    for cid in ("funnel", "funnel-w65", "funnel-w80", "funnel-nonet"):
+        p = lc.params_of(cid)[0]
+        assert float(p["eps"]) == np.float32(0.05) and float(p["gamma"]) == 4.0, cid
+    for cid in ("many-w64", "many-n33", "many-nonet"):
+        p = lc.params_of(cid)[0]
+        assert float(p["eps"]) == np.float32(0.05) and float(p["gamma"]) == 2.0, cid
+        assert np.allclose(np.exp(p["vd"]["logdiag"]).mean(), 60.0, rtol=0.3)      # the configuration's sigma, not many-floor's 100
+
+
+@pytest.mark.parametrize("case_id", sorted(SLAB_CLAIMS))
+def test_slab_walk_claims(case_id):
+    tiles, items, per_slab = SLAB_CLAIMS[case_id]
+    K = lc.params_of(case_id)[1][1]
+    assert _tiles(case_id) == tiles and K * tiles == items
+    nslabs, walk = _slab_walk(items)
+    assert nslabs == MAX_SLABS < items and sorted(sum(walk, [])) == list(range(items))
+    count = {}
+    for w in walk:
+        count[len(w)] = count.get(len(w), 0) + 1
+    assert count == per_slab
+    n = len(lc.seeds_of(case_id))
+    split = [[(item // tiles, item % tiles) for item in w] for w in walk]      # (bridge, tile) of the item kernel
+    if case_id == "gmm-slabs":
+        # both the bridge and the tile change inside every walk of two: 512 = 39 x 13 + 5
+        assert all(a[0] != b[0] and a[1] != b[1] for a, b in (s for s in split if len(s) == 2))
+    if case_id in ("gmm-slabs-k33", "funnel-slabs"):
+        # the last tile holds one particle, and it is the second item of some slabs and the only item of others
+        assert n % 16 == 1 and MAX_SLABS % tiles != 0
+        second = [s for s in split if len(s) == 2 and s[1][1] == tiles - 1]
+        assert len(second) == {"gmm-slabs-k33": 3, "funnel-slabs": 8}[case_id]
+        assert any(len(s) == 1 and s[0][1] == tiles - 1 for s in split)
+    if case_id.startswith("gmm-nw"):
+        assert K == 1 and all(b == 0 for s in split for b, _ in s)
+
+
+@pytest.mark.parametrize("case_id", sorted(WIDTH_CLAIMS))
+def test_width_claims(case_id):
+    width, T, inst = WIDTH_CLAIMS[case_id]
+    dim, K, _, spec = lc.build(case_id)["params_fixed"]
+    assert 2 * dim + spec.emb_dim == width and (width + 15) // 16 == T and _instance(dim, T) == inst
+    assert spec.rho_dim == dim and spec.arch == "geffner"
+    pad = 16 * inst - width
+    assert pad == {"gmm-w29": 31, "gmm-w44": 20, "gmm-w64": 0, "many-w64": 0, "funnel-w65": 15, "funnel-w80": 0}.get(case_id, pad)
+    if case_id == "gmm-w29":
+        assert width - 32 == 1            # one unit in the third tile, the fourth all padding
+    if case_id == "gmm-w44":
+        assert T == 3 and inst == 4       # a whole padded tile
+    if case_id == "funnel-w65":
+        assert width - 64 == 1            # one unit in the fifth tile
+
+
+def test_network_free_claims():
+    for cid, model, dim, K in (("funnel-nonet", "funnel", 10, 4), ("many-nonet", "many_gmm", 2, 8)):
+        b = lc.build(cid)
+        assert b["params_fixed"] == (dim, K, "MCD_U_a-lp", None) and b["cfg"]["model"] == model
+        assert b["unflatten"].offset("sn", "emb") == -1 and b["unflatten"].offset("gamma") >= 0
+
+
+@pytest.mark.parametrize("case_id", sorted(WAVE_CLAIMS))
+def test_forward_wave_claims(case_id):
+    nw, groups, live = WAVE_CLAIMS[case_id]
+    tiles = _tiles(case_id)
+    assert _nw(tiles) == nw and (tiles + nw - 1) // nw == groups and tiles - (groups - 1) * nw == live
+    if nw > 1:
+        assert _nw(tiles - 1) < nw        # the smallest tile count of this rule, hence the smallest n
+        assert len(lc.seeds_of(case_id)) == 16 * (tiles - 1) + 16
+
+
+def test_sweep_workgroup_claims():
+    """Four tiles per workgroup of the sweep: funnel-n65 opens a second one with one live wave; n = 1 and 16 are one tile."""
+    assert _tiles("funnel-n1") == 1 and _tiles("funnel-n16") == 1 and 16 % 16 == 0
+    assert _tiles("funnel-n65") == 5 and (5 + 3) // 4 == 2 and 5 - 4 == 1 and 65 % 16 == 1
+
+
+@pytest.mark.parametrize("case_id", ["many-w64", "many-n33", "many-nonet"])
+def test_band_guard_of_the_ordinary_many_gmm_cases(case_id):
+    """Seeds from 1 .. 40 by the band guard: what is kept (all 40 here: three tiles), that a kept floored particle sits far past
+    the floor, and that float32 takes no kept evaluation across it."""
+    seeds, l_all, lp = lc.floor_scan(case_id)
+    assert np.array_equal(seeds, np.arange(1, 41))
+    keep = lc.seeds_of(case_id)
+    m = np.isin(seeds, keep)
+    assert np.array_equal(m, (np.abs(lp - lc.FLOOR) > lc.BAND).all(0))
+    assert len(keep) == 40 and len(keep) >= 17
+    l, _, _ = lc.reference(case_id)
+    floored = np.isinf(l)
+    assert np.array_equal(floored, lp[-1, m] <= lc.FLOOR) and int(floored.sum()) == 1 and (l[floored] > 0).all()
+    assert (lp[-1, m][floored] < lc.FLOOR - lc.BAND).all()
+    # away from the floor regime: many-floor floors at least 4 of its 64
+    assert int(np.isfinite(l).sum()) == 39
+    p, (dim, K, mode, _), model = lc.params_of(case_id)
+    trace = {}
+    lr.forward(keep, p, dim, K, model, use_sn=mode == "MCD_U_a-lp-sn", trace=trace, dtype=torch.float32)
+    lp32 = np.stack(trace["lp"])
+    assert np.array_equal(lp32 <= lc.FLOOR, lp[:, m] <= lc.FLOOR)
+    assert np.abs(lp32 - lp[:, m]).max() <= lc.BAND / 10
+
+
 def test_float32_gaps_are_the_recorded_ones():
     """tests/golden/ldvi_gaps.json (python tests/ldvi_cases.py --write) holds, per case, what float32 alone costs the restatement:
     the worst particle's loss and every gradient block over its own maximum.  The device's bar of a block is
