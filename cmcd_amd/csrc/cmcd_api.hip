@@ -241,10 +241,13 @@ static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_
 //   segment:     the forward layout again (bridges [k0, k1) from a caller-supplied state); overdamped modes, no lgcp
 //   segment-uha: the same for MCD_CAIS_UHA_sn (the state carries the momentum); that mode only, no lgcp
 //   reverse-uha: the forward layout once more (the reverse-time chain of MCD_CAIS_UHA_sn); that mode only, no lgcp
+//   reverse-ldvi: the forward layout of LDVI's effective descriptor (cmcd_ldvi_bound_grad's), no gradient part; no lgcp
+//   reverse-hais: [one statistics record per 16-particle tile] (HaisReversePlan below: UHA has no tables and no descriptor)
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
 // ------------------------------------------------------------------------------------------
-enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT, PLAN_SEGMENT_UHA, PLAN_REVERSE_UHA };
+enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT, PLAN_SEGMENT_UHA, PLAN_REVERSE_UHA,
+                PLAN_REVERSE_LDVI };
 
 struct CallPlan {
   cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
@@ -310,6 +313,13 @@ static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKin
     if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain has no lgcp kernel%s");
     if (!reverse_uha_available(d, p.w.T))
       return fail(CMCD_ERR_UNSUPPORTED, "no 2nd-order reverse-chain kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    return CMCD_OK;
+  }
+  if (kind == PLAN_REVERSE_LDVI) {   // `desc` is LDVI's effective descriptor (ldvi_desc): CMCD_MODE_CAIS_UHA_SN = with the network
+    if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain has no lgcp kernel%s");
+    if (!reverse_ldvi_available(d, p.w.T, d.mode == CMCD_MODE_CAIS_UHA_SN))
+      return fail(CMCD_ERR_UNSUPPORTED, "no LDVI reverse-chain kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    p.total = p.need = align4(p.fwd) * 4;
     return CMCD_OK;
   }
 
@@ -769,6 +779,93 @@ int cmcd_ldvi_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, int32_t 
                    stream);
   if (rc != CMCD_OK) return rc;
   launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+// ---- the reverse-time chains of the two momentum baselines (cmcd_reverse_ldvi.hip, cmcd_reverse_hais.hip)
+int64_t cmcd_reverse_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n) {
+  cmcd_desc e;
+  CallPlan p;
+  if (ldvi_desc(desc, use_net, e) != CMCD_OK || n < 1 || n > (int64_t)1 << 31) return 0;
+  if (make_plan(e, n, 0, PLAN_REVERSE_LDVI, true, p) != CMCD_OK) return 0;
+  return p.total;
+}
+
+int cmcd_bound_reverse_ldvi(const cmcd_desc* desc, const cmcd_layout* lay, int32_t use_net, const int32_t* seeds, const float* x,
+                            int64_t n, const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
+                            void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, float* out_rho0,
+                            double* out_stats, void* stream_) {
+  cmcd_desc e;
+  int rc = ldvi_desc(desc, use_net, e);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_rho0 || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  if (!layout_inside(e, *lay, n_params) || lay->gamma < 0 || lay->gamma >= n_params)
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(e.target, target_consts, n_target)) != CMCD_OK) return rc;
+  CallPlan p, q;   // the layout is this call's, the demand is the size query's (many_gmm: the largest target block)
+  if ((rc = make_plan(e, n, n_target, PLAN_REVERSE_LDVI, false, p)) != CMCD_OK) return rc;
+  if ((rc = make_plan(e, n, 0, PLAN_REVERSE_LDVI, true, q)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, q.total)) != CMCD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  launch_prep(e, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(e, *lay, n, n_params, n_target));
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_ldvi_kernel");
+  rc = reverse_ldvi_launch(e, *lay, p.w, use_net != 0, seeds, x, n, params, ws, out_w, out_z0, out_rho0, stream);
+  if (rc != CMCD_OK) return rc;
+  launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+// UHA has no descriptor and no prep tables: its plan is the refusals of cmcd_hais_workspace_bytes, in that order, and one
+// statistics record per tile.  -> CMCD_OK and the workspace floats, or the refusal with cmcd_last_error set.
+static int reverse_hais_plan(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int64_t& floats) {
+  floats = 0;
+  if (nbridges < 1 || lfsteps < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges and lfsteps must be >= 1%s");
+  if (n < 1 || n > (int64_t)1 << 31 || dim < 1) return fail(CMCD_ERR_BAD_ARG, "n or dim out of range%s");
+  if (target == CMCD_TARGET_LGCP)
+    return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain of UHA has no lgcp kernel (lgcp has no exact target draws)%s");
+  if (!reverse_hais_available(target, dim))
+    return fail(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS reverse-chain kernel instance for this (target, dim)%s");
+  if (!reverse_hais_shape_ok(nbridges, lfsteps, n))
+    return fail(CMCD_ERR_UNSUPPORTED, "nbridges above 4096 or nbridges * lfsteps above 2^24%s");
+  floats = reverse_hais_floats(n);
+  return CMCD_OK;
+}
+
+int64_t cmcd_reverse_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n) {
+  int64_t floats;
+  return reverse_hais_plan(target, dim, nbridges, lfsteps, n, floats) == CMCD_OK ? floats * 4 : 0;
+}
+
+int cmcd_bound_reverse_hais(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* lay,
+                            const int32_t* seeds, const float* x, int64_t n, const float* params, int64_t n_params,
+                            const float* target_consts, int64_t n_target, void* workspace, int64_t workspace_bytes, float* out_w,
+                            float* out_z0, float* out_rho0, double* out_stats, void* stream_) {
+  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_rho0 || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  int64_t floats;
+  int rc = reverse_hais_plan(target, dim, nbridges, lfsteps, n, floats);
+  if (rc != CMCD_OK) return rc;
+  if (lay->ngrid < 0 || lay->ngrid > 1024) return fail(CMCD_ERR_BAD_ARG, "ngrid out of range (0 .. 1024)%s");
+  auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
+  if (!(inside(lay->vd_mean, dim) && inside(lay->vd_logdiag, dim) && inside(lay->eps, 1) && inside(lay->eta, 1) &&
+        inside(lay->md, dim) && inside(lay->mgridref_y, lay->ngrid + 1) && inside(lay->gridref_x, lay->ngrid + 2) &&
+        inside(lay->target_x, nbridges)))
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  int n_mix = 0;
+  if ((rc = check_many_gmm(target, target_consts, n_target, &n_mix)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, floats * 4)) != CMCD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_hais_kernel");
+  rc = reverse_hais_launch(target, dim, nbridges, lfsteps, *lay, seeds, x, n, params, target_consts, n_mix, ws, out_w, out_z0,
+                           out_rho0, stream);
+  if (rc != CMCD_OK) return rc;
+  launch_finalize(reinterpret_cast<double*>(ws), (int32_t)((n + 15) / 16), out_stats, stream, nullptr, 0u);
   CMCD_HIP_CHECK(hipGetLastError());
   return CMCD_OK;
 }

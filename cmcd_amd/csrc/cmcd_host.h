@@ -93,6 +93,24 @@ int ldvi_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, b
                 const float* params, int64_t n_params, float* ws, float* gws, float omega, float* out_loss, float* out_z,
                 float* grad, hipStream_t stream);
 
+// cmcd_reverse_ldvi.hip: the reverse-time chain of LDVI (include/cmcd_hip.h: cmcd_bound_reverse_ldvi), one wave per 16-particle
+// tile.  `d`, `w` and the tables in ws as for ldvi_launch; out_w receives w, out_z0 / out_rho0 the state at the q end, ws +
+// w.partials one statistics record per tile over l := w.  The instances and the launch rule of ldvi_traj_kernel.
+bool reverse_ldvi_available(const cmcd_desc& d, int T, bool use_net);
+int reverse_ldvi_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, bool use_net, const int32_t* seeds,
+                        const float* x, int64_t n, const float* params, float* ws, float* out_w, float* out_z0, float* out_rho0,
+                        hipStream_t stream);
+
+// cmcd_reverse_hais.hip: the reverse-time chain of UHA (include/cmcd_hip.h: cmcd_bound_reverse_hais), the mapping, instances and
+// shape limits of hais_traj_kernel.  The workspace holds one statistics record per 16-particle tile (reverse_hais_floats floats);
+// the arguments of the launch are the entry point's, already checked.
+bool reverse_hais_available(int target, int dim);
+bool reverse_hais_shape_ok(int32_t nbridges, int32_t lfsteps, int64_t n);
+int64_t reverse_hais_floats(int64_t n);
+int reverse_hais_launch(int target, int dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout& lay, const int32_t* seeds,
+                        const float* x, int64_t n, const float* params, const float* target_consts, int n_mix, float* ws,
+                        float* out_w, float* out_z0, float* out_rho0, hipStream_t stream);
+
 // cmcd_resample.hip: importance statistics + systematic resampling, one workgroup per group of n / groups rows, one launch.
 // The group is walked in chunks of kResampleChunk rows with a float64 running sum carried between them.
 constexpr int kResampleChunk = 1024;

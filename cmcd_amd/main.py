@@ -61,7 +61,10 @@ def get_config():
     #                             its main.py always uses (main.py:148-159); only MCD_CAIS_UHA_sn reads gamma
     c.compute_w2 = True         # extra: --noconfig.compute_w2 skips the Sinkhorn W2 block of main.py:248-271 (test harness)
     c.compute_eubo = True       # extra: --noconfig.compute_eubo skips the reverse-chain diagnostics (EUBO, reverse ln Z / ESS)
-    c.smc_eval = False          # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc / smc_uha: resampling between bridges)
+    c.eubo_uha = False          # extra: --config.eubo_uha adds the reverse-chain line to boundmode UHA (cmcd_amd.reverse_hais).  Off by
+    #                             default, unlike the MCD modes: tests/test_gpu_hais.py::test_driver_runs_the_default_boundmode holds
+    #                             the default UHA command line to printing no "Reverse chain" line, and existing tests stay as they are
+    c.smc_eval = False         # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc / smc_uha: resampling between bridges)
     # fields of the reference's config this driver accepts so that its README command lines run unchanged, but whose
     # only legal value here is the default (dds nets are 64-wide, the lgcp posterior is un-whitened, 40 mixtures
     # unless n_mixes says otherwise) or that configure subsystems left out (NICE, W&B, the cluster launcher)
@@ -279,12 +282,19 @@ def main(config):
         ess["ess"], ess["ess_std"], config.n_samples, 100.0 * ess["ess_frac"]))
     # The other half of the diagnostics (no analogue in the reference): exact target draws through the backward kernels.
     # (MCD_CAIS_UHA_sn: the chain carries a momentum, cmcd_amd.reverse_uha; same line, same diagnostics on w)
+    # (LDVI: cmcd_amd.reverse_ldvi.  UHA: cmcd_amd.reverse_hais, behind --config.eubo_uha only: the default UHA command line is
+    # held by tests/test_gpu_hais.py::test_driver_runs_the_default_boundmode to print no such line)
     reverse = (config.compute_eubo and sample_from_target_fn is not None and rank == 0 and
-               config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn"))
+               (config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn",
+                                     "MCD_U_a-lp-sn", "MCD_U_a-lp") or (config.boundmode == "UHA" and config.eubo_uha)))
     if reverse:
         from .model_handler import exact_target_draws
         if config.boundmode == "MCD_CAIS_UHA_sn":
             from . import reverse_uha as rev
+        elif config.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp"):
+            from . import reverse_ldvi as rev
+        elif config.boundmode == "UHA":
+            from . import reverse_hais as rev
         else:
             rev = mcdbm
         x_tgt = torch.from_numpy(exact_target_draws(config.model, sample_from_target_fn, 3, n, dim)).to(device)   # (seeds 1, 2: the W2 block)

@@ -1,0 +1,68 @@
+"""The reverse-time chain of UHA (Hamiltonian AIS, `config.boundmode = "UHA"`): `reverse_uha.bound_reverse` for the plain bounding
+machine with `nbridges >= 1`.
+
+`bound_reverse` is ONE call of libcmcd_hip.so (cmcd_bound_reverse_hais, csrc/cmcd_reverse_hais.hip): exact target draws
+`x[n, dim]` get a fresh momentum r = exp(md) normal(R) and run the forward chain's leap-frogs backwards, the momentum refreshed
+between the bridges by the forward rule (it is reversible with respect to N(0, exp(md)^2)), with the noise of `seeds[n]`.  w is the
+functional `hais.bound_forward` returns as -loss, on that reversed path: mean(w) is the EUBO (with the forward call's ELBO a bracket
+of ln Z), exp(-w) are the importance weights of the reverse estimate of 1 / Z.  Nothing here reads a device value back to the host,
+so the call can be captured into a graph.  The reference has no counterpart; the arithmetic is written out in include/cmcd_hip.h
+and restated in float64 in tests/reverse_hais_restatement.py.  No CPU fallback.
+
+Not here: chain segments for UHA, lgcp (it has no exact draws), a cooperative kernel form, sharding."""
+import torch
+
+from . import _lib
+from . import hais
+from .mcdboundingmachine import _inputs, _outputs, _stream, _workspace
+
+__all__ = ["bound_reverse", "compute_reverse_bound"]
+
+
+def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """`x[n, dim]`, draws from the target, through the reverse-time chain of UHA with the noise of `seeds[n]`; `params_fixed` is
+    `hais.initialize`'s (dim, nbridges, lfsteps).  Returns (w[N] f32, z0[N, dim] f32, rho0[N, dim] f32, stats[5] f64), all device
+    tensors, enqueued asynchronously on the current stream; rho0 is the chain's initial momentum, the statistics are taken over
+    l := w.  A non-finite row of x (or one under many_gmm's floor of log p) gives w = +inf.  gmm / funnel / many_gmm only
+    (NotImplementedError otherwise, lgcp included); nbridges = 0 has no chain (ValueError).  eps_schedule / grad_clipping are
+    accepted for the signature and ignored: the mode has neither."""
+    dim, nbridges, lfsteps = params_fixed
+    if not hasattr(log_prob, "target_id"):
+        raise TypeError("log_prob must be a cmcd_amd.model_handler.Target (see load_model)")
+    if log_prob.dim != dim:
+        raise ValueError(f"target dim {log_prob.dim} != params_fixed dim {dim}")
+    if nbridges < 1 or lfsteps < 1:
+        raise ValueError(f"nbridges = {nbridges}, lfsteps = {lfsteps}: the reverse chain needs nbridges >= 1 and lfsteps >= 1")
+    seeds, n = _inputs(seeds, params_flat)
+    device = params_flat.device
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
+        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, dim):
+        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {dim}]")
+    L = _lib.lib()
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    dev_index, stream, capturing = here
+    nbytes = L.cmcd_reverse_hais_workspace_bytes(log_prob.target_id, dim, nbridges, lfsteps, n)
+    if nbytes <= 0:
+        raise NotImplementedError(_lib.last_error() or "no Hamiltonian AIS reverse-chain kernel for this target")
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_hais")
+    consts = log_prob.consts_on(device)
+    w, z0, stats = _outputs(n, dim, device)
+    rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
+    lay = hais._layout(unflatten)
+    _lib.check(L.cmcd_bound_reverse_hais(
+        log_prob.target_id, dim, nbridges, lfsteps, lay, seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
+        params_flat.numel(), consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
+        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(), stats.data_ptr(), stream))
+    return w, z0, rho0, stats
+
+
+def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E[w] >= ln Z, the upper half of the bracket whose lower half is
+    -hais.compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
+    w, z0, _, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                    eps_schedule=eps_schedule, grad_clipping=grad_clipping)
+    return (stats[1] / w.numel()).to(torch.float32), (w, z0)

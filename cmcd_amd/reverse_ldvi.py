@@ -1,0 +1,68 @@
+"""The reverse-time chain of LDVI (`MCD_U_a-lp-sn` and its network-free sibling `MCD_U_a-lp`): `reverse_uha.bound_reverse` for
+the two modes it refuses.
+
+`bound_reverse` is ONE call of libcmcd_hip.so (cmcd_bound_reverse_ldvi, csrc/cmcd_reverse_ldvi.hip): exact target draws `x[n, dim]`
+get a fresh momentum and are pushed through the backward momentum kernels and the inverted leap-frogs of the trained sampler, with
+the noise of `seeds[n]`.  w is the functional `ldvi.bound_forward` returns as -loss, on a path drawn from
+p(z_K) N(rho_K) prod B_i: mean(w) is the EUBO (with the forward call's ELBO a bracket of ln Z), exp(-w) are the importance weights
+of the reverse estimate of 1 / Z (`utils.log_reverse_diagnostics`, `resample.importance_stats` on w).  Against the 2nd-order chain:
+no network in the forward kernel (one evaluation per bridge), the scalar step size, no clip of grad log p; the tree's `eta` leaf is
+not read.  Nothing here reads a device value back to the host, so the call can be captured into a graph.  The reference has no
+counterpart; the arithmetic is written out in include/cmcd_hip.h and restated in float64 in tests/reverse_ldvi_restatement.py.
+No CPU fallback.
+
+Not here: chain segments for LDVI, lgcp, a cooperative kernel form, sharding."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from . import ldvi
+from .mcdboundingmachine import _inputs, _outputs, _stream, _workspace
+
+__all__ = ["bound_reverse", "compute_reverse_bound"]
+
+MODES = ldvi.MODES
+
+
+def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """`x[n, dim]`, draws from the target, through the reverse-time chain of LDVI with the noise of `seeds[n]`; `params_fixed` is
+    `ldvi.initialize`'s.  Returns (w[N] f32, z0[N, dim] f32, rho0[N, dim] f32, stats[5] f64), all device tensors, enqueued
+    asynchronously on the current stream; the statistics are taken over l := w.  A non-finite row of x (or one under many_gmm's
+    floor of log p) gives w = +inf (its z0 / rho0 rows are meaningless).  gmm / funnel / many_gmm on the geffner widths of the
+    forward call only (NotImplementedError otherwise).  eps_schedule / grad_clipping are accepted for the signature and ignored:
+    the mode has neither."""
+    desc, lay, use_net = ldvi._plan(unflatten, params_fixed, log_prob)
+    seeds, n = _inputs(seeds, params_flat)
+    device = params_flat.device
+    dim = params_fixed[0]
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
+        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, dim):
+        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {dim}]")
+    L = _lib.lib()
+    here = _stream(device)
+    if here is None:
+        with torch.cuda.device(device):
+            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
+    dev_index, stream, capturing = here
+    nbytes = L.cmcd_reverse_ldvi_workspace_bytes(C.byref(desc), use_net, n)
+    if nbytes <= 0:
+        raise NotImplementedError(_lib.last_error() or "no LDVI reverse-chain kernel for this configuration")
+    ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_ldvi")
+    consts = log_prob.consts_on(device)
+    w, z0, stats = _outputs(n, dim, device)
+    rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
+    _lib.check(L.cmcd_bound_reverse_ldvi(
+        C.byref(desc), C.byref(lay), use_net, seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
+        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(), stats.data_ptr(), stream))
+    return w, z0, rho0, stats
+
+
+def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
+    """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E[w] >= ln Z, the upper half of the bracket whose lower half is
+    -ldvi.compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
+    w, z0, _, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                    eps_schedule=eps_schedule, grad_clipping=grad_clipping)
+    return (stats[1] / w.numel()).to(torch.float32), (w, z0)

@@ -14,7 +14,7 @@ captured into a graph.  The reference has no counterpart; the arithmetic is rest
 tests/smc_uha_restatement.py.  No CPU fallback.
 
 Not here: segments for LDVI and the UHA boundmode, lgcp, the cooperative kernel forms, sharding.  (The reverse-time chain of this
-mode: cmcd_amd.reverse_uha.)"""
+mode: cmcd_amd.reverse_uha; LDVI and UHA have reverse chains too, cmcd_amd.reverse_ldvi and cmcd_amd.reverse_hais, but no segments.)"""
 import ctypes as C
 
 import torch

@@ -322,7 +322,8 @@ int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* layout, int
  * form).  One kernel form (one wave per 16-particle tile) on gmm, funnel (dim 10) and many_gmm with the nets of the forward
  * call's wave-per-tile 2nd-order kernel (dds 64; geffner on 2 / 4 / 5 / 9 neuron tiles); the overdamped modes (they have
  * cmcd_bound_reverse), lgcp and other widths: CMCD_ERR_UNSUPPORTED, decided on the host before any device work.
- * No cooperative form, no reverse chain for LDVI or the UHA boundmode. */
+ * No cooperative form.  LDVI and the UHA boundmode have reverse chains of their own: cmcd_bound_reverse_ldvi and
+ * cmcd_bound_reverse_hais, below; this call keeps refusing them. */
 int64_t cmcd_reverse_uha_workspace_bytes(const cmcd_desc* desc, int64_t n);
 int cmcd_bound_reverse_uha(const cmcd_desc* desc, const cmcd_layout* layout,
                            const int32_t* seeds, const float* x, int64_t n,
@@ -502,6 +503,71 @@ int cmcd_ldvi_bound_grad(const cmcd_desc* desc, const cmcd_layout* layout, int32
                          const float* params, int64_t n_params, const float* target_consts, int64_t n_target, float omega,
                          void* workspace, int64_t workspace_bytes,
                          float* out_loss, float* out_z, double* out_stats, float* grad /* nullable: forward only */, void* stream);
+
+/* ---- The reverse-time chain of LDVI (use_net = 1: "MCD_U_a-lp-sn", use_net = 0: "MCD_U_a-lp"): cmcd_bound_reverse_uha's chain
+ * with three differences — the forward kernel has no network, the step size is the scalar leaf eps (no cos^2 table), grad log p
+ * is not clipped.  The Python mirror is cmcd_amd.reverse_ldvi, the float64 restatement tests/reverse_ldvi_restatement.py.  No
+ * analogue in the reference; the arithmetic is the forward chain's of cmcd_ldvi_bound_grad walked the other way.  With
+ * eta = gamma eps, sigma = sqrt(2 eta), gU(z, b) = -(b grad log p(z) + (1 - b) grad log q(z)) and the betas, the network
+ * s([z; rho], i) and q of cmcd_ldvi_bound_grad for the same (desc, layout, params) (the leaf `eta` is not read), particle p runs
+ *   z_K = x_p;  rho_K = normal(R);  w = log p(z_K) + log N(rho_K; 0, I)
+ *   for i = K-1 .. 0:
+ *             rho'' = rho_{i+1} + eps gU(z_{i+1}, beta_i) / 2          (the closing half-kick undone)
+ *             z_i   = z_{i+1} - eps rho''                              (the drift undone)
+ *             rho'  = rho'' + eps gU(z_i, beta_i) / 2                  (the opening half-kick undone)
+ *             m_b   = rho' (1 - eta) [+ 2 eta s([z_i; rho'], i)]       (the network only with use_net = 1; index i)
+ *             rho_i = m_b + sigma xi_r,  r = K-1-i
+ *             m_f   = rho_i (1 - eta)                                  (no network in the forward kernel)
+ *             w    += log N(rho_i; m_b, sigma) - log N(rho'; m_f, sigma)
+ *   w -= log q(z_0) + log N(rho_0; 0, I)
+ * so w is the functional cmcd_ldvi_bound_grad returns as -loss, on a path drawn from p(z_K) N(rho_K) prod B_i: E[w] >= ln Z.
+ * Key chain: cmcd_bound_reverse_uha's (the forward chain's without its first draw).  One rotated loop m = K .. 0 with a single
+ * target-evaluation site: K + 1 target evaluations and K network evaluations.
+ *   x[n*dim], seeds[n] [device]  ->  out_w[n], out_z0[n*dim], out_rho0[n*dim] [device, float32], out_stats[5] [device, float64]
+ *   over l := w, as cmcd_bound_reverse_uha.  A particle whose x row holds a non-finite entry, whose log p(x) is under many_gmm's
+ *   floor, or whose w comes out NaN gets w = +inf (weight 0); the other particles of its tile keep their bits.
+ * desc and layout as cmcd_ldvi_bound_grad reads them.  Workspace of cmcd_reverse_ldvi_workspace_bytes (the forward part of
+ * cmcd_ldvi_workspace_bytes; 0 where the call is unsupported).  Every call runs the prep launch.  No float atomics, repeated
+ * calls return equal bits; no host read-back, capturable.  Instances exactly cmcd_ldvi_bound_grad's eight (gmm / many_gmm on 2
+ * and 4 neuron tiles, funnel dim 10 on 5, the three network-free ones); lgcp, dds and other widths: CMCD_ERR_UNSUPPORTED.
+ * Null pointer, n < 1: CMCD_ERR_BAD_ARG; a short or misaligned workspace: CMCD_ERR_WORKSPACE. */
+int64_t cmcd_reverse_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n);
+int cmcd_bound_reverse_ldvi(const cmcd_desc* desc, const cmcd_layout* layout, int32_t use_net,
+                            const int32_t* seeds, const float* x, int64_t n,
+                            const float* params, int64_t n_params,
+                            const float* target_consts, int64_t n_target,
+                            void* workspace, int64_t workspace_bytes,
+                            float* out_w /*[n]*/, float* out_z0 /*[n*dim]*/, float* out_rho0 /*[n*dim]*/,
+                            double* out_stats /*[5]*/, void* stream);
+
+/* ---- The reverse-time chain of UHA (Hamiltonian AIS, cmcd_hais_bound_grad): the forward leap-frogs run backwards; the
+ * momentum refresh rho = eta rho_prev + sqrt(1 - eta^2) s xi is reversible with respect to N(0, s^2), so its backward kernel is
+ * the refresh itself.  The Python mirror is cmcd_amd.reverse_hais, the float64 restatement tests/reverse_hais_restatement.py.
+ * With s = exp(md), L = lfsteps, gU and the betas of cmcd_hais_bound_grad, particle p runs
+ *   z_K = x_p;  r = s normal(R);  w = log p(z_K)
+ *   for i = K-1 .. 0:
+ *     w  += log N(r; 0, s)
+ *     rho = r + eps gU(z, beta_i) / 2
+ *     (L - 1) times:  z -= eps rho / s^2;  rho += eps gU(z, beta_i)
+ *     z  -= eps rho / s^2;  rho += eps gU(z, beta_i) / 2              (now (z_i, rho_i))
+ *     w  -= log N(rho; 0, s)
+ *     r   = eta rho + sqrt(1 - eta^2) s xi_r,  r = K-1-i             (the refresh, reversed)
+ *   w -= log q(z_0)
+ * i.e. the functional cmcd_hais_bound_grad returns as -loss on a path drawn from p(z_K) N(r; 0, s) prod (reversed steps).  The
+ * two densities of a bridge share their constant: w takes sum_j (rho_j^2 - r_j^2) / (2 s_j^2).  K L + 1 target evaluations: the
+ * one that ends a bridge's leap-frog opens the next one's.  Key chain and the +inf conventions as cmcd_bound_reverse_ldvi.
+ * out_rho0 receives the last r (the chain's initial momentum).  Targets gmm, many_gmm (dim 2), funnel (dim 10); lgcp (no exact
+ * draws, "lgcp" in the message) and every other (target, dim): CMCD_ERR_UNSUPPORTED, 0 from the size query.  nbridges, lfsteps
+ * < 1: CMCD_ERR_BAD_ARG; nbridges > 4096 or nbridges * lfsteps > 2^24: CMCD_ERR_UNSUPPORTED.  The workspace holds one statistics
+ * record per 16-particle tile.  One launch plus the merge; no float atomics, no host read-back, capturable. */
+int64_t cmcd_reverse_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n);
+int cmcd_bound_reverse_hais(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* layout,
+                            const int32_t* seeds, const float* x, int64_t n,
+                            const float* params, int64_t n_params,
+                            const float* target_consts, int64_t n_target,
+                            void* workspace, int64_t workspace_bytes,
+                            float* out_w /*[n]*/, float* out_z0 /*[n*dim]*/, float* out_rho0 /*[n*dim]*/,
+                            double* out_stats /*[5]*/, void* stream);
 
 /* ---- Optimiser step of the training loop (/root/reference/src/opt.py:14-35,100-116) fused into one launch:
  * g = clip(grad, +-clip); Adam moments (optax.adam: bias correction 1 - b^step, eps outside the root);

@@ -42,6 +42,9 @@ ap.add_argument("--n_samples", type=int, default=500)
 ap.add_argument("--n_input_dist_seeds", type=int, default=30)
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--smc_eval", action="store_true", help="add the SMC evaluation (resampling between bridges) to both evaluations")
+ap.add_argument("--eubo_uha", action="store_true",
+                help="boundmode UHA: add the reverse-chain line (cmcd_amd.reverse_hais); off by default, as main.py's --config.eubo_uha "
+                     "(tests/test_gpu_hais.py::test_driver_runs_the_default_boundmode holds the default UHA run to no such line)")
 ap.add_argument("--file_path", default="", help="lgcp: pines.csv (default: the bin-count fixture under tests/golden)")
 cfg = ap.parse_args()
 
@@ -124,10 +127,15 @@ else:
 x_tgt = None
 res_sampler = res[2] if len(res) > 2 else None
 if len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and \
-        cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn"):
+        (cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn") or LDVI or
+         (cfg.boundmode == "UHA" and cfg.eubo_uha)):
     from cmcd_amd.model_handler import exact_target_draws
     if cfg.boundmode == "MCD_CAIS_UHA_sn":      # the chain carries a momentum: its own call, same diagnostics on w
         from cmcd_amd import reverse_uha as rev
+    elif LDVI:
+        from cmcd_amd import reverse_ldvi as rev
+    elif cfg.boundmode == "UHA":
+        from cmcd_amd import reverse_hais as rev
     else:
         rev = mcdbm
     x_tgt = torch.from_numpy(exact_target_draws(cfg.model, res[2], 3, cfg.n_samples * cfg.n_input_dist_seeds, dim)).cuda()
