@@ -11,7 +11,8 @@ import torch
 
 from . import _lib
 from . import variationaldist as vd
-from .mcdboundingmachine import ravel_pytree, _inputs, _outputs, _stream, _workspace, _zero_notrain
+from ._call import consts_args, _inputs, on_device, _outputs, _workspace, _zero_notrain
+from .mcdboundingmachine import ravel_pytree
 
 
 def initialize(dim, vdparams=None, nbridges=0, lfsteps=1, eps=0.0, eta=0.5, mdparams=None, ngridb=32,
@@ -54,27 +55,24 @@ def _call(seeds, params_flat, unflatten, params_fixed, log_prob, want_grad, n_to
     seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return _call(seeds, params_flat, unflatten, params_fixed, log_prob, want_grad, n_total)
-    dev_index, stream, capturing = here
-    nbytes = L.cmcd_mfvi_workspace_bytes(log_prob.target_id, dim, n)
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no mean-field kernel for this target")
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "mfvi")
-    consts = log_prob.consts_on(device)
-    losses, z, stats = _outputs(n, dim, device)
-    grad = torch.empty_like(params_flat) if want_grad else None
-    _lib.check(L.cmcd_mfvi_bound_grad(
-        log_prob.target_id, dim, unflatten.offset("vd", "mean"), unflatten.offset("vd", "logdiag"),
-        seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
-        losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr() if want_grad else None, stream))
-    if want_grad:
-        _zero_notrain(grad, unflatten)      # "vd" outside `trainable` => zero
-    return grad, losses, z, stats
+
+    def launch(dev_index, stream, capturing):
+        nbytes = L.cmcd_mfvi_workspace_bytes(log_prob.target_id, dim, n)
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "mfvi",
+                        "no mean-field kernel for this target")
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        losses, z, stats = _outputs(n, dim, device)
+        grad = torch.empty_like(params_flat) if want_grad else None
+        _lib.check(L.cmcd_mfvi_bound_grad(
+            log_prob.target_id, dim, unflatten.offset("vd", "mean"), unflatten.offset("vd", "logdiag"),
+            seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
+            1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
+            losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr() if want_grad else None, stream))
+        if want_grad:
+            _zero_notrain(grad, unflatten)      # "vd" outside `trainable` => zero
+        return grad, losses, z, stats
+
+    return on_device(device, launch)
 
 
 def compute_bound(seeds, params_flat, unflatten, params_fixed, log_prob):

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from . import mcdboundingmachine as _mcdbm
-from .mcdboundingmachine import _inputs, _outputs, _stream, _workspace, _zero_notrain
+from ._call import consts_args, _inputs, on_device, _outputs, _workspace, _zero_notrain
 from .nn import ScoreNet
 
 MODES = ("MCD_U_a-lp-sn", "MCD_U_a-lp")
@@ -79,26 +79,23 @@ def _call(seeds, params_flat, unflatten, params_fixed, log_prob, want_grad, n_to
     seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return _call(seeds, params_flat, unflatten, params_fixed, log_prob, want_grad, n_total)
-    dev_index, stream, capturing = here
-    nbytes = L.cmcd_ldvi_workspace_bytes(C.byref(desc), use_net, n, int(want_grad))
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no LDVI kernel for this configuration")
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "ldvi")
-    consts = log_prob.consts_on(device)
-    losses, z, stats = _outputs(n, dim, device)
-    grad = torch.empty_like(params_flat) if want_grad else None
-    _lib.check(L.cmcd_ldvi_bound_grad(
-        C.byref(desc), C.byref(lay), use_net, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
-        losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr() if want_grad else None, stream))
-    if want_grad:
-        _zero_notrain(grad, unflatten)      # leaves outside `trainable` => zero
-    return grad, losses, z, stats
+
+    def launch(dev_index, stream, capturing):
+        nbytes = L.cmcd_ldvi_workspace_bytes(C.byref(desc), use_net, n, int(want_grad))
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "ldvi",
+                        "no LDVI kernel for this configuration")
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        losses, z, stats = _outputs(n, dim, device)
+        grad = torch.empty_like(params_flat) if want_grad else None
+        _lib.check(L.cmcd_ldvi_bound_grad(
+            C.byref(desc), C.byref(lay), use_net, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+            cptr, cnum, 1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
+            losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr() if want_grad else None, stream))
+        if want_grad:
+            _zero_notrain(grad, unflatten)      # leaves outside `trainable` => zero
+        return grad, losses, z, stats
+
+    return on_device(device, launch)
 
 
 def bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob):

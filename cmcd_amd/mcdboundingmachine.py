@@ -14,6 +14,8 @@ import torch
 
 from . import _lib
 from . import variationaldist as vd
+from ._call import (PREP_CALLS, fixed_parameters,      # noqa: F401  (these two, and _outputs, are read through this module)
+                    _fixed, _inputs, _outputs, _prepared, _workspace, _zero_notrain, check_x, consts_args, on_device)
 from .nn import ScoreNet, initialize_network
 
 _SN_MODES = ["MCD_ULA_sn", "MCD_U_e-lp-sna", "MCD_U_a-lp-sna", "MCD_CAIS_sn", "MCD_CAIS_var_sn"]
@@ -162,109 +164,14 @@ def initialize(
 
 
 # --------------------------------------------------------------------------- the HIP call
-_workspaces = {}
-_WORKSPACE_CACHE = 16    # (stream, purpose) entries kept PER DEVICE; beyond that the least recently used buffer is released
-
 # Kernel variant handed to the library in cmcd_desc.reserved: 0 = auto (library heuristic),
 # 1 = wave-per-tile kernel, 2 = CU-cooperative kernel (library picks the tile), 3 / 4 = cooperative on 16- / 8-particle
 # tiles.  For tests / benchmarking only.
 KERNEL_VARIANT = int(__import__("os").environ.get("CMCD_KERNEL_VARIANT", "0"))
 
-
-# Prepared tables (include/cmcd_hip.h: cmcd_bound_forward_prepared): what the forward workspace of (device, buffer address)
-# holds, as the key of the call that formed it.  A forward call whose key matches skips the prep launch — evaluation loops on
-# fixed parameters (the reference's opt.sample: 30 calls of loss_fn on one params_flat).
-# OPT-IN: `with fixed_parameters():` around the loop (or CMCD_PREP_CACHE=1 for the process).  Inside, the key carries the
-# parameter tensor's address AND its version counter, and the entry a weak reference to the tensor object: every in-place
-# update through torch bumps the counter, and the two places of this package that write parameters through a raw pointer (the
-# fused optimiser step, eager and graph-replayed) bump it by hand (torch.autograd.graph.increment_version).  What NO key can
-# see is a write that bypasses the counter — `params_flat.data.mul_(...)` (`.data` has a counter of its own), a raw-pointer
-# write from other code — which is why the shortcut is not the default: the caller states that the parameters are fixed.
-# Never used while a graph is being captured (a captured "no prep" would outlive the parameters).
-_prepared = {}
+# Prepared tables for the whole process, without a `with fixed_parameters():` (see _call._prepared).  Read by bound_forward
+# at call time as THIS module's attribute: benchmarks and tests assign it here.
 PREP_CACHE = __import__("os").environ.get("CMCD_PREP_CACHE", "0") == "1"
-_fixed = __import__("threading").local()
-
-
-class fixed_parameters:
-    """Context of an evaluation loop on unchanged parameters: forward calls inside may reuse the per-parameter tables the
-    previous call left in the workspace (cmcd_bound_forward_prepared).  Re-entrant, per host thread."""
-
-    def __enter__(self):
-        _fixed.depth = getattr(_fixed, "depth", 0) + 1
-        return self
-
-    def __exit__(self, *exc):
-        _fixed.depth -= 1
-        return False
-
-
-PREP_CALLS = {"prepared": 0, "full": 0}      # forward calls that skipped / ran the prep launch (tests, bench)
-
-
-def _workspace(dev_index, device, stream, capturing, nbytes, tag):
-    """Scratch buffer of one (device, HIP stream, purpose): calls enqueued on different streams of one device — from
-    one host thread or several — never share a workspace, so they may overlap on the GPU (include/cmcd_hip.h: the
-    library itself keeps nothing between calls).  Calls on the same stream are ordered and reuse the buffer.
-    `dev_index`, `stream`, `capturing` are those of `device` (see _stream)."""
-    if capturing:
-        # inside torch.cuda.graph(): the buffer must come from (and stay with) the graph's private pool, so it is neither
-        # taken from the cache nor put into it — an eager call that later runs on a recycled stream handle never sees it
-        return torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-    per_dev = _workspaces.setdefault(dev_index, {})      # one LRU per device: a busy device never evicts another's buffers
-    key = (stream, tag)
-    ws = per_dev.pop(key, None)              # re-inserted below: the dict is ordered by last use
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _prepared.pop((dev_index, ws.data_ptr()), None)      # a fresh buffer holds nobody's tables, whatever lived at its address
-    per_dev[key] = ws
-    while len(per_dev) > _WORKSPACE_CACHE:         # least recently used first: streams that died, one-off streams
-        per_dev.pop(next(iter(per_dev)))
-    return ws
-
-
-def _stream(device):
-    """-> (device index, raw handle of the device's current HIP stream, whether that stream is being captured), or None when
-    `device` is not the current device: the caller then re-enters itself under torch.cuda.device(device), so that every HIP
-    call belongs to the tensor's device (rare; the common case pays no context manager)."""
-    dev_index, current = device.index, torch._C._cuda_getDevice()
-    if dev_index is None:
-        dev_index = current                  # "cuda" is the current device
-    elif dev_index != current:
-        return None
-    return dev_index, torch._C._cuda_getCurrentRawStream(dev_index), torch._C._cuda_isCurrentStreamCapturing()
-
-
-def _inputs(seeds, params_flat):
-    """The tensor checks every entry point makes -> (seeds as a contiguous int32 tensor on params_flat's device, n)."""
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
-    device = params_flat.device
-    if not isinstance(seeds, torch.Tensor) or seeds.device != device or seeds.dtype != torch.int32 or not seeds.is_contiguous():
-        seeds = torch.as_tensor(seeds).to(device=device, dtype=torch.int32).contiguous()
-    n = seeds.numel()
-    if n < 1:
-        raise ValueError("seeds is empty")
-    return seeds, n
-
-
-def _outputs(n, dim, device):
-    """-> (losses[n] f32, z[n, dim] f32, stats[NSTATS] f64), for the library to fill."""
-    return (torch.empty(n, dtype=torch.float32, device=device), torch.empty((n, dim), dtype=torch.float32, device=device),
-            torch.empty(_lib.NSTATS, dtype=torch.float64, device=device))
-
-
-def _zero_notrain(grad, unflatten):
-    """params_notrain = stop_gradient(params_notrain) (the reference's mcdboundingmachine.py:142, boundingmachine.py:75): only
-    the leaves of params_train carry a gradient; they are the leading block of params_flat.  Where that block ends is found
-    once per Unflatten."""
-    n_train = unflatten.__dict__.get("_n_train", -1)
-    if n_train == -1:
-        n_train = unflatten._n_train = min((off for path, (off, _) in unflatten.layout.items() if path[0] == 1), default=None)
-    if n_train is not None:
-        grad[n_train:].zero_()
 
 
 def _layout(unflatten, spec):
@@ -368,46 +275,44 @@ def bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob, eps_sch
     seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return bound_forward(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    dev_index, stream, capturing = here
-    nbytes = _nbytes(plan, "cmcd_workspace_bytes", n)
-    if nbytes <= 0:
-        _lib.check(-2 if "not implemented" in _lib.last_error() or "no kernel" in _lib.last_error() else -1)
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "")
-    consts = log_prob.consts_on(device)
-    losses, z, stats = _outputs(n, params_fixed[0], device)
-    # the tables this workspace holds: formed by the previous call from exactly these inputs?  (see _prepared)
-    # `slot` names the buffer on EVERY call — in or out of fixed_parameters(), capturing or not — because every call
-    # overwrites the buffer's tables and must therefore retire whatever claim an earlier call left on it (r04 advisor:
-    # with the slot computed inside the context only, `with fixed: f(P)`; `f(Q)`; `with fixed: f(P)` ran P on Q's tables)
-    slot = (dev_index, ws.data_ptr())
-    key = None
-    if (PREP_CACHE or getattr(_fixed, "depth", 0) > 0) and not capturing:
-        key = (params_flat.data_ptr(), params_flat._version, params_flat.numel(), n, desc_b, lay_b, spec,
-               None if consts is None else (consts.data_ptr(), consts._version, consts.numel()))
-    # (key, weak references to the very tensor OBJECTS the tables were formed from): an address and a version counter alone
-    # do not identify a tensor — the caching allocator hands a freed tensor's address to the next one of the same size, whose
-    # counter starts at the same value (r04: two parameter sets of one test module collided exactly so)
-    hit = False
-    ent = _prepared.get(slot) if key is not None else None
-    if ent is not None and ent[0] == key and ent[1]() is params_flat and (consts is None or ent[2]() is consts):
-        hit = True
-    fn = L.cmcd_bound_forward_prepared if hit else L.cmcd_bound_forward
-    _prepared.pop(slot, None)            # unconditionally: this launch rewrites (or, on an error, may have rewritten) the tables
-    PREP_CALLS["prepared" if hit else "full"] += 1
-    rc = fn(
-        C.byref(desc), C.byref(lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        ws.data_ptr(), ws.numel(), losses.data_ptr(), z.data_ptr(), stats.data_ptr(), stream)
-    _lib.check(rc)
-    if key is not None:
-        _prepared[slot] = (key, weakref.ref(params_flat), weakref.ref(consts) if consts is not None else None)
-        while len(_prepared) > 64:
-            _prepared.pop(next(iter(_prepared)))
-    return losses, z, stats
+
+    def launch(dev_index, stream, capturing):
+        nbytes = _nbytes(plan, "cmcd_workspace_bytes", n)
+        if nbytes <= 0:
+            _lib.check(-2 if "not implemented" in _lib.last_error() or "no kernel" in _lib.last_error() else -1)
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "")
+        consts = log_prob.consts_on(device)
+        cptr, cnum = consts_args(consts)
+        losses, z, stats = _outputs(n, params_fixed[0], device)
+        # the tables this workspace holds: formed by the previous call from exactly these inputs?  (see _call._prepared)
+        # `slot` names the buffer on EVERY call — in or out of fixed_parameters(), capturing or not — because every call
+        # overwrites the buffer's tables and must therefore retire whatever claim an earlier call left on it (r04 advisor:
+        # with the slot computed inside the context only, `with fixed: f(P)`; `f(Q)`; `with fixed: f(P)` ran P on Q's tables)
+        slot = (dev_index, ws.data_ptr())
+        key = None
+        if (PREP_CACHE or getattr(_fixed, "depth", 0) > 0) and not capturing:
+            key = (params_flat.data_ptr(), params_flat._version, params_flat.numel(), n, desc_b, lay_b, spec,
+                   None if consts is None else (cptr, consts._version, cnum))
+        # (key, weak references to the very tensor OBJECTS the tables were formed from): an address and a version counter
+        # alone do not identify a tensor — the caching allocator hands a freed tensor's address to the next one of the same
+        # size, whose counter starts at the same value (r04: two parameter sets of one test module collided exactly so)
+        hit = False
+        ent = _prepared.get(slot) if key is not None else None
+        if ent is not None and ent[0] == key and ent[1]() is params_flat and (consts is None or ent[2]() is consts):
+            hit = True
+        fn = L.cmcd_bound_forward_prepared if hit else L.cmcd_bound_forward
+        _prepared.pop(slot, None)        # unconditionally: this launch rewrites (or, on an error, may have rewritten) the tables
+        PREP_CALLS["prepared" if hit else "full"] += 1
+        _lib.check(fn(
+            C.byref(desc), C.byref(lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
+            ws.data_ptr(), ws.numel(), losses.data_ptr(), z.data_ptr(), stats.data_ptr(), stream))
+        if key is not None:
+            _prepared[slot] = (key, weakref.ref(params_flat), weakref.ref(consts) if consts is not None else None)
+            while len(_prepared) > 64:
+                _prepared.pop(next(iter(_prepared)))
+        return losses, z, stats
+
+    return on_device(device, launch)
 
 
 def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
@@ -418,37 +323,36 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
     The reference has no such call.  Overdamped modes on gmm / funnel / many_gmm only (NotImplementedError otherwise)."""
     plan = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
     seeds, n = _inputs(seeds, params_flat)
-    device = params_flat.device
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
-    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, params_fixed[0]):
-        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {params_fixed[0]}]")
-    L = _lib.lib()
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    dev_index, stream, capturing = here
-    nbytes = _nbytes(plan, "cmcd_reverse_workspace_bytes", n)
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no reverse-chain kernel for this configuration")
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev")
-    _prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
-    consts = log_prob.consts_on(device)
-    w, z0, stats = _outputs(n, params_fixed[0], device)
-    _lib.check(L.cmcd_bound_reverse(
-        C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), stats.data_ptr(), stream))
-    return w, z0, stats
+    device, dim = params_flat.device, params_fixed[0]
+    check_x(x, n, dim, device)
+
+    def launch(dev_index, stream, capturing):
+        nbytes = _nbytes(plan, "cmcd_reverse_workspace_bytes", n)
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev",
+                        "no reverse-chain kernel for this configuration", retire=True)
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        w, z0, stats = _outputs(n, dim, device)
+        _lib.check(_lib.lib().cmcd_bound_reverse(
+            C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
+            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), stats.data_ptr(),
+            stream))
+        return w, z0, stats
+
+    return on_device(device, launch)
+
+
+def eubo_of(out):
+    """-> (EUBO = mean(w), (w, z0)) of what a `bound_reverse` of this package returned, (w, z0, [rho0,] stats): the one body
+    of every module's `compute_reverse_bound`."""
+    w, z0, stats = out[0], out[1], out[-1]
+    return (stats[1] / w.numel()).to(torch.float32), (w, z0)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
     """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E_P[w] >= ln Z, the upper half of the bracket whose lower half is
     -compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
-    w, z0, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
-                                 eps_schedule=eps_schedule, grad_clipping=grad_clipping)
-    return (stats[1] / w.numel()).to(torch.float32), (w, z0)
+    return eubo_of(bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                 eps_schedule=eps_schedule, grad_clipping=grad_clipping))
 
 
 def compute_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
@@ -493,37 +397,33 @@ def compute_log_var_grad(seeds, params_flat, unflatten, params_fixed, log_prob, 
     seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return compute_log_var_grad(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping,
-                                        n_total, stats_total)
-    dev_index, stream, capturing = here
-    desc, lay = C.byref(plan.desc), C.byref(plan.lay)
-    nbytes = _nbytes(plan, "cmcd_grad_workspace_bytes", n, _lib.sync_grad_item_override())
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no gradient kernel for this configuration")
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "grad")
-    consts = log_prob.consts_on(device)
-    cptr, cnum = (consts.data_ptr(), consts.numel()) if consts is not None else (None, 0)
-    losses, z, stats = _outputs(n, params_fixed[0], device)
-    omega = torch.empty(n, dtype=torch.float32, device=device)
-    grad = torch.empty_like(params_flat)
-    # forward on the gradient workspace: the per-call tables (and, for small batches, the trajectory) stay
-    # there for the gradient call, so the chain runs once
-    _lib.check(L.cmcd_bound_var_forward(
-        desc, lay, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        cptr, cnum, ws.data_ptr(), ws.numel(), losses.data_ptr(), z.data_ptr(), stats.data_ptr(), stream))
-    st = stats if stats_total is None else stats_total
-    if callable(st):   # multi-GPU: the caller merges the local statistics across ranks here
-        st = st(stats)
-    _lib.check(L.cmcd_vargrad_weights(losses.data_ptr(), st.data_ptr(), n, n if n_total is None else int(n_total),
-                                      omega.data_ptr(), stream))
-    _lib.check(L.cmcd_bound_var_grad_kept(
-        desc, lay, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        cptr, cnum, omega.data_ptr(), ws.data_ptr(), ws.numel(), grad.data_ptr(), stream))
-    _zero_notrain(grad, unflatten)
-    return grad, (losses, z)
+
+    def launch(dev_index, stream, capturing):
+        desc, lay = C.byref(plan.desc), C.byref(plan.lay)
+        nbytes = _nbytes(plan, "cmcd_grad_workspace_bytes", n, _lib.sync_grad_item_override())
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "grad",
+                        "no gradient kernel for this configuration")
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        losses, z, stats = _outputs(n, params_fixed[0], device)
+        omega = torch.empty(n, dtype=torch.float32, device=device)
+        grad = torch.empty_like(params_flat)
+        # forward on the gradient workspace: the per-call tables (and, for small batches, the trajectory) stay
+        # there for the gradient call, so the chain runs once
+        _lib.check(L.cmcd_bound_var_forward(
+            desc, lay, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+            cptr, cnum, ws.data_ptr(), ws.numel(), losses.data_ptr(), z.data_ptr(), stats.data_ptr(), stream))
+        st = stats if stats_total is None else stats_total
+        if callable(st):   # multi-GPU: the caller merges the local statistics across ranks here
+            st = st(stats)
+        _lib.check(L.cmcd_vargrad_weights(losses.data_ptr(), st.data_ptr(), n, n if n_total is None else int(n_total),
+                                          omega.data_ptr(), stream))
+        _lib.check(L.cmcd_bound_var_grad_kept(
+            desc, lay, seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+            cptr, cnum, omega.data_ptr(), ws.data_ptr(), ws.numel(), grad.data_ptr(), stream))
+        _zero_notrain(grad, unflatten)
+        return grad, (losses, z)
+
+    return on_device(device, launch)
 
 
 def compute_bound_grad(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None,
@@ -543,28 +443,24 @@ def compute_bound_grad(seeds, params_flat, unflatten, params_fixed, log_prob, ep
     seeds, n = _inputs(seeds, params_flat)
     L = _lib.lib()
     device = params_flat.device
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return compute_bound_grad(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping,
-                                      n_total, return_stats)
-    dev_index, stream, capturing = here
-    nbytes = _nbytes(plan, "cmcd_bound_grad_workspace_bytes", n, _lib.sync_grad_item_override())
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no gradient kernel for this configuration")
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "bptt")
-    consts = log_prob.consts_on(device)
-    losses, z, stats = _outputs(n, params_fixed[0], device)
-    grad = torch.empty_like(params_flat)
-    _lib.check(L.cmcd_bound_grad(
-        C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
-        losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr(), stream))
-    _zero_notrain(grad, unflatten)
-    if return_stats:
-        return grad, (losses, z), stats
-    return grad, (losses, z)
+
+    def launch(dev_index, stream, capturing):
+        nbytes = _nbytes(plan, "cmcd_bound_grad_workspace_bytes", n, _lib.sync_grad_item_override())
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "bptt",
+                        "no gradient kernel for this configuration")
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        losses, z, stats = _outputs(n, params_fixed[0], device)
+        grad = torch.empty_like(params_flat)
+        _lib.check(L.cmcd_bound_grad(
+            C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
+            cptr, cnum, 1.0 / float(n if n_total is None else n_total), ws.data_ptr(), ws.numel(),
+            losses.data_ptr(), z.data_ptr(), stats.data_ptr(), grad.data_ptr(), stream))
+        _zero_notrain(grad, unflatten)
+        if return_stats:
+            return grad, (losses, z), stats
+        return grad, (losses, z)
+
+    return on_device(device, launch)
 
 
 def make_grad_and_loss(boundmode, eps_schedule=None, grad_clipping=False):

@@ -104,7 +104,7 @@ class _FusedClipAdam(_ClipAdam):
 
 def _bump(*tensors):
     """The fused step writes its parameters through raw pointers: tell torch (the version counter is what the forward's
-    prepared-table cache keys on, cmcd_amd/mcdboundingmachine.py:_prepared)."""
+    prepared-table cache keys on, cmcd_amd/_call.py:_prepared)."""
     for t in tensors:
         if t is not None:
             torch.autograd.graph.increment_version(t)

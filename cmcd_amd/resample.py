@@ -11,7 +11,7 @@ and every group is weighted, measured and resampled on its own.  No CPU fallback
 import torch
 
 from . import _lib
-from .mcdboundingmachine import _stream, _workspace
+from ._call import on_device, _workspace
 
 CHUNK = 1024             # rows a workgroup scans per step (csrc/cmcd_host.h: kResampleChunk); groups longer than this carry a running sum
 MAX_GROUP = 1 << 20      # rows per group the library accepts
@@ -35,22 +35,21 @@ def launch(losses, z=None, groups=1, seed=0, index=True, copy=True):
         if n < 1 or z.numel() % n != 0 or z.numel() < n:
             raise ValueError("z must hold one row per loss")
         dim = z.numel() // n
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return launch(losses, z, groups, seed, index, copy)
-    dev_index, stream, capturing = here
-    L = _lib.lib()
-    nbytes = L.cmcd_resample_workspace_bytes(n, groups)
-    ws = _workspace(dev_index, device, stream, capturing, max(nbytes, 16), "resample")
-    stats = torch.empty((max(groups, 1), _lib.NSTATS), dtype=torch.float64, device=device)
-    out_index = torch.empty(n, dtype=torch.int32, device=device) if index else None
-    out_z = torch.empty((n, dim), dtype=torch.float32, device=device) if copy else None
-    # (a size query that answered 0 refused the arguments: the call below refuses them too, with the message)
-    _lib.check(L.cmcd_resample_systematic(
-        losses.data_ptr(), z.data_ptr() if z is not None else None, n, dim, groups, int(seed) & 0xFFFFFFFF, ws.data_ptr(),
-        nbytes, out_index.data_ptr() if index else None, out_z.data_ptr() if copy else None, stats.data_ptr(), stream))
-    return out_z, out_index, stats
+
+    def run(dev_index, stream, capturing):
+        L = _lib.lib()
+        nbytes = L.cmcd_resample_workspace_bytes(n, groups)
+        # (a size query that answered 0 refused the arguments: the call below refuses them too, with the message)
+        ws = _workspace(dev_index, device, stream, capturing, max(nbytes, 16), "resample")
+        stats = torch.empty((max(groups, 1), _lib.NSTATS), dtype=torch.float64, device=device)
+        out_index = torch.empty(n, dtype=torch.int32, device=device) if index else None
+        out_z = torch.empty((n, dim), dtype=torch.float32, device=device) if copy else None
+        _lib.check(L.cmcd_resample_systematic(
+            losses.data_ptr(), z.data_ptr() if z is not None else None, n, dim, groups, int(seed) & 0xFFFFFFFF, ws.data_ptr(),
+            nbytes, out_index.data_ptr() if index else None, out_z.data_ptr() if copy else None, stats.data_ptr(), stream))
+        return out_z, out_index, stats
+
+    return on_device(device, run)
 
 
 def _as_dict(stats):

@@ -14,7 +14,8 @@ import torch
 
 from . import _lib
 from . import hais
-from .mcdboundingmachine import _inputs, _outputs, _stream, _workspace
+from ._call import check_x, consts_args, _inputs, on_device, _outputs, _workspace
+from .mcdboundingmachine import eubo_of
 
 __all__ = ["bound_reverse", "compute_reverse_bound"]
 
@@ -35,34 +36,28 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
         raise ValueError(f"nbridges = {nbridges}, lfsteps = {lfsteps}: the reverse chain needs nbridges >= 1 and lfsteps >= 1")
     seeds, n = _inputs(seeds, params_flat)
     device = params_flat.device
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
-    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, dim):
-        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {dim}]")
+    check_x(x, n, dim, device)
     L = _lib.lib()
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    dev_index, stream, capturing = here
-    nbytes = L.cmcd_reverse_hais_workspace_bytes(log_prob.target_id, dim, nbridges, lfsteps, n)
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no Hamiltonian AIS reverse-chain kernel for this target")
-    ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_hais")
-    consts = log_prob.consts_on(device)
-    w, z0, stats = _outputs(n, dim, device)
-    rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
-    lay = hais._layout(unflatten)
-    _lib.check(L.cmcd_bound_reverse_hais(
-        log_prob.target_id, dim, nbridges, lfsteps, lay, seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
-        params_flat.numel(), consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(), stats.data_ptr(), stream))
-    return w, z0, rho0, stats
+
+    def launch(dev_index, stream, capturing):
+        nbytes = L.cmcd_reverse_hais_workspace_bytes(log_prob.target_id, dim, nbridges, lfsteps, n)
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_hais",
+                        "no Hamiltonian AIS reverse-chain kernel for this target")
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        w, z0, stats = _outputs(n, dim, device)
+        rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
+        lay = hais._layout(unflatten)
+        _lib.check(L.cmcd_bound_reverse_hais(
+            log_prob.target_id, dim, nbridges, lfsteps, lay, seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
+            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(),
+            stats.data_ptr(), stream))
+        return w, z0, rho0, stats
+
+    return on_device(device, launch)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
     """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E[w] >= ln Z, the upper half of the bracket whose lower half is
     -hais.compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
-    w, z0, _, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
-                                    eps_schedule=eps_schedule, grad_clipping=grad_clipping)
-    return (stats[1] / w.numel()).to(torch.float32), (w, z0)
+    return eubo_of(bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                 eps_schedule=eps_schedule, grad_clipping=grad_clipping))

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from . import mcdboundingmachine as mcdbm
+from ._call import check_x, consts_args, _inputs, on_device, _outputs, _workspace
 
 __all__ = ["bound_reverse", "compute_reverse_bound"]
 
@@ -29,37 +30,28 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
     gmm / funnel / many_gmm only (NotImplementedError otherwise; the overdamped modes: `mcdboundingmachine.bound_reverse`).
     eps_schedule / grad_clipping are accepted for the signature and ignored, as by the forward call of this mode."""
     plan = mcdbm._plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    seeds, n = mcdbm._inputs(seeds, params_flat)
-    device = params_flat.device
-    dim = params_fixed[0]
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != device:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat")
-    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (n, dim):
-        raise ValueError(f"x must be contiguous float32 of shape [n, dim] = [{n}, {dim}]")
-    L = _lib.lib()
-    here = mcdbm._stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    dev_index, stream, capturing = here
-    nbytes = mcdbm._nbytes(plan, "cmcd_reverse_uha_workspace_bytes", n)
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no 2nd-order reverse-chain kernel for this configuration")
-    ws = mcdbm._workspace(dev_index, device, stream, capturing, nbytes, "rev_uha")
-    mcdbm._prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
-    consts = log_prob.consts_on(device)
-    w, z0, stats = mcdbm._outputs(n, dim, device)
-    rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
-    _lib.check(L.cmcd_bound_reverse_uha(
-        C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(), stats.data_ptr(), stream))
-    return w, z0, rho0, stats
+    seeds, n = _inputs(seeds, params_flat)
+    device, dim = params_flat.device, params_fixed[0]
+    check_x(x, n, dim, device)
+
+    def launch(dev_index, stream, capturing):
+        nbytes = mcdbm._nbytes(plan, "cmcd_reverse_uha_workspace_bytes", n)
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_uha",
+                        "no 2nd-order reverse-chain kernel for this configuration", retire=True)
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        w, z0, stats = _outputs(n, dim, device)
+        rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
+        _lib.check(_lib.lib().cmcd_bound_reverse_uha(
+            C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
+            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(),
+            stats.data_ptr(), stream))
+        return w, z0, rho0, stats
+
+    return on_device(device, launch)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
     """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E[w] >= ln Z, the upper half of the bracket whose lower half is
     -compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
-    w, z0, _, stats = bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
-                                    eps_schedule=eps_schedule, grad_clipping=grad_clipping)
-    return (stats[1] / w.numel()).to(torch.float32), (w, z0)
+    return mcdbm.eubo_of(bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                       eps_schedule=eps_schedule, grad_clipping=grad_clipping))

@@ -10,7 +10,7 @@ tests/test_gpu_sinkhorn.py.  No CPU fallback."""
 import torch
 
 from . import _lib
-from .mcdboundingmachine import _stream, _workspace
+from ._call import on_device, _workspace
 
 ROWS = 64                # rows of K per workgroup (csrc/cmcd_host.h: kSinkhornRows)
 MAX_N = 8192             # points per cloud the library accepts
@@ -49,35 +49,34 @@ def w2_batched(x, y, a=None, b=None, reg=0.01, num_iter_max=10000, stop_thr=1e-1
     num_iter_max, poll_every = int(num_iter_max), int(poll_every)
     if G < 1:
         raise ValueError("no problems")
-    here = _stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return w2_batched(x, y, a, b, reg, num_iter_max, stop_thr, poll_every, max_workspace_bytes)
-    dev_index, stream, capturing = here
-    if capturing and poll_every:
-        raise RuntimeError("w2_batched under graph capture needs poll_every=0 (polling reads the done words back)")
-    L = _lib.lib()
-    per = L.cmcd_sinkhorn_workspace_bytes(n, dim, 1)
-    # (a size query that answered 0 refused the shape: the setup call below refuses it too, with the message)
-    chunk = min(G, MAX_GROUPS, max(1, int(max_workspace_bytes) // per)) if per > 0 else min(G, MAX_GROUPS)
-    out = torch.empty((G, 4), dtype=torch.float64, device=device)
-    flags = torch.empty(chunk, dtype=torch.int32, device=device) if poll_every else None
-    for g0 in range(0, G, chunk):
-        g = min(chunk, G - g0)
-        nbytes = L.cmcd_sinkhorn_workspace_bytes(n, dim, g)
-        ws = _workspace(dev_index, device, stream, capturing, max(nbytes, 16), "sinkhorn")
-        xs, ys = x[g0:g0 + g], y[g0:g0 + g]
-        _lib.check(L.cmcd_sinkhorn_setup(
-            xs.data_ptr(), ys.data_ptr(), a[g0:g0 + g].data_ptr() if a is not None else None,
-            b[g0:g0 + g].data_ptr() if b is not None else None, n, dim, g, float(reg), ws.data_ptr(), nbytes, stream))
-        it = 0
-        while it < num_iter_max:
-            count = min(poll_every, num_iter_max - it) if poll_every else num_iter_max - it
-            _lib.check(L.cmcd_sinkhorn_iterate(n, dim, g, it, count, num_iter_max, float(stop_thr), ws.data_ptr(), nbytes,
-                                               flags.data_ptr() if poll_every else None, stream))
-            it += count
-            if poll_every and it < num_iter_max and bool(flags[:g].all()):
-                break
-        _lib.check(L.cmcd_sinkhorn_cost(xs.data_ptr(), ys.data_ptr(), n, dim, g, ws.data_ptr(), nbytes,
-                                        out[g0:g0 + g].data_ptr(), None, stream))
-    return {name: out[:, i] for i, name in enumerate(FIELDS)}
+
+    def solve(dev_index, stream, capturing):
+        if capturing and poll_every:
+            raise RuntimeError("w2_batched under graph capture needs poll_every=0 (polling reads the done words back)")
+        L = _lib.lib()
+        per = L.cmcd_sinkhorn_workspace_bytes(n, dim, 1)
+        # (a size query that answered 0 refused the shape: the setup call below refuses it too, with the message)
+        chunk = min(G, MAX_GROUPS, max(1, int(max_workspace_bytes) // per)) if per > 0 else min(G, MAX_GROUPS)
+        out = torch.empty((G, 4), dtype=torch.float64, device=device)
+        flags = torch.empty(chunk, dtype=torch.int32, device=device) if poll_every else None
+        for g0 in range(0, G, chunk):
+            g = min(chunk, G - g0)
+            nbytes = L.cmcd_sinkhorn_workspace_bytes(n, dim, g)
+            ws = _workspace(dev_index, device, stream, capturing, max(nbytes, 16), "sinkhorn")
+            xs, ys = x[g0:g0 + g], y[g0:g0 + g]
+            _lib.check(L.cmcd_sinkhorn_setup(
+                xs.data_ptr(), ys.data_ptr(), a[g0:g0 + g].data_ptr() if a is not None else None,
+                b[g0:g0 + g].data_ptr() if b is not None else None, n, dim, g, float(reg), ws.data_ptr(), nbytes, stream))
+            it = 0
+            while it < num_iter_max:
+                count = min(poll_every, num_iter_max - it) if poll_every else num_iter_max - it
+                _lib.check(L.cmcd_sinkhorn_iterate(n, dim, g, it, count, num_iter_max, float(stop_thr), ws.data_ptr(), nbytes,
+                                                   flags.data_ptr() if poll_every else None, stream))
+                it += count
+                if poll_every and it < num_iter_max and bool(flags[:g].all()):
+                    break
+            _lib.check(L.cmcd_sinkhorn_cost(xs.data_ptr(), ys.data_ptr(), n, dim, g, ws.data_ptr(), nbytes,
+                                            out[g0:g0 + g].data_ptr(), None, stream))
+        return {name: out[:, i] for i, name in enumerate(FIELDS)}
+
+    return on_device(device, solve)

@@ -15,32 +15,36 @@ import torch
 
 from . import _lib, resample
 from . import mcdboundingmachine as mcdbm
+from ._call import consts_args, _inputs, on_device, _workspace
 
 STATE_FIELDS = ("z", "wpath", "lg", "key")
 
 
-def _state_inputs(state, params_flat, dim):
-    """The checks on a state handed to a segment with k0 > 0 -> (z, wpath, key) as fresh tensors the library overwrites."""
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
-    if not isinstance(state, dict) or any(k not in state for k in ("z", "wpath", "key")):
-        raise TypeError("a segment with k0 > 0 starts from the state dict an earlier segment (or resample_stage) returned")
-    device = params_flat.device
-    for name in ("z", "wpath", "key"):
+def _state_tensors(state, device, dim, fields):
+    """The checks on the tensors of a state handed to a segment with k0 > 0 -> (*fields, n), the fields as fresh tensors the
+    library overwrites.  `fields` holds "wpath"[n] and "key"[n, 2]; every other one is a float32 matrix [n, dim]."""
+    for name in fields:
         t = state[name]
         if not isinstance(t, torch.Tensor) or t.device != device:
             raise RuntimeError(f"the CMCD hot path runs on a ROCm device only: state[{name!r}] is not a tensor on the device of "
                                "params_flat")
+    mats = [f for f in fields if f not in ("wpath", "key")]
+    both = lambda names: ", ".join(names[:-1]) + " and " + names[-1] if len(names) > 1 else names[0]
     n = state["wpath"].numel()
-    if n < 1 or state["wpath"].dtype != torch.float32 or state["z"].dtype != torch.float32 or state["key"].dtype != torch.int32:
-        raise ValueError("state: z and wpath must be float32, key int32")
-    if tuple(state["z"].shape) != (n, dim) or tuple(state["key"].shape) != (n, 2):
-        raise ValueError(f"state: z must have shape [{n}, {dim}] and key [{n}, 2]")
-    return (state["z"].detach().clone(memory_format=torch.contiguous_format),
-            state["wpath"].detach().reshape(-1).clone(memory_format=torch.contiguous_format),
-            state["key"].detach().clone(memory_format=torch.contiguous_format), n)
+    if n < 1 or any(state[f].dtype != torch.float32 for f in mats + ["wpath"]) or state["key"].dtype != torch.int32:
+        raise ValueError(f"state: {both(mats + ['wpath'])} must be float32, key int32")
+    if any(tuple(state[f].shape) != (n, dim) for f in mats) or tuple(state["key"].shape) != (n, 2):
+        raise ValueError(f"state: {both(mats)} must have shape [{n}, {dim}] and key [{n}, 2]")
+    fresh = lambda t: t.detach().clone(memory_format=torch.contiguous_format)
+    return (*(fresh(state[f].reshape(-1) if f == "wpath" else state[f]) for f in fields), n)
+
+
+def _state_inputs(state, params_flat, dim):
+    """The checks on a state handed to a segment with k0 > 0 -> (z, wpath, key, n)."""
+    _inputs(None, params_flat, seedless=True)
+    if not isinstance(state, dict) or any(k not in state for k in ("z", "wpath", "key")):
+        raise TypeError("a segment with k0 > 0 starts from the state dict an earlier segment (or resample_stage) returned")
+    return _state_tensors(state, params_flat.device, dim, ("z", "wpath", "key"))
 
 
 def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
@@ -52,34 +56,32 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     dim, k0, k1 = params_fixed[0], int(k0), int(k1)
     device = params_flat.device
     if k0 == 0:
-        seeds, n = mcdbm._inputs(state, params_flat)
+        seeds, n = _inputs(state, params_flat)
         z = torch.empty((n, dim), dtype=torch.float32, device=device)
         wpath = torch.empty(n, dtype=torch.float32, device=device)
         key = torch.empty((n, 2), dtype=torch.int32, device=device)
     else:
         seeds = None
         z, wpath, key, n = _state_inputs(state, params_flat, dim)
-    here = mcdbm._stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    dev_index, stream, capturing = here
-    L = _lib.lib()
-    nbytes = mcdbm._nbytes(plan, "cmcd_segment_workspace_bytes", n)
-    if nbytes <= 0:
-        hint = " — MCD_CAIS_UHA_sn: cmcd_amd.smc_uha (the state with momentum)" if params_fixed[2] == "MCD_CAIS_UHA_sn" else ""
-        raise NotImplementedError((_lib.last_error() or "no segment kernel for this configuration") + hint)
-    ws = mcdbm._workspace(dev_index, device, stream, capturing, nbytes, "seg")
-    mcdbm._prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
-    consts = log_prob.consts_on(device)
-    lg = torch.empty(n, dtype=torch.float32, device=device)
-    stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
-    _lib.check(L.cmcd_bound_segment(
-        C.byref(plan.desc), C.byref(plan.lay), k0, k1, seeds.data_ptr() if seeds is not None else None, n,
-        params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        ws.data_ptr(), ws.numel(), z.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(), stats.data_ptr(), stream))
-    return {"z": z, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
+
+    def launch(dev_index, stream, capturing):
+        what = "no segment kernel for this configuration"
+        nbytes = mcdbm._nbytes(plan, "cmcd_segment_workspace_bytes", n)
+        if nbytes <= 0 and params_fixed[2] == "MCD_CAIS_UHA_sn":      # the refusal, and where this mode's segments are
+            raise NotImplementedError((_lib.last_error() or what)
+                                      + " — MCD_CAIS_UHA_sn: cmcd_amd.smc_uha (the state with momentum)")
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "seg", what, retire=True)
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        lg = torch.empty(n, dtype=torch.float32, device=device)
+        stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
+        _lib.check(_lib.lib().cmcd_bound_segment(
+            C.byref(plan.desc), C.byref(plan.lay), k0, k1, seeds.data_ptr() if seeds is not None else None, n,
+            params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
+            ws.data_ptr(), ws.numel(), z.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(), stats.data_ptr(),
+            stream))
+        return {"z": z, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
+
+    return on_device(device, launch)
 
 
 def losses_of(state):
@@ -136,7 +138,7 @@ def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedul
     cuts = default_cuts(K) if cuts is None else [int(c) for c in cuts]
     if any(c <= 0 or c >= K for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):
         raise ValueError(f"cuts must be ascending bridges inside (0, {K})")
-    seeds, n = mcdbm._inputs(seeds, params_flat)
+    seeds, n = _inputs(seeds, params_flat)
     groups = int(groups)
     if groups < 1 or n % groups != 0:
         raise ValueError("N must be a multiple of groups")

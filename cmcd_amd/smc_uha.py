@@ -21,7 +21,8 @@ import torch
 
 from . import _lib, resample
 from . import mcdboundingmachine as mcdbm
-from .smc import default_cuts, losses_of
+from ._call import consts_args, _inputs, on_device, _workspace
+from .smc import _state_tensors, default_cuts, losses_of
 
 __all__ = ["STATE_FIELDS", "segment", "losses_of", "resample_stage", "default_cuts", "smc_bound"]
 
@@ -30,27 +31,12 @@ MODE = "MCD_CAIS_UHA_sn"
 
 
 def _state_inputs(state, params_flat, dim):
-    """The checks on a state handed to a segment with k0 > 0 -> (z, rho, wpath, key) as fresh tensors the library overwrites."""
+    """The checks on a state handed to a segment with k0 > 0 -> (z, rho, wpath, key, n)."""
     if not isinstance(state, dict) or any(k not in state for k in ("z", "rho", "wpath", "key")):
         raise TypeError("a 2nd-order segment with k0 > 0 starts from the state dict an earlier smc_uha.segment (or resample_stage) "
                         "returned: z, rho, wpath and key")
-    if not params_flat.is_cuda:
-        raise RuntimeError("the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor")
-    if params_flat.dtype != torch.float32 or not params_flat.is_contiguous():
-        raise ValueError("params_flat must be contiguous float32")
-    device = params_flat.device
-    for name in ("z", "rho", "wpath", "key"):
-        t = state[name]
-        if not isinstance(t, torch.Tensor) or t.device != device:
-            raise RuntimeError(f"the CMCD hot path runs on a ROCm device only: state[{name!r}] is not a tensor on the device of "
-                               "params_flat")
-    n = state["wpath"].numel()
-    if n < 1 or any(state[f].dtype != torch.float32 for f in ("z", "rho", "wpath")) or state["key"].dtype != torch.int32:
-        raise ValueError("state: z, rho and wpath must be float32, key int32")
-    if tuple(state["z"].shape) != (n, dim) or tuple(state["rho"].shape) != (n, dim) or tuple(state["key"].shape) != (n, 2):
-        raise ValueError(f"state: z and rho must have shape [{n}, {dim}] and key [{n}, 2]")
-    fresh = lambda t: t.detach().clone(memory_format=torch.contiguous_format)
-    return fresh(state["z"]), fresh(state["rho"]), fresh(state["wpath"].reshape(-1)), fresh(state["key"]), n
+    _inputs(None, params_flat, seedless=True)
+    return _state_tensors(state, params_flat.device, dim, ("z", "rho", "wpath", "key"))
 
 
 def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
@@ -65,7 +51,7 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     dim, k0, k1 = params_fixed[0], int(k0), int(k1)
     device = params_flat.device
     if k0 == 0:
-        seeds, n = mcdbm._inputs(state, params_flat)
+        seeds, n = _inputs(state, params_flat)
         z = torch.empty((n, dim), dtype=torch.float32, device=device)
         rho = torch.empty((n, dim), dtype=torch.float32, device=device)
         wpath = torch.empty(n, dtype=torch.float32, device=device)
@@ -73,27 +59,22 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     else:
         seeds = None
         z, rho, wpath, key, n = _state_inputs(state, params_flat, dim)
-    here = mcdbm._stream(device)
-    if here is None:
-        with torch.cuda.device(device):
-            return segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    dev_index, stream, capturing = here
-    L = _lib.lib()
-    nbytes = mcdbm._nbytes(plan, "cmcd_segment_uha_workspace_bytes", n)
-    if nbytes <= 0:
-        raise NotImplementedError(_lib.last_error() or "no 2nd-order segment kernel for this configuration")
-    ws = mcdbm._workspace(dev_index, device, stream, capturing, nbytes, "seg_uha")
-    mcdbm._prepared.pop((dev_index, ws.data_ptr()), None)      # this launch rewrites the buffer's tables: retire any claim on them
-    consts = log_prob.consts_on(device)
-    lg = torch.empty(n, dtype=torch.float32, device=device)
-    stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
-    _lib.check(L.cmcd_bound_segment_uha(
-        C.byref(plan.desc), C.byref(plan.lay), k0, k1, seeds.data_ptr() if seeds is not None else None, n,
-        params_flat.data_ptr(), params_flat.numel(),
-        consts.data_ptr() if consts is not None else None, consts.numel() if consts is not None else 0,
-        ws.data_ptr(), ws.numel(), z.data_ptr(), rho.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(),
-        stats.data_ptr(), stream))
-    return {"z": z, "rho": rho, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
+
+    def launch(dev_index, stream, capturing):
+        nbytes = mcdbm._nbytes(plan, "cmcd_segment_uha_workspace_bytes", n)
+        ws = _workspace(dev_index, device, stream, capturing, nbytes, "seg_uha",
+                        "no 2nd-order segment kernel for this configuration", retire=True)
+        cptr, cnum = consts_args(log_prob.consts_on(device))
+        lg = torch.empty(n, dtype=torch.float32, device=device)
+        stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
+        _lib.check(_lib.lib().cmcd_bound_segment_uha(
+            C.byref(plan.desc), C.byref(plan.lay), k0, k1, seeds.data_ptr() if seeds is not None else None, n,
+            params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
+            ws.data_ptr(), ws.numel(), z.data_ptr(), rho.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(),
+            stats.data_ptr(), stream))
+        return {"z": z, "rho": rho, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
+
+    return on_device(device, launch)
 
 
 def resample_stage(state, groups=1, ess_threshold=0.5, seed=0):
@@ -135,7 +116,7 @@ def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedul
     cuts = default_cuts(K) if cuts is None else [int(c) for c in cuts]
     if any(c <= 0 or c >= K for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):
         raise ValueError(f"cuts must be ascending bridges inside (0, {K})")
-    seeds, n = mcdbm._inputs(seeds, params_flat)
+    seeds, n = _inputs(seeds, params_flat)
     groups = int(groups)
     if groups < 1 or n % groups != 0:
         raise ValueError("N must be a multiple of groups")

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from cmcd_amd import _call
 from cmcd_amd import mcdboundingmachine as mcdbm
 from cmcd_amd import model_handler, synthetic
 from cmcd_amd import variationaldist as vd
@@ -296,18 +297,34 @@ def _entry_points():
     """(name, call(seeds, params_flat, unflatten, params_fixed, target)) of every bound / gradient entry point, with a CPU
     build whose mode that entry point accepts."""
     from cmcd_amd import boundingmachine as bm
+    from cmcd_amd import hais, ldvi, reverse_hais, reverse_ldvi, reverse_uha, smc, smc_uha
     sn = synthetic.build("gmm_n300_k8", device="cpu")
     var = synthetic.build("many_gmm_var_n16000_k256", device="cpu")
-    flat, un, fixed = bm.initialize(dim=2, device="cpu")
-    mf = {"params_flat": flat, "unflatten": un, "params_fixed": fixed, "target": sn["target"]}
+
+    def built(initialize, **kw):
+        flat, un, fixed = initialize(dim=2, device="cpu", **kw)
+        return {"params_flat": flat, "unflatten": un, "params_fixed": fixed, "target": sn["target"]}
+    mf = built(bm.initialize)
+    uha = built(hais.initialize, nbridges=4)
+    cmcd2 = built(mcdbm.initialize, nbridges=8, mode="MCD_CAIS_UHA_sn", nn_arch="geffner", emb_dim=20)
+    lv = built(ldvi.initialize, nbridges=8, nn_arch="geffner", emb_dim=20)
+    x = torch.zeros((8, 2))
+    reverse = lambda module: lambda seeds, *rest: module.bound_reverse(seeds, x, *rest)
+    segment = lambda module: lambda seeds, *rest: module.segment(seeds, 0, 2, *rest)
     return [("compute_bound", mcdbm.compute_bound, sn), ("compute_bound_var", mcdbm.compute_bound_var, var),
             ("compute_bound_grad", mcdbm.compute_bound_grad, sn), ("compute_log_var_grad", mcdbm.compute_log_var_grad, var),
-            ("bm.compute_bound", bm.compute_bound, mf), ("bm.grad_and_loss", bm.grad_and_loss, mf)]
+            ("bm.compute_bound", bm.compute_bound, mf), ("bm.grad_and_loss", bm.grad_and_loss, mf),
+            ("hais.compute_bound", hais.compute_bound, uha), ("hais.grad_and_loss", hais.grad_and_loss, uha),
+            ("ldvi.compute_bound", ldvi.compute_bound, lv), ("ldvi.grad_and_loss", ldvi.grad_and_loss, lv),
+            ("bound_reverse", reverse(mcdbm), sn), ("reverse_uha.bound_reverse", reverse(reverse_uha), cmcd2),
+            ("reverse_ldvi.bound_reverse", reverse(reverse_ldvi), lv), ("reverse_hais.bound_reverse", reverse(reverse_hais), uha),
+            ("smc.segment", segment(smc), sn), ("smc_uha.segment", segment(smc_uha), cmcd2)]
 
 
 def test_every_entry_point_validates_alike_before_it_needs_a_device():
-    """One call path: forward, both gradients and the mean-field bound refuse the same inputs with the same exceptions, in the
-    same order (mode, target type, target dim, then the device), all before the library is loaded."""
+    """One call path: forward, both gradients, the mean-field bound, UHA, LDVI, the four reverse chains and the two segments
+    refuse the same inputs with the same exceptions, in the same order (mode, target type, target dim, then the device), all
+    before the library is loaded."""
     seeds = torch.arange(1, 9, dtype=torch.int32)
     wide = model_handler.load_model("funnel")[0]                       # dim 10 against the builds' dim 2
     assert wide.dim == 10
@@ -320,9 +337,10 @@ def test_every_entry_point_validates_alike_before_it_needs_a_device():
             fn(*args(target=lambda z: z.sum()))
         with pytest.raises(ValueError, match="target dim 10 != params_fixed dim 2"):
             fn(*args(target=wide))
-        if not name.startswith("bm."):
+        if len(b["params_fixed"]) == 4:                                # (dim, nbridges, lfsteps) of bm / hais names no mode
             dim, K, _, spec = b["params_fixed"]
-            for mode in ("MCD_U_a-lp", "MCD_U_a-lp-sna"):
+            # MCD_U_a-lp is LDVI's own network-free mode: there an overdamped mode is the foreign one
+            for mode in ("MCD_CAIS_sn" if "ldvi" in name else "MCD_U_a-lp", "MCD_U_a-lp-sna"):
                 with pytest.raises(NotImplementedError, match="Mode not implemented."):   # before the TypeError / RuntimeError
                     fn(*args(params_fixed=(dim, K, mode, spec), target=lambda z: z.sum()))
     # each gradient keeps its own mode gate: the other gradient's mode is refused, on CPU tensors, as an unknown one is
@@ -330,6 +348,29 @@ def test_every_entry_point_validates_alike_before_it_needs_a_device():
     for fn, b in ((bptt, var), (vargrad, sn)):
         with pytest.raises(NotImplementedError, match="Mode not implemented."):
             fn(seeds, b["params_flat"], b["unflatten"], b["params_fixed"], b["target"])
+
+
+def test_hais_lgcp_validates_in_its_own_order_before_it_needs_a_device():
+    """cmcd_amd.hais_lgcp is the one entry point whose order differs: the target type, then ITS target gate (lgcp only, so the
+    dim-10 funnel of the table above is refused as a foreign target, not for its dim), then the target dim, then the device."""
+    from cmcd_amd import hais_lgcp
+    from cmcd_amd.lgcp import load_model_lgcp
+    from helpers import lgcp_counts_fixture
+    seeds = torch.arange(1, 9, dtype=torch.int32)
+    lgcp = load_model_lgcp("lgcp", None, flat_bin_counts=lgcp_counts_fixture())[0]
+    assert lgcp.dim == 1600
+    flat, un, fixed = hais_lgcp.initialize(dim=1600, nbridges=4, device="cpu")
+    small = hais_lgcp.initialize(dim=2, nbridges=4, device="cpu")
+    for fn in (hais_lgcp.compute_bound, hais_lgcp.grad_and_loss):
+        with pytest.raises(RuntimeError, match="the CMCD hot path runs on a ROCm device only: params_flat is not a device tensor"):
+            fn(seeds, flat, un, fixed, lgcp)
+        with pytest.raises(TypeError, match="log_prob must be a cmcd_amd.model_handler.Target"):
+            fn(seeds, flat, un, fixed, lambda z: z.sum())
+        with pytest.raises(NotImplementedError,
+                           match="cmcd_amd.hais_lgcp runs UHA on lgcp only: use cmcd_amd.hais for target 'funnel'"):
+            fn(seeds, flat, un, fixed, model_handler.load_model("funnel")[0])
+        with pytest.raises(ValueError, match="target dim 1600 != params_fixed dim 2"):
+            fn(seeds, *small, lgcp)
 
 
 def test_plan_is_shared_and_follows_the_kernel_variant(monkeypatch):
@@ -360,34 +401,34 @@ def test_workspace_lru_rules(monkeypatch):
             dropped.append(key)
             return super().pop(key, *default)
 
-    monkeypatch.setattr(mcdbm, "_workspaces", {})
-    monkeypatch.setattr(mcdbm, "_prepared", Prepared())
+    monkeypatch.setattr(_call, "_workspaces", {})
+    monkeypatch.setattr(_call, "_prepared", Prepared())
     cpu = torch.device("cpu")
-    ws = lambda stream, nbytes, tag="", capturing=False: mcdbm._workspace("cpu", cpu, stream, capturing, nbytes, tag)
+    ws = lambda stream, nbytes, tag="", capturing=False: _call._workspace("cpu", cpu, stream, capturing, nbytes, tag)
     a = ws(7, 100)
     assert a.dtype == torch.uint8 and a.numel() == 1 << 20 and dropped == [("cpu", a.data_ptr())]
-    mcdbm._prepared[("cpu", a.data_ptr())] = "tables of an earlier call"
+    _call._prepared[("cpu", a.data_ptr())] = "tables of an earlier call"
     assert ws(7, 1 << 20) is a and len(dropped) == 1                   # same (stream, tag), large enough: reused, claim untouched
     assert ws(7, 100, "grad") is not a and ws(8, 100) is not a         # another purpose / another stream: buffers of their own
     dropped.clear()
     big = ws(7, (1 << 20) + 1)
     assert big is not a and big.numel() == (1 << 20) + 1 and dropped == [("cpu", big.data_ptr())]
-    assert ws(7, 100) is big and mcdbm._workspaces["cpu"][(7, "")] is big
+    assert ws(7, 100) is big and _call._workspaces["cpu"][(7, "")] is big
     # capture: private, never cached, and nothing in the cache moves
-    before = dict(mcdbm._workspaces["cpu"])
+    before = dict(_call._workspaces["cpu"])
     private = ws(7, 100, capturing=True)
-    assert private is not big and private.numel() == 1 << 20 and mcdbm._workspaces["cpu"] == before
-    assert ws(99, 100, capturing=True) is not None and (99, "") not in mcdbm._workspaces["cpu"]
+    assert private is not big and private.numel() == 1 << 20 and _call._workspaces["cpu"] == before
+    assert ws(99, 100, capturing=True) is not None and (99, "") not in _call._workspaces["cpu"]
     # per-device LRU of 16: fill it, touch the oldest key, add one more
-    monkeypatch.setattr(mcdbm, "_workspaces", {})
-    first = [ws(s, 100) for s in range(mcdbm._WORKSPACE_CACHE)]
-    assert len(mcdbm._workspaces["cpu"]) == 16
+    monkeypatch.setattr(_call, "_workspaces", {})
+    first = [ws(s, 100) for s in range(_call._WORKSPACE_CACHE)]
+    assert len(_call._workspaces["cpu"]) == 16
     assert ws(0, 100) is first[0]                                      # stream 0 is now the most recently used, stream 1 the least
     ws(16, 100)                                                        # the 17th key
-    assert len(mcdbm._workspaces["cpu"]) == 16 and (1, "") not in mcdbm._workspaces["cpu"]
+    assert len(_call._workspaces["cpu"]) == 16 and (1, "") not in _call._workspaces["cpu"]
     assert ws(0, 100) is first[0] and ws(2, 100) is first[2]
-    other = mcdbm._workspace("cpu:1", cpu, 0, False, 100, "")          # another device's LRU is its own
-    assert other is not first[0] and len(mcdbm._workspaces["cpu"]) == 16 and len(mcdbm._workspaces["cpu:1"]) == 1
+    other = _call._workspace("cpu:1", cpu, 0, False, 100, "")          # another device's LRU is its own
+    assert other is not first[0] and len(_call._workspaces["cpu"]) == 16 and len(_call._workspaces["cpu:1"]) == 1
 
 
 def test_non_trainable_tail_is_found_once_per_unflatten():
@@ -396,25 +437,124 @@ def test_non_trainable_tail_is_found_once_per_unflatten():
     n_train = un.offset("eta")                                         # keys sorted: eta is the first leaf of params_notrain
     assert n_train == min(off for path, (off, _) in un.layout.items() if path[0] == 1)
     g = torch.ones_like(flat)
-    mcdbm._zero_notrain(g, un)
+    _call._zero_notrain(g, un)
     assert un._n_train == n_train and bool((g[:n_train] == 1).all()) and bool((g[n_train:] == 0).all())
     un.layout = None                                                   # a second call does not scan the layout again
     g = torch.ones_like(flat)
-    mcdbm._zero_notrain(g, un)
+    _call._zero_notrain(g, un)
     assert float(g.sum()) == n_train
     flat, un = mcdbm.ravel_pytree(({"a": torch.ones(3)},))              # no params_notrain at all: nothing to zero
     g = torch.ones_like(flat)
-    mcdbm._zero_notrain(g, un)
+    _call._zero_notrain(g, un)
     assert un._n_train is None and float(g.sum()) == 3
 
 
 def test_stream_helper_answers_only_for_the_current_device(monkeypatch):
-    """_stream: (device index, raw stream of THAT device, capturing) when the tensor's device is current, None otherwise (the
-    entry point then re-enters itself under torch.cuda.device)."""
+    """_stream: (device index, raw stream of THAT device, capturing) when the tensor's device is current, None otherwise
+    (on_device then runs the entry point's body under torch.cuda.device)."""
     asked = []
     monkeypatch.setattr(torch._C, "_cuda_getDevice", lambda: 1, raising=False)
     monkeypatch.setattr(torch._C, "_cuda_getCurrentRawStream", lambda i: asked.append(i) or 0xABC0 + i, raising=False)
     monkeypatch.setattr(torch._C, "_cuda_isCurrentStreamCapturing", lambda: False, raising=False)
-    assert mcdbm._stream(torch.device("cuda", 1)) == (1, 0xABC1, False)
-    assert mcdbm._stream(torch.device("cuda")) == (1, 0xABC1, False)           # "cuda" is the current device
-    assert mcdbm._stream(torch.device("cuda", 0)) is None and asked == [1, 1]
+    assert _call._stream(torch.device("cuda", 1)) == (1, 0xABC1, False)
+    assert _call._stream(torch.device("cuda")) == (1, 0xABC1, False)           # "cuda" is the current device
+    assert _call._stream(torch.device("cuda", 0)) is None and asked == [1, 1]
+
+
+class _FakeDevices:
+    """torch's three device queries as _call._stream reads them, on a machine without a GPU: `current` is the current device,
+    device i's stream handle is 0xABC0 + i; torch.cuda.device(d) is a context that makes d current and records its use."""
+
+    def __init__(self, monkeypatch, current):
+        self.current, self.asked, self.entered, self.depth = current, [], [], 0
+        monkeypatch.setattr(torch._C, "_cuda_getDevice", lambda: self.current, raising=False)
+        monkeypatch.setattr(torch._C, "_cuda_getCurrentRawStream",
+                            lambda i: self.asked.append((i, self.depth)) or 0xABC0 + i, raising=False)
+        monkeypatch.setattr(torch._C, "_cuda_isCurrentStreamCapturing", lambda: False, raising=False)
+        monkeypatch.setattr(torch.cuda, "device", self.context)
+
+    def context(self, device):
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            self.entered.append(device)
+            was, self.current, self.depth = self.current, device.index, self.depth + 1
+            try:
+                yield
+            finally:
+                self.current, self.depth = was, self.depth - 1
+        return cm()
+
+
+def test_on_device_runs_the_body_once_with_the_device_and_stream_of_the_tensor(monkeypatch):
+    """Current device: the body runs directly, no context manager.  Another device: once, inside torch.cuda.device(that
+    device), with the stream asked for under it; the body's return value comes back either way."""
+    fake = _FakeDevices(monkeypatch, current=1)
+    seen = []
+
+    def body(dev_index, stream, capturing):
+        seen.append((dev_index, stream, capturing, fake.depth))
+        return "the body's result"
+    for here in (torch.device("cuda", 1), torch.device("cuda")):       # "cuda" is the current device
+        assert _call.on_device(here, body) == "the body's result"
+        assert seen.pop() == (1, 0xABC1, False, 0) and not seen and fake.entered == []
+    away = torch.device("cuda", 0)
+    fake.asked.clear()
+    assert _call.on_device(away, body) == "the body's result"
+    assert seen == [(0, 0xABC0, False, 1)] and fake.entered == [away]
+    assert fake.asked == [(0, 1)] and fake.depth == 0 and fake.current == 1       # asked under the context, which was left
+
+
+def test_workspace_refuses_a_size_of_zero_and_retires_claims_only_where_told(monkeypatch):
+    """_workspace as the entry points call it: an answer <= 0 of a size query is NotImplementedError with the library's last
+    error, else the site's text, and no buffer is made; otherwise the buffer of (device, stream, tag), whose claim in _prepared
+    goes with retire=True and stays without it."""
+    monkeypatch.setattr(_call, "_workspaces", {})
+    monkeypatch.setattr(_call, "_prepared", {})
+    last = [""]
+    monkeypatch.setattr(_call._lib, "last_error", lambda: last[0])
+    cpu = torch.device("cpu")
+
+    def workspace(nbytes, tag, *what, capturing=False, **kw):
+        return _call._workspace("cpu", cpu, 7, capturing, nbytes, tag, *what, **kw)
+    for nbytes in (0, -1):
+        with pytest.raises(NotImplementedError, match="^no kernel of this site$"):
+            workspace(nbytes, "rev", "no kernel of this site", retire=True)
+        last[0] = "cmcd: dim 3 has no instance"
+        with pytest.raises(NotImplementedError, match="^cmcd: dim 3 has no instance$"):
+            workspace(nbytes, "rev", "no kernel of this site")
+        last[0] = ""
+    assert _call._workspaces == {}
+    ws = workspace(100, "rev", "no kernel of this site")
+    assert ws.numel() == 1 << 20 and _call._workspaces == {"cpu": {(7, "rev"): ws}}
+    slot = ("cpu", ws.data_ptr())
+    _call._prepared[slot] = "tables of a forward call"
+    assert workspace(100, "rev", "no kernel of this site") is ws and _call._prepared[slot] == "tables of a forward call"
+    assert workspace(100, "rev", "no kernel of this site", retire=True) is ws and slot not in _call._prepared
+    private = workspace(100, "rev", capturing=True)                # capturing: never the cached buffer
+    assert private is not ws and _call._workspaces == {"cpu": {(7, "rev"): ws}}
+
+
+def test_consts_args_and_check_x():
+    assert _call.consts_args(None) == (None, 0)
+    c = torch.arange(5, dtype=torch.float32)
+    assert _call.consts_args(c) == (c.data_ptr(), 5)
+    # check_x on CPU tensors: `meta` stands in for "another device"; no CPU tensor is a device tensor
+    cpu = torch.device("cpu")
+    device_only = "the CMCD hot path runs on a ROCm device only: x is not a tensor on the device of params_flat"
+    for x in ([[0.0, 0.0]] * 3, torch.zeros((3, 2)), torch.zeros((3, 2), device="meta")):
+        with pytest.raises(RuntimeError, match=device_only):
+            _call.check_x(x, 3, 2, cpu)
+
+    class OnDevice(torch.Tensor):                                      # a CPU tensor that answers is_cuda, to reach the ValueError
+        is_cuda = True
+    on = lambda t: t.as_subclass(OnDevice)
+    _call.check_x(on(torch.zeros((3, 2))), 3, 2, cpu)
+    with pytest.raises(RuntimeError, match=device_only):
+        _call.check_x(on(torch.zeros((3, 2))), 3, 2, torch.device("meta"))
+    shape = r"x must be contiguous float32 of shape \[n, dim\] = \[3, 2\]"
+    for bad in (torch.zeros((3, 2), dtype=torch.float64), torch.zeros((2, 3)).t(), torch.zeros((3, 3)), torch.zeros((2, 2)),
+                torch.zeros(6)):
+        with pytest.raises(ValueError, match=shape):
+            _call.check_x(on(bad), 3, 2, cpu)
