@@ -1452,6 +1452,26 @@ static int lgcp_gemm_attrs() {
   return gemm_lds;
 }
 
+// Up to three ranges of 32-bit words (float tables and the int arrival counters alike) start from zero.  A launch, not
+// hipMemsetAsync (cmcd_ldvi.hip: ldvi_zero_kernel): captured into a graph a memset becomes a memset node, and from the second replay
+// on the d = 1600 calls came back with garbage (-4.69e24) in every fourth word of the cleared ranges — a quarter of every weight
+// gradient, five of twenty losses (tests/test_gpu_capture.py, test_lgcp_one_stream).  Why the memset nodes do that is not known; what
+// is observed is that the same clears done by a kernel node return the eager bits on every replay.  Plain stores.
+struct LgcpZeroArgs { uint32_t* p[3]; int64_t n[3]; };
+__global__ __launch_bounds__(256) void lgcp_zero_kernel(LgcpZeroArgs a) {
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int r = 0; r < 3; ++r)
+    for (int64_t i = t0; i < a.n[r]; i += stride) a.p[r][i] = 0u;
+}
+// (a range with n = 0 is skipped; its pointer is not read)
+static int lgcp_zero(hipStream_t stream, void* p0, int64_t n0, void* p1 = nullptr, int64_t n1 = 0, void* p2 = nullptr, int64_t n2 = 0) {
+  LgcpZeroArgs a{{static_cast<uint32_t*>(p0), static_cast<uint32_t*>(p1), static_cast<uint32_t*>(p2)}, {n0, n1, n2}};
+  const int64_t longest = std::max(n0, std::max(n1, n2)), blocks = (longest + 255) / 256;
+  if (blocks < 1) return CMCD_OK;
+  hipLaunchKernelGGL(lgcp_zero_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
+}
+
 int lgcp_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, const int32_t* seeds, int64_t n,
                  const float* params, const float* tc, float* ws, float* out_loss, float* out_z,
                  double** partials_out, float* traj, void* stream_, bool tables_ready, float* keep_gws) {
@@ -1538,8 +1558,7 @@ int lgcp_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw,
       if (hipStreamWaitEvent(st_l, ev_fork, 0) != hipSuccess) return bail();
       forked[l] = true;
     }
-    counters[l] = reinterpret_cast<int*>(ws + w.lane[l].counters);
-    if (hipMemsetAsync(counters[l], 0, sizeof(int) * (cbD + cbIN), st_l) != hipSuccess) return bail();
+    counters[l] = reinterpret_cast<int*>(ws + w.lane[l].counters);     // (cleared with the lane's first pass below)
   }
   const int ula = d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0);
   const LgcpKeep keep = keep_gws ? lgcp_keep(d, n, keep_gws) : LgcpKeep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
@@ -1555,9 +1574,11 @@ int lgcp_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw,
       hipStream_t st_l = l == 0 ? stream : side[l];
       const LgcpLane& wl = w.lane[l];
       M[l] = (int)((n - base) < kMP ? (n - base) : kMP);
-      if (hipMemsetAsync(ws + wl.slots, 0, sizeof(float) * 3 * cbD * kMP, st_l) != hipSuccess) return bail();
-      // packed operands: the padding (rows >= M, inputs >= IN) must read as zeros; slots start at zero
-      if (nsk && hipMemsetAsync(ws + wl.nsk, 0, sizeof(float) * (kNskOps * kNskOperand + 3 * (int64_t)tD * kMP), st_l) != hipSuccess)
+      // packed operands: the padding (rows >= M, inputs >= IN) must read as zeros; slots start at zero; the lane's arrival
+      // counters once per call (every lane is live in the first group).  One launch on the lane's stream (lgcp_zero_kernel).
+      if (lgcp_zero(st_l, ws + wl.slots, 3 * (int64_t)cbD * kMP,
+                    nsk ? ws + wl.nsk : nullptr, nsk ? kNskOps * kNskOperand + 3 * (int64_t)tD * kMP : 0,
+                    gbase == 0 ? counters[l] : nullptr, gbase == 0 ? cbD + cbIN : 0) != CMCD_OK)
         return bail();
       LgcpStateArgs st{};
       st.seeds = seeds + base; st.params = params; st.tc = tc; st.x = nsk ? ws + wl.nsk : ws + wl.x; st.packed = nsk ? 1 : 0;
@@ -2049,8 +2070,7 @@ int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, in
   const int D = d.dim, E = d.emb_dim, IN = D + E, K = d.nbridges;
   const LgcpWs w = lgcp_ws(d, n, sw.total_floats);
   const LgcpGradWs g = lgcp_grad_ws(d, n);
-  if (hipMemsetAsync(grad, 0, sizeof(float) * n_params, stream) != hipSuccess) return CMCD_ERR_HIP;
-  if (hipMemsetAsync(gws + g.zero_lo, 0, sizeof(float) * (g.zero_hi - g.zero_lo), stream) != hipSuccess) return CMCD_ERR_HIP;
+  if (lgcp_zero(stream, grad, n_params, gws + g.zero_lo, g.zero_hi - g.zero_lo) != CMCD_OK) return CMCD_ERR_HIP;
   const int ula = d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0);
   const bool net = ula != 1;
   // transposed weight copies: the backward GEMMs are then the forward kernel on W^T
@@ -2108,15 +2128,16 @@ int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, in
   // bias1 rows are still in the forward workspace (lgcp_forward's prep)
   for (int64_t base = 0; base < n; base += kMP) {
     const int M = (int)((n - base) < kMP ? (n - base) : kMP);
-    if (base > 0) {  // lambda / g start from zero for every pass
-      if (hipMemsetAsync(gws + g.lamn, 0, sizeof(float) * 2 * ((kMP * (int64_t)D + 3) & ~3), stream) != hipSuccess) return CMCD_ERR_HIP;
-      if (hipMemsetAsync(gws + g.gmu_acc, 0, sizeof(float) * 2 * ((kMP * (int64_t)D + 3) & ~3), stream) != hipSuccess) return CMCD_ERR_HIP;
-    }
-    if (!kept && (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess)) return CMCD_ERR_HIP;
     const bool nskb = nskb_ok && kept && M <= 20;      // (21 .. 32 particles: two workgroups per column tile — the split-K form)
     float* const dOp = gws + g.bops, *vp = dOp + kNskOperand, *da2p = vp + kNskOperand, *da1p = da2p + kNskOperand;
-    // the padding of the packed operands (rows >= M, inputs past the contraction) must read as zeros
-    if (nskb && hipMemsetAsync(dOp, 0, sizeof(float) * 4 * kNskOperand, stream) != hipSuccess) return CMCD_ERR_HIP;
+    {
+      // lambda / g (lamn | gE) and the accumulators (gmu_acc | glam_acc) start from zero for every pass (the first one's by the
+      // call's clear above); the padding of the packed operands (rows >= M, inputs past the contraction) must read as zeros
+      const int64_t pair = base > 0 ? 2 * ((kMP * (int64_t)D + 3) & ~int64_t(3)) : 0;
+      if (lgcp_zero(stream, gws + g.lamn, pair, gws + g.gmu_acc, pair, nskb ? dOp : nullptr, nskb ? 4 * (int64_t)kNskOperand : 0) != CMCD_OK)
+        return CMCD_ERR_HIP;
+    }
+    if (!kept && (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess)) return CMCD_ERR_HIP;
 
     // forward recompute at z_e into buffer set e & 1, on stream st: the forward path's three launches (activations
     // fused into the GEMMs; the third has no consumer here: the adjoint step sums its slabs)
@@ -2741,7 +2762,8 @@ static int lgcp_uha_forward(const cmcd_desc& d, const cmcd_layout& lay, const Ws
   const float mu0 = 3.8812819069514780f;
   const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64;
   int* counters = reinterpret_cast<int*>(ws + w.counters);
-  if (hipMemsetAsync(counters, 0, sizeof(int) * (cbD + cbIN), stream) != hipSuccess) return CMCD_ERR_HIP;
+  // (no parity case takes this split-K form in the 2nd-order mode, so no capture test reaches this clear: a launch like its siblings)
+  if (lgcp_zero(stream, counters, cbD + cbIN) != CMCD_OK) return CMCD_ERR_HIP;
   for (int64_t base = 0; base < n; base += kMP) {
     const int M = (int)((n - base) < kMP ? (n - base) : kMP);
     LgcpUhaStepArgs sa{};
@@ -3140,8 +3162,7 @@ static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLay
   const int D = d.dim, E = d.emb_dim, IN = 2 * D + E, K = d.nbridges;
   const LgcpUhaWs w = lgcp_uha_ws(d, n, sw.total_floats);
   const LgcpUhaGradWs g = lgcp_uha_grad_ws(d, n);
-  if (hipMemsetAsync(grad, 0, sizeof(float) * n_params, stream) != hipSuccess) return CMCD_ERR_HIP;
-  if (hipMemsetAsync(gws + g.zero_lo, 0, sizeof(float) * (g.zero_hi - g.zero_lo), stream) != hipSuccess) return CMCD_ERR_HIP;
+  if (lgcp_zero(stream, grad, n_params, gws + g.zero_lo, g.zero_hi - g.zero_lo) != CMCD_OK) return CMCD_ERR_HIP;
   {
     const dim3 tb(32, 8);
     hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (2 * D + 31) / 32), tb, 0, stream, params + lay.g_w1,
@@ -3175,9 +3196,6 @@ static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLay
 
   for (int64_t base = 0; base < n; base += kMP) {
     const int M = (int)((n - base) < kMP ? (n - base) : kMP);
-    if (base > 0) {   // per-pass accumulators start from zero (lz / lr are initialised at point K)
-      if (hipMemsetAsync(gws + g.gmu_acc, 0, sizeof(float) * 2 * ((kMP * (int64_t)D + 3) & ~3), stream) != hipSuccess) return CMCD_ERR_HIP;
-    }
     LgcpUhaAdjArgs aa{};
     aa.params = params; aa.tc = tc; aa.sched = ws + sw.sched; aa.traj = traj; aa.kr = gws + g.kr; aa.hv = gws + g.hv;
     aa.snA = gws + g.fs[0].sn; aa.snB = gws + g.fs[1].sn; aa.du1 = gws + g.du1; aa.dxf = gws + g.dxf;
@@ -3190,10 +3208,12 @@ static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLay
     const bool nskb = kept && M <= 20;
     const bool merged = M > 16;
     float* const dOp = gws + g.bops, *vp = dOp + kNskOperand, *da2p = vp + kNskOperand, *da1p = da2p + 2 * kNskOperand;
-    if (nskb) {
-      if (hipMemsetAsync(dOp, 0, sizeof(float) * 6 * kNskOperand, stream) != hipSuccess) return CMCD_ERR_HIP;
-      aa.dOp = dOp; aa.vp = vp; aa.bslab = 1;
-    }
+    // per-pass accumulators (gmu_acc | glam_acc) start from zero (the first pass's by the call's clear above; lz / lr are
+    // initialised at point K); the padding of the packed operands must read as zeros
+    if (lgcp_zero(stream, gws + g.gmu_acc, base > 0 ? 2 * ((kMP * (int64_t)D + 3) & ~int64_t(3)) : 0,
+                  nskb ? dOp : nullptr, nskb ? 6 * (int64_t)kNskOperand : 0) != CMCD_OK)
+      return CMCD_ERR_HIP;
+    if (nskb) { aa.dOp = dOp; aa.vp = vp; aa.bslab = 1; }
     auto kr_at = [&](int e) {   // K^-1 (z_e - mu0)
       GemmArgs gm{};
       gm.M = M; gm.Kdim = D; gm.counters = counters;

@@ -2905,6 +2905,17 @@ static float* g_uha_xdump = nullptr;   // tests: cmcd_debug_uha_xdump — the ne
 extern "C" void cmcd_debug_uha_xdump(float* buf) { g_uha_xdump = buf; }
 #endif
 
+// grad[n_grad] and gtab[n_gtab] start from zero.  A launch, not two hipMemsetAsync (cmcd_ldvi.hip: ldvi_zero_kernel): captured into
+// a graph those become memset nodes, and from the second replay on — in one run of three — the whole-chain gradient came back wrong
+// (tests/test_gpu_capture.py, test_uha_gradient [*-item0]).  The mechanism is not known; observed: with the clear as a kernel node
+// every replay returns the eager bits.
+__global__ __launch_bounds__(256) void uha_zero_kernel(float* grad, int64_t n_grad, float* gtab, int64_t n_gtab) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_grad + n_gtab; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < n_grad) grad[i] = 0.f;
+    else gtab[i - n_grad] = 0.f;
+  }
+}
+
 // ws_fwd / traj as left by the forward launch on the SAME desc / params; gws: uha_grad_workspace_floats; grad: [n_params],
 // fully overwritten (zeros for the leaves the loss does not reach).
 int uha_grad_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, int64_t n, const float* params,
@@ -2928,8 +2939,8 @@ int uha_grad_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& 
   // (behind the item buffers, whether this call uses them or not)
   ga.det = slabs + uha_slab_floats(d, HP) * kUhaSlabs + uha_item_floats(d, w.T, n);
   if (!items) {   // (the work-item path's Jacobian launch zeroes both on its way)
-    if (hipMemsetAsync(gws, 0, sizeof(float) * tot, stream) != hipSuccess) return CMCD_ERR_HIP;
-    if (hipMemsetAsync(grad, 0, sizeof(float) * n_params, stream) != hipSuccess) return CMCD_ERR_HIP;
+    const int64_t blocks = (n_params + tot + 255) / 256;
+    hipLaunchKernelGGL(uha_zero_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, grad, n_params, gws, tot);
   }
   const bool wglobal = w.T > 4;
   // (keep the small-batch sweep's workgroup under 80 KB: two then share a CU — measured 510 against 668 us for the named shape
