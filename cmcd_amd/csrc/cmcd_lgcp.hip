@@ -2762,7 +2762,7 @@ static int lgcp_uha_forward(const cmcd_desc& d, const cmcd_layout& lay, const Ws
   const float mu0 = 3.8812819069514780f;
   const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64;
   int* counters = reinterpret_cast<int*>(ws + w.counters);
-  // (no parity case takes this split-K form in the 2nd-order mode, so no capture test reaches this clear: a launch like its siblings)
+  // (a launch like its siblings, not a memset node; the captured case lgcp-uha-rc-n33 and the uha-rc-* / uha-w3332-* parity cases reach it)
   if (lgcp_zero(stream, counters, cbD + cbIN) != CMCD_OK) return CMCD_ERR_HIP;
   for (int64_t base = 0; base < n; base += kMP) {
     const int M = (int)((n - base) < kMP ? (n - base) : kMP);

@@ -368,6 +368,9 @@ LGCP_FACTS = {
     "lgcp-n33": _facts([32, 1], 2, True, True),           # the forward forks a lane; the `base > 0` clears of lgcp_grad run
     "lgcp-rc-n21": _facts([21], 1, False, True),          # form 3: the sweep's two-stream recompute
     "lgcp-uha-n33": _facts([32, 1], 1, True, False),      # two passes in turn on one stream: lgcp_uha_grad's `base > 0` clear
+    # form 3 of the 2nd-order mode: the split-K forward (its counter clear) and the recompute sweep (its lgcp_zero launches), two
+    # passes in turn on one stream
+    "lgcp-uha-rc-n33": _facts([32, 1], 1, False, False),
     "lgcp-fwd-n33": _facts([32, 1], 2, None, True),
     "lgcp-wide-n230": _facts(None, 1, None, False, wide=True),
 }
@@ -403,8 +406,8 @@ CASES = (
     # ---- tests/lgcp_grad_cases.py, the call on the caller's stream alone
     + [("lgcp-" + cid, "lgcp_one_stream", LgcpCase(cid, entry="grad")) for cid in ("n20", "n21", "var-n21", "ulasn-n17", "ula-n20", "uha-n17")]
     + [("lgcp-fwd-n20", "lgcp_one_stream", LgcpCase("n20", entry="forward"))]
-    # ---- d = 1600 with side streams (uha-n33 sits here with its pass count; its sequence stays on one stream)
-    + [("lgcp-" + cid, "lgcp_forked_streams", LgcpCase(cid, entry="grad")) for cid in ("n33", "rc-n21", "uha-n33")]
+    # ---- d = 1600 with side streams (uha-n33 and uha-rc-n33 sit here with their pass count; their sequences stay on one stream)
+    + [("lgcp-" + cid, "lgcp_forked_streams", LgcpCase(cid, entry="grad")) for cid in ("n33", "rc-n21", "uha-n33", "uha-rc-n33")]
     + [("lgcp-fwd-n33", "lgcp_forked_streams", LgcpCase("n33", entry="forward")),
        ("lgcp-wide-n230", "lgcp_forked_streams", LgcpWideCase((230, 2)))]
 )

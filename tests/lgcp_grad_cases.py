@@ -38,7 +38,33 @@ M <= 16 rows takes the no-split-K GEMM, 17 .. 20 its merged instance (rows 16 ..
   ulasn-*                         MCD_ULA_sn, K = 2, n = 17, 33, 52: the network's time index e - 1 lands in row 0 of S twice
   ula-*                           MCD_ULA (no network), K = 2, n = 6, 20, 33
   uha-*                           MCD_CAIS_UHA_sn (width 3220, 2 kNskChunks chunks, seven products per bridge): n = 16, 17, 20,
-                                  21, 33 at K = 2 and n = 52 at K = 1
+                                  21, 33 at K = 2 and n = 52 at K = 1: the no-split-K forward, the sweep on kept activations
+
+The 2nd-order mode's other launch sequence (`uha_route`): the split-K forward (lgcp_uha_forward below its early return:
+lgcp_uha_init_kernel unpacked, lgcp_gemm_kernel<EPI_NONE> on the 2 D-pitch state, lgcp_uha_net with slabs and arrival counters,
+lgcp_uha_mid_kernel<4> / lgcp_uha_close_kernel<4> summing kSplit slabs) and the recompute sweep (the `!kept` branch of
+lgcp_uha_grad: kr_at, lgcp_uha_gather_kernel, two lgcp_uha_net per bridge into the two LgcpUhaFwdSets, the EPI_ACTB products
+writing U1 / U2, the kSplit sums of the lgcp_uha_adj_* kernels), pinned by form 3 or taken by the library itself at IN > 3328.
+
+  id            n    K  form  over         what it reaches
+  uha-rc-n1     1    2  3                  one row: dim3(cb, kSplit) grids with M = 1, both buffer sets
+  uha-rc-n20    20   2  3                  the configuration's pass (the merged instance on the kept path; no such split here)
+  uha-rc-n21    21   1  3                  K = 1: kr_at(K) and kr_at(0) with one bridge between; the first boundary is the last
+  uha-rc-n33    33   3  3                  32 + 1: counters and forward buffers reused by a second pass, the `base > 0` clear, three
+                                           bridges through the two buffer sets
+  uha-rc-n65    65   2  3                  three passes
+  uha-w3332-5   5    2  0     emb_dim=132  IN = 3332 > 32 kNskChunks: the split-K form by the library's own choice; cbIN = 53
+                                           with a 4-column last block
+  uha-w3332-37  37   2  0     emb_dim=132  the same over 32 + 5
+  uha-w3328-20  20   2  0     emb_dim=128  the last width the no-split-K form takes (exactly 2 x 104 chunks), merged pass
+  uha-w3212-37  37   2  0     emb_dim=12   kept path at tIN = 201 with a ragged last tile, both GEMM families (32 + 5)
+  uha-w3204-20  20   2  0     emb_dim=4    kept path, merged pass, IN % 16 = 4
+
+The route the library takes in production when the kept tables pass 2^28 floats (`uha_keep_floats`; at width 3220 from
+K n = 15 183 on whatever K is, e.g. K = 128 with n >= 119: `UHA_KEEP_OFF_KN`) is the no-split-K forward followed by the
+recompute sweep.  No case can afford it as one call (2 K n > 27 000 evaluations of a 3220-wide network, and float64 autograd
+through them); its two halves are pinned separately, the forward by the uha-* cases at form 0 and the sweep by the uha-rc-*
+and uha-w3332-* cases.
 
 Blocks (`blocks`): every leaf cut where different code writes it, each block scaled by its own maximum — see `blocks`.
 Bars (`bars`): DESIGN.md section 2, "Gradients at d = 1600".  The reference of the bars is the restatement's own float32 against
@@ -105,6 +131,18 @@ CASES = [
     ("uha-n21", UHA, 21, 2, 0, {}),
     ("uha-n33", UHA, 33, 2, 0, {}),
     ("uha-n52", UHA, 52, 1, 0, {}),
+    # ---- 2nd order: the split-K forward and the recompute sweep, pinned (form 3) ...
+    ("uha-rc-n1", UHA, 1, 2, 3, {}),
+    ("uha-rc-n20", UHA, 20, 2, 3, {}),
+    ("uha-rc-n21", UHA, 21, 1, 3, {}),
+    ("uha-rc-n33", UHA, 33, 3, 3, {}),
+    ("uha-rc-n65", UHA, 65, 2, 3, {}),
+    # ---- ... by the library's own choice (IN = 3332), at the last no-split-K width (3328), and the kept path at ragged widths
+    ("uha-w3332-5", UHA, 5, 2, 0, dict(emb_dim=132)),
+    ("uha-w3332-37", UHA, 37, 2, 0, dict(emb_dim=132)),
+    ("uha-w3328-20", UHA, 20, 2, 0, dict(emb_dim=128)),
+    ("uha-w3212-37", UHA, 37, 2, 0, dict(emb_dim=12)),
+    ("uha-w3204-20", UHA, 20, 2, 0, dict(emb_dim=4)),
 ]
 IDS = [c[0] for c in CASES]
 PARAM_SETS = ("sparse", "dense")
@@ -117,7 +155,10 @@ PASSES = {
     "var-n17": [17], "var-n21": [21], "var-n33": [32, 1], "var-n52": [32, 20], "var-w1612": [21],
     "ulasn-n17": [17], "ulasn-n33": [32, 1], "ulasn-n52": [32, 20], "ula-n6": [6], "ula-n20": [20], "ula-n33": [32, 1],
     "uha-n16": [16], "uha-n17": [17], "uha-n20": [20], "uha-n21": [21], "uha-n33": [32, 1], "uha-n52": [32, 20],
+    "uha-rc-n1": [1], "uha-rc-n20": [20], "uha-rc-n21": [21], "uha-rc-n33": [32, 1], "uha-rc-n65": [32, 32, 1],
+    "uha-w3332-5": [5], "uha-w3332-37": [32, 5], "uha-w3328-20": [20], "uha-w3212-37": [32, 5], "uha-w3204-20": [20],
 }
+UHA_IDS = [c[0] for c in CASES if c[1] == UHA]
 
 
 def case_by_id(cid):
@@ -132,6 +173,52 @@ def passes_of(n):
 def gemm_of(m):
     """Which product kernel a pass of m rows takes on kept activations."""
     return "nsk" if m <= 16 else "merged" if m <= 20 else "split-k"
+
+
+# ---- the 2nd-order mode's launch rules, restated from cmcd_lgcp.hip (lgcp_uha_nsk_ok, lgcp_uha_grad_ws)
+NSK_CHUNKS = 104                # kNskChunks: 16-deep chunks of a packed operand
+KEEP_FLOATS = 1 << 28           # cap of the tables the forward keeps for the sweep
+
+
+def uha_nsk_ok(dim, emb_dim, form):
+    """lgcp_uha_nsk_ok: the no-split-K forward serves d <= 1664 in whole 16-column tiles and widths up to two rounds of chunks."""
+    return form != 3 and dim % 16 == 0 and dim <= 16 * NSK_CHUNKS and 2 * dim + emb_dim <= 32 * NSK_CHUNKS
+
+
+def uha_keep_floats(dim, emb_dim, K, n):
+    """Floats of the kept tables (lgcp_uha_grad_ws): pre1, pre2 [2 K n][IN], sn [2 K n][D], kr [(K + 1) n][D]; u1 / u2 go to the
+    tables the sweep has anyway."""
+    IN, R = 2 * dim + emb_dim, 2 * K * n
+    return R * (2 * IN + dim) + (K + 1) * n * dim
+
+
+def uha_route(dim, emb_dim, K, n, form):
+    """-> (forward, sweep) of a 2nd-order gradient call: "nsk" / "split-k", "kept" / "recompute"."""
+    nsk = uha_nsk_ok(dim, emb_dim, form)
+    kept = nsk and uha_keep_floats(dim, emb_dim, K, n) <= KEEP_FLOATS
+    return "nsk" if nsk else "split-k", "kept" if kept else "recompute"
+
+
+def route_of(case):
+    _, mode, n, K, form, over = case
+    assert mode == UHA
+    return uha_route(D, over.get("emb_dim", 20), K, n, form)
+
+
+# what each 2nd-order case says about its route (tests/test_oracle_lgcp_grad.py re-derives it)
+UHA_ROUTES = {
+    "uha-n16": ("nsk", "kept"), "uha-n17": ("nsk", "kept"), "uha-n20": ("nsk", "kept"), "uha-n21": ("nsk", "kept"),
+    "uha-n33": ("nsk", "kept"), "uha-n52": ("nsk", "kept"),
+    "uha-rc-n1": ("split-k", "recompute"), "uha-rc-n20": ("split-k", "recompute"), "uha-rc-n21": ("split-k", "recompute"),
+    "uha-rc-n33": ("split-k", "recompute"), "uha-rc-n65": ("split-k", "recompute"),
+    "uha-w3332-5": ("split-k", "recompute"), "uha-w3332-37": ("split-k", "recompute"),
+    "uha-w3328-20": ("nsk", "kept"), "uha-w3212-37": ("nsk", "kept"), "uha-w3204-20": ("nsk", "kept"),
+}
+# Width 3220: the tables are K n (2 (2 IN + D) + D) + n D = 17 680 K n + 1600 n floats, so where `keep` turns off depends on K n
+# and, weakly, on n.  The first K n at which it is off: 13 924 at K = 1, 15 183 as n -> 1; at the configuration's K = 128 the
+# first n is 119 (K n = 15 232).  (Asserted on the CPU from uha_keep_floats.)
+UHA_KEEP_OFF_KN = dict(k1=13924, any=15183)
+UHA_KEEP_OFF_N_AT_K128 = 119
 
 
 def seeds_of(case):
@@ -234,9 +321,11 @@ def reference(case, param_set):
 # ------------------------------------------------------------------------------------------ blocks
 def blocks(un, flat):
     """-> [(name, array view, covers)]: the leaves of a flat gradient cut where different code writes them.
-      W1                 state rows [:D] ([:2D] in the 2nd-order mode: lgcp_tn_gemm_kernel, X^T dA1) against the emb_dim
-                         embedding rows (launch_geffner_tails, out of the S table), each split at the last emb_dim columns (they
-                         sit behind the last full 16- and 128-column tile);
+      W1                 state rows [:D] (lgcp_tn_gemm_kernel, X^T dA1) against the emb_dim embedding rows
+                         (launch_geffner_tails, out of the S table), each split at the last emb_dim columns (they sit behind the
+                         last full 16- and 128-column tile); in the 2nd-order mode the state rows are `W1.z` [:D] and `W1.rho`
+                         [D:2D]: the two halves of XIN's rows are written by different code (lgcp_uha_xin_kernel /
+                         lgcp_uha_gather_kernel copy z once and rho, rho' apart), and the rho rows are the smaller ones;
       W2, b1, b2         the same column split;
       W3, b3             the last 64 columns (the last column block of cbD) against the rest;
       emb                per row (one per time index);
@@ -253,7 +342,13 @@ def blocks(un, flat):
         if name in ("W1", "W2", "b1", "b2"):
             IN = shape[-1]
             emb = un.shape("sn", "emb")[1]
-            rows = [("", slice(None))] if name != "W1" else [(".state", slice(0, IN - emb)), (".emb", slice(IN - emb, IN))]
+            d = un.shape("vd", "mean")[0]
+            if name != "W1":
+                rows = [("", slice(None))]
+            elif IN - emb == d:
+                rows = [(".state", slice(0, d)), (".emb", slice(d, IN))]
+            else:
+                rows = [(".z", slice(0, d)), (".rho", slice(d, 2 * d)), (".emb", slice(2 * d, IN))]
             for rn, rs in rows:
                 sub = a[rs] if a.ndim == 2 else a
                 out.append((name + rn + ".cols", sub[..., :IN - emb], True))
@@ -338,6 +433,14 @@ def bars(case, param_set):
     """-> (bar of a block by name, [lost blocks]) from the stored gaps; an unlisted block has a gap below 1.5 x LISTED."""
     listed = stored_gap(case, param_set)["blocks"]
     return (lambda name: bar_of(listed.get(name, LISTED))), sorted(k for k, g in listed.items() if g > LOST)
+
+
+def uha_loss_bars():
+    """-> (bar of the worst-particle loss error, bar of z_error) of every 2nd-order case: FACTOR x the largest float32 gap of
+    that metric the golden file stores for any uha-* case.  helpers.compare_losses' 1e-3 of a loss of 1e3 .. 1e4 nats is several
+    nats: a missing column's term would pass it.  tests/test_oracle_lgcp_grad.py holds both within a quarter of that bar."""
+    gaps = [stored_gaps()[cid][ps] for cid in UHA_IDS for ps in PARAM_SETS]
+    return FACTOR * max(g["loss"] for g in gaps), FACTOR * max(g["z"] for g in gaps)
 
 
 def compare_blocks(case, param_set, un, flat, flat_ref, tag=""):

@@ -88,6 +88,12 @@ def test_lgcp_cases_reach_what_they_are_there_for():
     assert f["lgcp-n33"]["lanes"] == 2 and f["lgcp-fwd-n33"]["lanes"] == 2 and f["lgcp-n33"]["kept"]
     assert f["lgcp-rc-n21"]["kept"] is False and f["lgcp-rc-n21"]["side_streams"] and f["lgcp-rc-n21"]["lanes"] == 1
     assert f["lgcp-uha-n33"]["passes"] == [32, 1] and not f["lgcp-uha-n33"]["side_streams"]
+    # the 2nd-order mode's other sequence: pinned by its form, nothing kept, both passes on the caller's stream
+    rc = f["lgcp-uha-rc-n33"]
+    assert rc["passes"] == [32, 1] and rc["lanes"] == 1 and rc["kept"] is False and not rc["side_streams"] and not rc["wide"]
+    assert cc.case_by_id("lgcp-uha-rc-n33")[2].resolve() == lc.case_by_id("uha-rc-n33") and lc.case_by_id("uha-rc-n33")[4] == 3
+    assert lc.UHA_ROUTES["uha-rc-n33"] == ("split-k", "recompute") and lc.UHA_ROUTES["uha-n33"] == ("nsk", "kept")
+    assert cc.case_by_id("lgcp-uha-rc-n33")[1] == "lgcp_forked_streams"                  # the function that takes > 1 pass
     assert f["lgcp-wide-n230"]["wide"] and not f["lgcp-fwd-n33"]["wide"]
     assert lc.LGCP_PASS == 32 and cc.LGCP_WIDE_MIN > 129
 

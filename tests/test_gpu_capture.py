@@ -44,8 +44,9 @@ def test_lgcp_forked_streams(hip_lib, monkeypatch, cid):
     """d = 1600 beyond one pass or with the recompute: the forward's lanes and the sweep's recompute run on side streams forked
     from and joined to the caller's by events, so the captured graph has parallel branches and the side streams' memsets are
     nodes of it; lgcp_grad and lgcp_uha_grad clear their per-pass accumulators at `base > 0`; the wide-batch forward.  Runs with
-    the process's own queue count; sets no environment variable.  (uha-n33 and the wide call stay on one stream: they are here
-    for their pass count and their size.)"""
+    the process's own queue count; sets no environment variable.  (uha-n33, uha-rc-n33 and the wide call stay on one stream: they
+    are here for their pass count and their size.  uha-rc-n33 is the 2nd-order mode's split-K forward, whose counter clear is a
+    zeroing launch, and its recompute sweep.)"""
     facts = cc.LGCP_FACTS[cid]
     assert facts["side_streams"] or facts["wide"] or len(facts["passes"]) > 1
     cc.run_case(cid, monkeypatch)

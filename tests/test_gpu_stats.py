@@ -287,7 +287,8 @@ def test_second_order_funnel_on_8_particle_tiles(hip_lib, param_set, monkeypatch
     (230, 0, "MCD_CAIS_sn", "lgcp wide-batch"),                     # the wide-batch form by the library's choice
     (20, 3, "MCD_CAIS_sn", "lgcp launch sequence"),                 # the split-K sequence
     (257, 2, "MCD_CAIS_sn", "lgcp wide-batch"),                     # wide, forced: 256 -> 257 records
-    (20, 0, UHA, "lgcp launch sequence")])                          # the 2nd-order sequence
+    (20, 0, UHA, "lgcp launch sequence"),                           # the 2nd-order sequence
+    (33, 3, UHA, "lgcp launch sequence")])                          # ... its split-K form: records per pass at partials + base * CMCD_NSTATS
 def test_lgcp_records(hip_lib, monkeypatch, n, variant, mode, kernel):
     """d = 1600, K = 2: one record per particle; losses of magnitude 1e3 .. 1e4 — the hard case for the sum of squares."""
     over = dict(nbridges=2, boundmode=mode, **(dict(init_eps=0.02, init_gamma=5.0) if mode == UHA else {}))

@@ -308,12 +308,15 @@ def test_training_lowers_the_loss(hip_lib):
 
 
 # ---------------------------------------------------------------------------------------------- lgcp (d = 1600)
-@pytest.mark.parametrize("n,k", [(20, 8), (5, 3), (40, 2), (20, 32), (20, 128)])
-def test_lgcp_matches_oracle(hip_lib, param_set, n, k):
+@pytest.mark.parametrize("n,k,form", [(20, 8, 0), (5, 3, 0), (40, 2, 0), (20, 32, 0), (20, 128, 0),
+                                      (5, 3, 3), (40, 2, 3), (20, 32, 3)],     # form 3: the split-K sequence (lgcp_uha_forward)
+                         ids=["20-8", "5-3", "40-2", "20-32", "20-128", "5-3-form3", "40-2-form3", "20-32-form3"])
+def test_lgcp_matches_oracle(hip_lib, param_set, monkeypatch, n, k, form):
     """d = 1600, geffner net on concat(z, rho): width 2 * 1600 + 20 = 3220 (the reference's lgcp runs of this mode,
     /root/reference/src/notebooks/plotting_rebuttal.ipynb:3538-3548).  40 particles = two passes of the 32-row GEMM;
     (20, 128) is the configuration's own size (BASELINE.json configs[4] on this mode; /root/reference/src/mcd_under_lp_a_cais.py:42-88)."""
     from helpers import lgcp_counts_fixture
+    monkeypatch.setattr(mcdbm, "KERNEL_VARIANT", form)
     counts = lgcp_counts_fixture()
     b = synthetic.build("lgcp_n20_k128", device="cuda", lgcp_counts=counts, boundmode=MODE, nbridges=k, init_eps=0.02,
                         init_gamma=5.0)
@@ -324,7 +327,7 @@ def test_lgcp_matches_oracle(hip_lib, param_set, n, k):
     torch.cuda.synchronize()
     l_ref, z_ref = run_oracle(b, seeds, dtype=np.float64, lgcp_counts=counts)
     rep = compare_losses(losses.cpu().numpy(), l_ref, z.cpu().numpy(), z_ref, tag=f"UHA lgcp n={n} k={k}", K=k)
-    print("UHA lgcp", n, k, rep, "mean loss", float(val), l_ref.mean())
+    print("UHA lgcp", n, k, form, rep, "mean loss", float(val), l_ref.mean())
     assert abs(float(val) - losses.double().mean().item()) <= 1e-5 * abs(l_ref.mean())
 
 
