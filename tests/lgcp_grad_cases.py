@@ -443,14 +443,15 @@ def uha_loss_bars():
     return FACTOR * max(g["loss"] for g in gaps), FACTOR * max(g["z"] for g in gaps)
 
 
-def compare_blocks(case, param_set, un, flat, flat_ref, tag=""):
+def compare_blocks(case, param_set, un, flat, flat_ref, tag="", bars_of=None, errors_of=None):
     """Every block of the HIP gradient against the reference under `bars`; a block whose reference is exactly zero must be
     exactly zero.  A bar is relative to the block's own maximum, whatever its size (no escape for small blocks: the tiny ones the
     golden file names get the same rule, i.e. an absolute bar of bar x their maximum, FACTOR x the float32 gap where that
-    counts).  -> ({block: error / scale}, [failures])."""
-    bar, lost = bars(case, param_set)
+    counts).  `bars_of` / `errors_of`: another table's `bars` and `block_errors` under the same rule (tests/grad_blocks.py: the
+    small-d gradients and their cut).  -> ({block: error / scale}, [failures])."""
+    bar, lost = (bars_of or bars)(case, param_set)
     rep, bad = {}, []
-    for name, (e, s) in block_errors(un, flat, flat_ref).items():
+    for name, (e, s) in (errors_of or block_errors)(un, flat, flat_ref).items():
         if s == 0.0:
             if e != 0.0:
                 bad.append("%s: expected exactly zero, got up to %.3e" % (name, e))

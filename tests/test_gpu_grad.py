@@ -1,5 +1,8 @@
 """Gradients of the HIP path — VarGrad (compute_log_var_grad) and the reparameterised MCD_CAIS_sn gradient
-(compute_bound_grad) — vs torch-autograd on the float64 restatement."""
+(compute_bound_grad) — vs torch-autograd on the float64 restatement.
+
+The cases, their ids and the float64 references (once per (case, parameter set)) come from tests/grad_blocks.py; every comparison
+holds the per-leaf 2e-3 bar and the cosine, and on top of them every block of that file's cut to its own bar."""
 import numpy as np
 import pytest
 import torch
@@ -7,6 +10,8 @@ import torch
 from cmcd_amd import mcdboundingmachine as mcdbm
 from cmcd_amd import synthetic
 from oracle import cmcd_oracle_torch as ot
+
+import grad_blocks as gb
 
 pytestmark = pytest.mark.gpu
 
@@ -41,20 +46,7 @@ def oracle_grad_flat(b, seeds):
     return val, losses, flat
 
 
-CASES = [
-    ("many_gmm_n2000_k256_dds", 96, dict(boundmode="MCD_CAIS_var_sn", nbridges=8, init_sigma=15.0)),
-    ("many_gmm_n2000_k256_dds", 50, dict(boundmode="MCD_CAIS_var_sn", nbridges=5, init_sigma=15.0, eps_schedule="linear",
-                                         init_eps=0.3)),
-    ("gmm_n300_k8", 128, dict(boundmode="MCD_CAIS_var_sn", grad_clipping=True)),
-    ("funnel_n300_k64", 70, dict(boundmode="MCD_CAIS_var_sn", nbridges=6)),
-    ("funnel_n300_k64", 40, dict(boundmode="MCD_CAIS_var_sn", nbridges=5, emb_dim=20)),          # the default emb_dim: width 30 -> 64
-    ("funnel_n300_k64", 40, dict(boundmode="MCD_CAIS_var_sn", nbridges=5, nn_arch="dds")),
-    ("many_gmm_var_n16000_k256", 64, dict(nbridges=6, emb_dim=20)),
-    ("many_gmm_var_n16000_k256", 80, dict(nbridges=5)),                  # 132-wide net (config 4), 3-wave groups
-    ("many_gmm_var_n16000_k256", 60, dict(nbridges=6, emb_dim=40)),      # the reference README's example width (42 -> padded to 64)
-    ("many_gmm_var_n16000_k256", 40, dict(nbridges=4, emb_dim=70)),      # width 72 -> padded to 144
-    ("gmm_n300_k8", 40, dict(boundmode="MCD_CAIS_var_sn", nbridges=4, emb_dim=90)),   # 9 tiles on gmm
-]
+CASES = gb.rows("var")       # (config, particles, overrides): tests/grad_blocks.py, VAR_CASES
 
 
 @pytest.mark.parametrize("item", [0, 1])
@@ -68,29 +60,18 @@ def test_vargrad_matches_autograd(hip_lib, param_set, monkeypatch, name, n, over
                                                    b["params_fixed"], b["target"], eps_schedule=b["eps_schedule"],
                                                    grad_clipping=b["grad_clipping"])
     torch.cuda.synchronize()
-    val, l_ref, g_ref = oracle_grad_flat(b, seeds)
+    cid = gb.cid_of("var", name, n, over)
+    val, l_ref, g_ref = gb.reference_torch(cid, param_set)
     assert np.isfinite(l_ref).all(), "pick a case without +inf particles for the gradient check"
-    g = grad.double().cpu()
-    un = b["unflatten"]
-    worst = {}
-    for path, (off, shape) in un.layout.items():
-        numel = max(1, int(np.prod(shape)))
-        a, r = g[off:off + numel], g_ref[off:off + numel]
-        scale = max(float(r.abs().max()), 1e-12)
-        err = float((a - r).abs().max())
-        worst["/".join(map(str, path))] = (err / scale, scale)
-        if float(r.abs().max()) == 0.0:
-            assert float(a.abs().max()) == 0.0, f"{path}: expected exactly zero gradient"
-    bad = {k: v for k, v in worst.items() if v[0] > 2e-3 and v[1] > 1e-9}
-    print(name, over, {k: "%.1e" % v[0] for k, v in worst.items()})
-    assert not bad, f"gradient mismatch (max abs err / max |ref|, max |ref|): {bad}"
-    cos = float((g * g_ref).sum() / (g.norm() * g_ref.norm()))
-    assert cos > 1 - 1e-5
+    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref, blocks=(cid, param_set))
 
 
-def _compare(name, over, un, g, g_ref, tol=2e-3):
+def _compare(name, over, un, g, g_ref, tol=2e-3, blocks=None):
     """`tol`: the bar of every leaf, or {leaf name ("vd/mean", "sn/nn/0/0", ...): bar} for the leaves that have one of their
-    own (tests/trained_cases.py) — every other leaf keeps 2e-3."""
+    own (tests/trained_cases.py) — every other leaf keeps 2e-3.
+    `blocks`: (case id, parameter set) of tests/grad_blocks.py — on top of the leaf bars and the cosine, every block of that
+    file's cut is held to its own bar (from the stored float32 gap of the restatement, never from `g`)."""
+    block_failures = gb.report_blocks(*blocks, un, g, g_ref) if blocks is not None else []
     own = tol if isinstance(tol, dict) else {}
     tol = 2e-3 if isinstance(tol, dict) else tol
     worst = {}
@@ -106,25 +87,11 @@ def _compare(name, over, un, g, g_ref, tol=2e-3):
     assert not bad, f"gradient mismatch (max abs err / max |ref|, max |ref|): {bad}"
     cos = float((g * g_ref).sum() / (g.norm() * g_ref.norm()))
     assert cos > 1 - 1e-5
+    assert not block_failures, block_failures
 
 
 # the reparameterised gradient: no stop_gradient, back-propagation through all K steps
-BPTT_CASES = [
-    ("many_gmm_n2000_k256_dds", 96, dict(nbridges=8, init_sigma=15.0)),                      # clipping on, cos_sq
-    ("many_gmm_n2000_k256_dds", 50, dict(nbridges=5, init_sigma=15.0, eps_schedule="linear", init_eps=0.3,
-                                         grad_clipping=False)),
-    ("many_gmm_n2000_k256_dds", 40, dict(nbridges=24, init_sigma=15.0, init_eps=0.2)),        # longer chain
-    ("gmm_n300_k8", 128, dict()),                                                             # geffner 22
-    ("gmm_n300_k8", 64, dict(nn_arch="dds", grad_clipping=True)),
-    ("funnel_n300_k64", 70, dict(nbridges=6)),                                                # d = 10, geffner 58
-    ("funnel_n300_k64", 40, dict(nbridges=5, emb_dim=20)),                                    # default emb_dim (width 30 -> 64)
-    ("funnel_n300_k64", 40, dict(nbridges=5, nn_arch="dds")),
-    ("many_gmm_n2000_k256_dds", 64, dict(nbridges=6, nn_arch="geffner", emb_dim=20, init_sigma=15.0, init_eps=0.3)),
-    ("many_gmm_n2000_k256_dds", 48, dict(nbridges=5, nn_arch="geffner", emb_dim=40, init_sigma=15.0, init_eps=0.3)),   # width 42 -> 64
-    ("gmm_n300_k8", 50, dict(emb_dim=7)),                                                                              # width 9 -> 32
-    ("many_gmm_n2000_k256_dds", 40, dict(nbridges=4, nn_arch="geffner", emb_dim=100, init_sigma=15.0, init_eps=0.3)),  # width 102 -> 144
-    ("gmm_n300_k8", 40, dict(nbridges=4, emb_dim=130)),                                                                # 9 tiles, gmm
-]
+BPTT_CASES = gb.rows("sn")     # tests/grad_blocks.py, BPTT_CASES
 
 
 @pytest.mark.parametrize("variant,item", [(1, 0), (2, 0), (1, 1), (2, 1), (3, 1)])
@@ -147,32 +114,38 @@ def test_reparameterised_gradient_matches_autograd(hip_lib, param_set, monkeypat
             pytest.skip("no cooperative instance for this net")
         raise
     torch.cuda.synchronize()
-    val, l_ref, g_ref = oracle_grad_flat(b, seeds)
+    cid = gb.cid_of("sn", name, n, over)
+    val, l_ref, g_ref = gb.reference_torch(cid, param_set)
     assert np.isfinite(l_ref).all(), "pick a case without +inf particles for the gradient check"
     np.testing.assert_allclose(losses.cpu().numpy(), l_ref, rtol=2e-3, atol=2e-3)
-    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref)
+    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref, blocks=(cid, param_set))
 
 
 @pytest.mark.parametrize("item", [0, 1])
 @pytest.mark.parametrize("mode", ["MCD_CAIS_sn", "MCD_CAIS_var_sn"])
 @pytest.mark.parametrize("n,K", [(1, 1), (17, 2), (3, 1), (33, 3)])
 def test_gradient_edge_shapes(hip_lib, monkeypatch, mode, n, K, item):
-    """Single particle, single bridge, ragged last tile — both gradients, both kernel paths."""
+    """Single particle, single bridge, ragged last tile — both gradients, both kernel paths, both parameter sets; the flat
+    gradient against its largest entry, and every block of tests/grad_blocks.py's cut against its own bar."""
     monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
-    b = synthetic.build("gmm_n300_k8", device="cuda", boundmode=mode, nbridges=K)
-    seeds = synthetic.parity_seeds(n)
-    fn = mcdbm.compute_bound_grad if mode == "MCD_CAIS_sn" else mcdbm.compute_log_var_grad
-    grad, (losses, z) = fn(torch.from_numpy(seeds).cuda(), b["params_flat"], b["unflatten"], b["params_fixed"],
-                           b["target"], eps_schedule=b["eps_schedule"], grad_clipping=b["grad_clipping"])
-    torch.cuda.synchronize()
-    val, l_ref, g_ref = oracle_grad_flat(b, seeds)
-    np.testing.assert_allclose(losses.cpu().numpy(), l_ref, rtol=2e-3, atol=2e-3)
-    g = grad.double().cpu()
-    if n == 1 and mode == "MCD_CAIS_var_sn":
-        assert float(g.abs().max()) == 0.0 and float(g_ref.abs().max()) < 1e-12   # variance of one particle
-        return
-    scale = float(g_ref.abs().max())
-    assert float((g - g_ref).abs().max()) <= 3e-3 * scale, (float((g - g_ref).abs().max()), scale)
+    cid = gb.cid_of("edge", "gmm_n300_k8", n, dict(boundmode=mode, nbridges=K))
+    for param_set in gb.PARAM_SETS:
+        monkeypatch.setattr(synthetic, "DENSE_DEFAULT", param_set == "dense")
+        b = synthetic.build("gmm_n300_k8", device="cuda", boundmode=mode, nbridges=K)
+        seeds = synthetic.parity_seeds(n)
+        fn = mcdbm.compute_bound_grad if mode == "MCD_CAIS_sn" else mcdbm.compute_log_var_grad
+        grad, (losses, z) = fn(torch.from_numpy(seeds).cuda(), b["params_flat"], b["unflatten"], b["params_fixed"],
+                               b["target"], eps_schedule=b["eps_schedule"], grad_clipping=b["grad_clipping"])
+        torch.cuda.synchronize()
+        val, l_ref, g_ref = gb.reference_torch(cid, param_set)
+        np.testing.assert_allclose(losses.cpu().numpy(), l_ref, rtol=2e-3, atol=2e-3)
+        g = grad.double().cpu()
+        if n == 1 and mode == "MCD_CAIS_var_sn":
+            assert float(g.abs().max()) == 0.0 and float(g_ref.abs().max()) < 1e-12   # variance of one particle
+            continue
+        scale = float(g_ref.abs().max())
+        assert float((g - g_ref).abs().max()) <= 3e-3 * scale, (float((g - g_ref).abs().max()), scale)
+        gb.assert_blocks(cid, param_set, b["unflatten"], g, g_ref)
 
 
 @pytest.mark.parametrize("item", [0, 1])
@@ -480,11 +453,7 @@ def test_lgcp_vargrad_matches_autograd(hip_lib, param_set, n, K, clip):
     assert not bad, bad
 
 
-ULA_CASES = [
-    ("many_gmm_n2000_k256_dds", 70, dict(nbridges=6, init_sigma=15.0, init_eps=0.2)),
-    ("gmm_n300_k8", 96, dict()),
-    ("funnel_n300_k64", 40, dict(nbridges=5)),
-]
+ULA_CASES = [c[1:] for c in gb.ULA_CASES]     # tests/grad_blocks.py: ids "ulasn-*" with the network, "ula-*" without
 
 
 @pytest.mark.parametrize("variant,item", [(1, 0), (2, 1), (1, 1)])
@@ -500,10 +469,11 @@ def test_ula_sn_gradient_matches_autograd(hip_lib, param_set, monkeypatch, name,
                                                  b["params_fixed"], b["target"], eps_schedule=b["eps_schedule"],
                                                  grad_clipping=b["grad_clipping"])
     torch.cuda.synchronize()
-    val, l_ref, g_ref = oracle_grad_flat(b, seeds)
+    cid = gb.cid_of("ulasn", name, n, over)
+    val, l_ref, g_ref = gb.reference_torch(cid, param_set)
     assert np.isfinite(l_ref).all()
     np.testing.assert_allclose(losses.cpu().numpy(), l_ref, rtol=2e-3, atol=2e-3)
-    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref)
+    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref, blocks=(cid, param_set))
 
 
 @pytest.mark.parametrize("name,n,over", ULA_CASES)
@@ -530,6 +500,8 @@ def test_ula_gradient_matches_autograd(hip_lib, param_set, name, n, over):
         ref = np.asarray(ref, np.float64).reshape(-1)
         got = gh[off:off + ref.size]
         assert np.abs(got - ref).max() <= 2e-3 * max(np.abs(ref).max(), 1e-9), (path, got, ref)
+    cid = gb.cid_of("ula", name, n, over)
+    gb.assert_blocks(cid, param_set, un, gh, gb.reference(cid, param_set)[3])
 
 
 @pytest.mark.parametrize("mode,n,K", [("MCD_ULA_sn", 6, 3), ("MCD_ULA", 37, 3)])
@@ -619,6 +591,9 @@ def test_gradient_with_a_17_component_mixture(hip_lib, param_set, monkeypatch, i
     for leaf in ("mean", "logdiag"):
         off = b["unflatten"].offset("vd", leaf)
         assert np.abs(grad[off:off + 2].double().cpu().numpy() - g["vd"][leaf]).max() <= 2e-3 * np.abs(g["vd"][leaf]).max()
+    cid = gb.MIX17_CASE[0]
+    assert gb.MIX17_CASE[1:] == ("many_gmm_n2000_k256_dds", 80, dict(nbridges=6, n_mixes=17, init_sigma=15.0, init_eps=0.3))
+    gb.assert_blocks(cid, param_set, b["unflatten"], grad, gb.reference(cid, param_set)[3])
 
 
 # ---------------------------------------------------------------------------------------------- the gated cases
@@ -693,7 +668,7 @@ def test_gradient_where_a_gate_acts_matches_autograd(hip_lib, param_set, monkeyp
     compare_losses_with_inf(losses.cpu().numpy(), l_ref)
     if case[0] == "floor-end":
         assert np.isinf(l_ref).any() and bool(torch.isfinite(grad).all())
-    _compare(case[0], case[2], b["unflatten"], grad.double().cpu(), g_ref)
+    _compare(case[0], case[2], b["unflatten"], grad.double().cpu(), g_ref, blocks=("gated-" + case[0], param_set))
 
 
 @pytest.mark.parametrize("case", gc.cases_of(*_GATED_PATHS), ids=lambda c: c[0])

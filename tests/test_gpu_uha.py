@@ -47,7 +47,7 @@ def variant(request, monkeypatch):
 # The oracle's answer for a case does not depend on the kernel form or the gradient path under test: computed once per
 # (case, parameter set) and reused across the variants (the float64 restatement of a 2000 x 256 batch takes ~6 s, the
 # autograd sweep of a 40-bridge case ~8 s — a minute of the suite otherwise).
-_ORACLE_FWD, _ORACLE_GRAD = {}, {}
+_ORACLE_FWD = {}
 
 
 def _case_key(param_set, name, n, over):
@@ -168,29 +168,17 @@ def test_key_chain_and_deviates_are_bit_exact(hip_lib, variant, name, n, K):
 
 
 # ---------------------------------------------------------------------------------------------- gradient
-GRAD_CASES = [
-    ("gmm_n300_k8", 128, {}),                                                               # geffner 24 (2 tiles)
-    ("gmm_n300_k8", 64, dict(nn_arch="dds", init_gamma=3.0)),                               # dds on d = 2
-    ("many_gmm_n2000_k256_dds", 96, dict(nbridges=8, init_eps=0.2, init_gamma=2.0, init_sigma=15.0)),
-    ("many_gmm_n2000_k256_dds", 40, dict(nbridges=24, init_eps=0.1, init_gamma=3.0, init_sigma=15.0)),   # longer chain
-    ("funnel_n300_k64", 70, dict(nbridges=6, init_eps=0.05, init_gamma=4.0)),               # d = 10, geffner 68 (5 tiles)
-    ("funnel_n300_k64", 40, dict(nbridges=5, nn_arch="dds", init_eps=0.05)),                # d = 10: two input tiles
-    ("funnel_n300_k64", 40, dict(nbridges=4, emb_dim=20, init_eps=0.05)),                   # width 40 -> 64
-    ("many_gmm_var_n16000_k256", 80, dict(nbridges=5, init_eps=0.1, init_gamma=3.0)),       # geffner 134 (9 tiles)
-    ("gmm_n300_k8", 50, dict(emb_dim=40, nbridges=5)),                                      # width 44 -> 64
-    ("gmm_n300_k8", 300, dict(nbridges=3)),                                                 # 19 tiles: five workgroups, ragged
-    ("gmm_n300_k8", 20, dict(nbridges=1, nn_arch="dds")),                                   # a single bridge
-    ("gmm_n300_k8", 70, dict(nbridges=40, init_eps=0.05)),                                  # 41 points: ten chunks of work items
-    ("funnel_n300_k64", 50, dict(nbridges=19, init_eps=0.03, init_gamma=4.0)),              # d = 10 in chunks (330-float items)
-]
+import grad_blocks as gb
+
+GRAD_CASES = gb.rows("uha")      # (config, particles, overrides): tests/grad_blocks.py, UHA_CASES
 
 
 @pytest.mark.parametrize("item", [0, 1], ids=["whole_chain", "work_items"])
 @pytest.mark.parametrize("name,n,over", GRAD_CASES)
 def test_reparameterised_gradient_matches_autograd(hip_lib, param_set, variant, monkeypatch, name, n, over, item):
     _skip_without_instance(variant, name, over)
-    if variant != 3 and GRAD_CASES.index((name, n, over)) not in (0, 2, 4, 7):
-        pytest.skip("the wave-per-tile and 8-particle forwards keep the trajectory for four representative cases (suite time)")
+    if variant != 3 and GRAD_CASES.index((name, n, over)) not in (0, 2, 4, 7, 13):
+        pytest.skip("the wave-per-tile and 8-particle forwards keep the trajectory for five representative cases (suite time)")
     if item and variant != 3:
         pytest.skip("the work-item path (Jacobian launch, scan, chunked sweep) reads the same kept trajectory whatever forward "
                     "wrote it")
@@ -198,20 +186,18 @@ def test_reparameterised_gradient_matches_autograd(hip_lib, param_set, variant, 
     monkeypatch.setenv("CMCD_GRAD_ITEM", str(item))
     """jax.grad(compute_bound, 1) (/root/reference/src/main.py:174-176) through mcd_under_lp_a_cais.py:42-88: every leaf of
     params_flat (network, eps, gamma, q, mgridref_y) against torch-autograd through the float64 restatement."""
-    from test_gpu_grad import _compare, oracle_grad_flat
+    from test_gpu_grad import _compare
     b = synthetic.build(name, device="cuda", boundmode=MODE, **over)
     seeds = synthetic.parity_seeds(n)
     grad, (losses, z) = mcdbm.compute_bound_grad(torch.from_numpy(seeds).cuda(), b["params_flat"], b["unflatten"],
                                                  b["params_fixed"], b["target"], eps_schedule=b["eps_schedule"],
                                                  grad_clipping=b["grad_clipping"])
     torch.cuda.synchronize()
-    key = _case_key(param_set, name, n, over)
-    if key not in _ORACLE_GRAD:
-        _ORACLE_GRAD[key] = oracle_grad_flat(b, seeds)
-    val, l_ref, g_ref = _ORACLE_GRAD[key]
+    cid = gb.cid_of("uha", name, n, over)
+    val, l_ref, g_ref = gb.reference_torch(cid, param_set)      # once per (case, parameter set)
     assert np.isfinite(l_ref).all(), "pick a case without +inf particles for the gradient check"
     np.testing.assert_allclose(losses.double().cpu().numpy(), l_ref, rtol=2e-3, atol=2e-3)
-    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref)
+    _compare(name, over, b["unflatten"], grad.double().cpu(), g_ref, blocks=(cid, param_set))
     assert float(g_ref[b["unflatten"].offset("gamma")].abs()) > 0     # the friction is a trained leaf in this mode
 
 
@@ -230,7 +216,7 @@ def test_gradient_where_a_gate_acts_matches_autograd(hip_lib, param_set, variant
     grad, losses = gated_call(b, case)
     compare_losses_with_inf(losses.cpu().numpy(), l_ref)
     assert bool(torch.isfinite(grad).all())
-    _compare(case[0], case[2], b["unflatten"], grad.double().cpu(), g_ref)
+    _compare(case[0], case[2], b["unflatten"], grad.double().cpu(), g_ref, blocks=("gated-" + case[0], param_set))
     assert float(g_ref[b["unflatten"].offset("gamma")].abs()) > 0
 
 
