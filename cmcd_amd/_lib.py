@@ -153,6 +153,20 @@ def lib():
         L.cmcd_bound_reverse_hais.argtypes = [
             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HaisLayout), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
             C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmcd_segment_ldvi_workspace_bytes.restype = C.c_int64
+        L.cmcd_segment_ldvi_workspace_bytes.argtypes = [C.POINTER(Desc), C.c_int32, C.c_int64]
+        L.cmcd_bound_segment_ldvi.restype = C.c_int
+        L.cmcd_bound_segment_ldvi.argtypes = [
+            C.POINTER(Desc), C.POINTER(Layout), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p]
+        L.cmcd_segment_hais_workspace_bytes.restype = C.c_int64
+        L.cmcd_segment_hais_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+        L.cmcd_bound_segment_hais.restype = C.c_int
+        L.cmcd_bound_segment_hais.argtypes = [
+            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HaisLayout), C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmcd_adam_step.restype = C.c_int
         L.cmcd_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_float,

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libcmcd_hip.so")
-SOURCES = ["cmcd_api.hip", "cmcd_kernels.hip", "cmcd_uha.hip", "cmcd_reverse.hip", "cmcd_segment.hip", "cmcd_segment_uha.hip", "cmcd_reverse_uha.hip", "cmcd_coop.hip", "cmcd_coop_wide.hip", "cmcd_lgcp.hip", "cmcd_lgcp_wide.hip", "cmcd_grad.hip", "cmcd_bptt.hip", "cmcd_mfvi.hip", "cmcd_hais.hip", "cmcd_hais_lgcp.hip", "cmcd_ldvi.hip", "cmcd_reverse_ldvi.hip", "cmcd_reverse_hais.hip", "cmcd_opt.hip", "cmcd_resample.hip", "cmcd_sinkhorn.hip"]
+SOURCES = ["cmcd_api.hip", "cmcd_kernels.hip", "cmcd_uha.hip", "cmcd_reverse.hip", "cmcd_segment.hip", "cmcd_segment_uha.hip", "cmcd_reverse_uha.hip", "cmcd_coop.hip", "cmcd_coop_wide.hip", "cmcd_lgcp.hip", "cmcd_lgcp_wide.hip", "cmcd_grad.hip", "cmcd_bptt.hip", "cmcd_mfvi.hip", "cmcd_hais.hip", "cmcd_hais_lgcp.hip", "cmcd_ldvi.hip", "cmcd_reverse_ldvi.hip", "cmcd_reverse_hais.hip", "cmcd_segment_ldvi.hip", "cmcd_segment_hais.hip", "cmcd_opt.hip", "cmcd_resample.hip", "cmcd_sinkhorn.hip"]
 HEADERS = ["cmcd_device.h", os.path.join(ROOT, "include", "cmcd_hip.h"), os.path.join(ROOT, "include", "cmcd_hip_diag.h")]
 # Per-file flags.  cmcd_kernels.hip holds the wave-per-tile trajectory kernel, which is VALU-issue bound at 4 waves per
 # SIMD: there a packed fp32 instruction holds the pipe ~1.8x as long as a plain one and the SLP vectoriser pays v_mov
@@ -30,6 +30,8 @@ EXTRA_FLAGS = {"cmcd_kernels.hip": ["-fno-slp-vectorize"],
                "cmcd_ldvi.hip": ["-fno-slp-vectorize"],   # LDVI: the same wave-per-tile mapping and network evaluation as cmcd_uha.hip
                "cmcd_reverse_ldvi.hip": ["-fno-slp-vectorize"],   # the mapping and network evaluation of cmcd_ldvi.hip
                "cmcd_reverse_hais.hip": ["-fno-slp-vectorize"],   # the mapping of cmcd_hais.hip
+               "cmcd_segment_ldvi.hip": ["-fno-slp-vectorize"],   # the mapping and network evaluation of cmcd_ldvi.hip
+               "cmcd_segment_hais.hip": ["-fno-slp-vectorize"],   # the mapping of cmcd_hais.hip
                # Jacobian / scan kernels of the work-item reparameterised gradient: -11 % / -5 % without SLP (cmcd_bptt.hip)
                "cmcd_bptt.hip": ["-fno-slp-vectorize"]}
 

@@ -243,11 +243,12 @@ static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_
 //   reverse-uha: the forward layout once more (the reverse-time chain of MCD_CAIS_UHA_sn); that mode only, no lgcp
 //   reverse-ldvi: the forward layout of LDVI's effective descriptor (cmcd_ldvi_bound_grad's), no gradient part; no lgcp
 //   reverse-hais: [one statistics record per 16-particle tile] (HaisReversePlan below: UHA has no tables and no descriptor)
+//   segment-ldvi, segment-hais: the layouts of reverse-ldvi and reverse-hais (bridges [k0, k1) from a state with momentum)
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
 // ------------------------------------------------------------------------------------------
 enum PlanKind { PLAN_FORWARD, PLAN_VAR_GRAD, PLAN_BOUND_GRAD, PLAN_REVERSE, PLAN_SEGMENT, PLAN_SEGMENT_UHA, PLAN_REVERSE_UHA,
-                PLAN_REVERSE_LDVI };
+                PLAN_REVERSE_LDVI, PLAN_SEGMENT_LDVI };
 
 struct CallPlan {
   cmcd_desc d;      // effective descriptor: the caller's, with what its mode fixes
@@ -319,6 +320,13 @@ static int make_plan(const cmcd_desc& desc, int64_t n, int64_t n_target, PlanKin
     if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain has no lgcp kernel%s");
     if (!reverse_ldvi_available(d, p.w.T, d.mode == CMCD_MODE_CAIS_UHA_SN))
       return fail(CMCD_ERR_UNSUPPORTED, "no LDVI reverse-chain kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
+    p.total = p.need = align4(p.fwd) * 4;
+    return CMCD_OK;
+  }
+  if (kind == PLAN_SEGMENT_LDVI) {   // LDVI's effective descriptor again
+    if (p.lgcp) return fail(CMCD_ERR_UNSUPPORTED, "chain segments have no lgcp kernel%s");
+    if (!segment_ldvi_available(d, p.w.T, d.mode == CMCD_MODE_CAIS_UHA_SN))
+      return fail(CMCD_ERR_UNSUPPORTED, "no LDVI segment kernel instance for this (target, dim, arch, width=%s%lld)", "", p.w.HP);
     p.total = p.need = align4(p.fwd) * 4;
     return CMCD_OK;
   }
@@ -864,6 +872,104 @@ int cmcd_bound_reverse_hais(int32_t target, int32_t dim, int32_t nbridges, int32
   snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_hais_kernel");
   rc = reverse_hais_launch(target, dim, nbridges, lfsteps, *lay, seeds, x, n, params, target_consts, n_mix, ws, out_w, out_z0,
                            out_rho0, stream);
+  if (rc != CMCD_OK) return rc;
+  launch_finalize(reinterpret_cast<double*>(ws), (int32_t)((n + 15) / 16), out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+// ---- chain segments of the two momentum baselines (cmcd_segment_ldvi.hip, cmcd_segment_hais.hip): the plans, the layouts and
+// the refusals of their reverse chains, then cmcd_bound_segment_uha's checks on [k0, k1) and the seeds
+static int segment_range(int32_t k0, int32_t k1, int32_t nbridges, const int32_t* seeds) {
+  if (k0 < 0 || k0 >= k1 || k1 > nbridges)
+    return fail(CMCD_ERR_BAD_ARG, "segment bridges must satisfy 0 <= k0 < k1 <= nbridges (got k1 = %s%lld)", "", k1);
+  if (k0 == 0 && !seeds) return fail(CMCD_ERR_BAD_ARG, "a segment that starts at bridge 0 needs seeds%s");
+  return CMCD_OK;
+}
+
+int64_t cmcd_segment_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n) {
+  cmcd_desc e;
+  CallPlan p;
+  if (ldvi_desc(desc, use_net, e) != CMCD_OK || n < 1 || n > (int64_t)1 << 31) return 0;
+  if (make_plan(e, n, 0, PLAN_SEGMENT_LDVI, true, p) != CMCD_OK) return 0;
+  return p.total;
+}
+
+int cmcd_bound_segment_ldvi(const cmcd_desc* desc, const cmcd_layout* lay, int32_t use_net, int32_t k0, int32_t k1,
+                            const int32_t* seeds, int64_t n, const float* params, int64_t n_params, const float* target_consts,
+                            int64_t n_target, void* workspace, int64_t workspace_bytes, float* z_inout, float* rho_inout,
+                            float* wpath_inout, uint32_t* key_inout, float* out_lg, double* out_stats, void* stream_) {
+  cmcd_desc e;
+  int rc = ldvi_desc(desc, use_net, e);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !params || !workspace || !z_inout || !rho_inout || !wpath_inout || !key_inout || !out_lg || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  if ((rc = segment_range(k0, k1, e.nbridges, seeds)) != CMCD_OK) return rc;
+  if (!layout_inside(e, *lay, n_params) || lay->gamma < 0 || lay->gamma >= n_params)
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(e.target, target_consts, n_target)) != CMCD_OK) return rc;
+  CallPlan p, q;   // the layout is this call's, the demand is the size query's (many_gmm: the largest target block)
+  if ((rc = make_plan(e, n, n_target, PLAN_SEGMENT_LDVI, false, p)) != CMCD_OK) return rc;
+  if ((rc = make_plan(e, n, 0, PLAN_SEGMENT_LDVI, true, q)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, q.total)) != CMCD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  launch_prep(e, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(e, *lay, n, n_params, n_target));
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_ldvi_kernel");
+  rc = segment_ldvi_launch(e, *lay, p.w, use_net != 0, k0, k1, seeds, n, params, ws, z_inout, rho_inout, wpath_inout, key_inout,
+                           out_lg, stream);
+  if (rc != CMCD_OK) return rc;
+  launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
+  CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+// UHA: reverse_hais_plan's refusals with the segment call's words for lgcp and a missing instance
+static int segment_hais_plan(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int64_t& floats) {
+  floats = 0;
+  if (nbridges < 1 || lfsteps < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges and lfsteps must be >= 1%s");
+  if (n < 1 || n > (int64_t)1 << 31 || dim < 1) return fail(CMCD_ERR_BAD_ARG, "n or dim out of range%s");
+  if (target == CMCD_TARGET_LGCP)
+    return fail(CMCD_ERR_UNSUPPORTED, "chain segments of UHA have no lgcp kernel (cmcd_hais_lgcp.hip runs whole chains)%s");
+  if (!segment_hais_available(target, dim))
+    return fail(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS segment kernel instance for this (target, dim)%s");
+  if (!reverse_hais_shape_ok(nbridges, lfsteps, n))
+    return fail(CMCD_ERR_UNSUPPORTED, "nbridges above 4096 or nbridges * lfsteps above 2^24%s");
+  floats = reverse_hais_floats(n);
+  return CMCD_OK;
+}
+
+int64_t cmcd_segment_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n) {
+  int64_t floats;
+  return segment_hais_plan(target, dim, nbridges, lfsteps, n, floats) == CMCD_OK ? floats * 4 : 0;
+}
+
+int cmcd_bound_segment_hais(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* lay, int32_t k0,
+                            int32_t k1, const int32_t* seeds, int64_t n, const float* params, int64_t n_params,
+                            const float* target_consts, int64_t n_target, void* workspace, int64_t workspace_bytes, float* z_inout,
+                            float* rho_inout, float* wpath_inout, uint32_t* key_inout, float* out_lg, double* out_stats,
+                            void* stream_) {
+  if (!lay || !params || !workspace || !z_inout || !rho_inout || !wpath_inout || !key_inout || !out_lg || !out_stats)
+    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  int64_t floats;
+  int rc = segment_hais_plan(target, dim, nbridges, lfsteps, n, floats);
+  if (rc != CMCD_OK) return rc;
+  if ((rc = segment_range(k0, k1, nbridges, seeds)) != CMCD_OK) return rc;
+  if (lay->ngrid < 0 || lay->ngrid > 1024) return fail(CMCD_ERR_BAD_ARG, "ngrid out of range (0 .. 1024)%s");
+  auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
+  if (!(inside(lay->vd_mean, dim) && inside(lay->vd_logdiag, dim) && inside(lay->eps, 1) && inside(lay->eta, 1) &&
+        inside(lay->md, dim) && inside(lay->mgridref_y, lay->ngrid + 1) && inside(lay->gridref_x, lay->ngrid + 2) &&
+        inside(lay->target_x, nbridges)))
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  int n_mix = 0;
+  if ((rc = check_many_gmm(target, target_consts, n_target, &n_mix)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(workspace, workspace_bytes, floats * 4)) != CMCD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws = static_cast<float*>(workspace);
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_hais_kernel");
+  rc = segment_hais_launch(target, dim, nbridges, lfsteps, *lay, k0, k1, seeds, n, params, target_consts, n_mix, ws, z_inout,
+                           rho_inout, wpath_inout, key_inout, out_lg, stream);
   if (rc != CMCD_OK) return rc;
   launch_finalize(reinterpret_cast<double*>(ws), (int32_t)((n + 15) / 16), out_stats, stream, nullptr, 0u);
   CMCD_HIP_CHECK(hipGetLastError());

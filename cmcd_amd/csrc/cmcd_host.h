@@ -111,6 +111,23 @@ int reverse_hais_launch(int target, int dim, int32_t nbridges, int32_t lfsteps, 
                         const float* x, int64_t n, const float* params, const float* target_consts, int n_mix, float* ws,
                         float* out_w, float* out_z0, float* out_rho0, hipStream_t stream);
 
+// cmcd_segment_ldvi.hip: bridges [k0, k1) of the LDVI forward chain from (z, rho, wpath, key) (include/cmcd_hip.h:
+// cmcd_bound_segment_ldvi), one wave per 16-particle tile.  `d`, `w` and the tables in ws as for ldvi_launch; seeds are read when
+// k0 == 0; z / rho / wpath / key are read (k0 > 0) and overwritten in place, lg receives log gamma_k1(z) + log N(rho; 0, I), ws +
+// w.partials one statistics record per tile over l := -(wpath + lg).  The instances and the launch rule of ldvi_traj_kernel.
+bool segment_ldvi_available(const cmcd_desc& d, int T, bool use_net);
+int segment_ldvi_launch(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& w, bool use_net, int32_t k0, int32_t k1,
+                        const int32_t* seeds, int64_t n, const float* params, float* ws, float* z, float* rho, float* wpath,
+                        uint32_t* key, float* lg, hipStream_t stream);
+
+// cmcd_segment_hais.hip: the same for UHA (include/cmcd_hip.h: cmcd_bound_segment_hais); rho is the momentum between bridges and lg
+// = log gamma_k1(z) alone.  The mapping and instances of hais_traj_kernel, the shape limits and the workspace of the reverse call
+// (reverse_hais_shape_ok, reverse_hais_floats: one statistics record per tile); the arguments are the entry point's, already checked.
+bool segment_hais_available(int target, int dim);
+int segment_hais_launch(int target, int dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout& lay, int32_t k0, int32_t k1,
+                        const int32_t* seeds, int64_t n, const float* params, const float* target_consts, int n_mix, float* ws,
+                        float* z, float* rho, float* wpath, uint32_t* key, float* lg, hipStream_t stream);
+
 // cmcd_resample.hip: importance statistics + systematic resampling, one workgroup per group of n / groups rows, one launch.
 // The group is walked in chunks of kResampleChunk rows with a float64 running sum carried between them.
 constexpr int kResampleChunk = 1024;

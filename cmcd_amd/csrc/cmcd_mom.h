@@ -1,4 +1,5 @@
-// What the two reverse-time chains of the momentum baselines share (cmcd_reverse_ldvi.hip, cmcd_reverse_hais.hip): the geffner
+// What the reverse-time chains and the chain segments of the two momentum baselines share (cmcd_reverse_ldvi.hip,
+// cmcd_reverse_hais.hip, cmcd_segment_ldvi.hip, cmcd_segment_hais.hip): the geffner
 // score network on [z; rho] for 16 particles per wave, the log density of a standard-normal momentum, a uniform value moved to
 // a scalar register, and Hamiltonian AIS's beta table formed from params_flat in the workgroup prologue.
 //

@@ -8,6 +8,7 @@
 //   cmcd_segment_uha.hip  tile_split, tile_normal, tile_chain_step, tile_stats_record (network and launch: its own, below)
 //   cmcd_reverse_uha.hip  the same four (network and launch: its own, below)
 //   cmcd_reverse_ldvi.hip, cmcd_reverse_hais.hip (through cmcd_mom.h)  the same four; the second also tile_stage_many_gmm, tile_pick_plain
+//   cmcd_segment_ldvi.hip, cmcd_segment_hais.hip (through cmcd_mom.h)  what their reverse siblings take
 //   cmcd_hais.hip    hais_traj_kernel: tile_split, tile_normal, tile_chain_step, tile_stats_record; both kernels:
 //                    tile_stage_many_gmm; tile_pick_plain
 //   cmcd_mfvi.hip    tile_pick_plain (mfvi_kernel itself stays on inline copies, below)
@@ -33,7 +34,8 @@
 //   reverse_ldvi_kernel (cmcd_reverse_ldvi.hip) takes the pair's geffner branch from cmcd_mom.h (mom_pre_z / mom_eval_rho, copied from
 //     ldvi_pre_z / ldvi_eval_rho: cmcd_ldvi.hip stays as it is), the header it shares with reverse_hais_kernel
 //     (cmcd_reverse_hais.hip), whose beta table is a copy of cmcd_hais.hip's hais_form_betas; tests/test_gpu_reverse_ldvi.py's and
-//     tests/test_gpu_reverse_hais.py's parity cases fail when those copies drift.
+//     tests/test_gpu_reverse_hais.py's parity cases fail when those copies drift.  segment_ldvi_kernel (cmcd_segment_ldvi.hip) and
+//     segment_hais_kernel (cmcd_segment_hais.hip) take the same header: no further copy.
 //   reverse_traj_kernel and segment_traj_kernel keep inline the LDS staging, q's constants and log q, grad log q with the clips,
 //     the z_0 draw, the two ends of a step and the head of the statistics record: as helpers each of them compiled to other code
 //     (another register allocation over the whole kernel, other scratch sizes on the funnel geffner instances), for reasons that

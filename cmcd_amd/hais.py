@@ -6,7 +6,8 @@
 grids); `compute_bound` / `grad_and_loss` have the signatures `opt.run` and `utils.sample` expect, with
 `params_fixed = (dim, nbridges, lfsteps)`.  `nbridges = 0` is the mean-field bound and goes to `boundingmachine`.  There is no
 CPU fallback; lgcp (d = 1600) runs through `cmcd_amd.hais_lgcp`, a launch sequence with entry points of its own, and is refused here
-(NotImplementedError)."""
+(NotImplementedError).  The reverse-time chain of this boundmode is `cmcd_amd.reverse_hais`, its chain segments and SMC evaluation
+`cmcd_amd.smc_hais` (gmm / funnel / many_gmm; lgcp has whole chains only).  Not here: a cooperative kernel form, sharding."""
 import torch
 
 from . import _lib

@@ -8,7 +8,8 @@ MCD bounding machine on the underdamped chain with an approximate momentum refre
 only the mode string of `params_fixed` differs; `MCD_U_a-lp` has no `sn`.  `compute_bound` / `grad_and_loss` have the signatures
 `opt.run` and `utils.sample` expect, with `params_fixed = (dim, nbridges, mode, apply_fun_sn)`.  The mode takes no `eps_schedule`
 and no `grad_clipping` (the function body has neither); the tree's `eta` leaf is not read.  There is no CPU fallback; lgcp and
-the dds network have no kernel (NotImplementedError)."""
+the dds network have no kernel (NotImplementedError).  The reverse-time chain of these modes is `cmcd_amd.reverse_ldvi`, their chain
+segments and SMC evaluation `cmcd_amd.smc_ldvi`.  Not here: lgcp, a cooperative kernel form, sharding."""
 import ctypes as C
 
 import torch

@@ -64,7 +64,7 @@ def get_config():
     c.eubo_uha = False          # extra: --config.eubo_uha adds the reverse-chain line to boundmode UHA (cmcd_amd.reverse_hais).  Off by
     #                             default, unlike the MCD modes: tests/test_gpu_hais.py::test_driver_runs_the_default_boundmode holds
     #                             the default UHA command line to printing no "Reverse chain" line, and existing tests stay as they are
-    c.smc_eval = False         # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc / smc_uha: resampling between bridges)
+    c.smc_eval = False         # extra: --config.smc_eval adds the SMC evaluation (cmcd_amd.smc / smc_uha / smc_ldvi / smc_hais: resampling between bridges)
     # fields of the reference's config this driver accepts so that its README command lines run unchanged, but whose
     # only legal value here is the default (dds nets are 64-wide, the lgcp posterior is un-whitened, 40 mixtures
     # unless n_mixes says otherwise) or that configure subsystems left out (NICE, W&B, the cluster launcher)
@@ -311,13 +311,19 @@ def main(config):
 
         say_reverse(params_flat, final_elbo, final_ln_Z)
     # SMC evaluation (no analogue in the reference): the same chain with the groups resampled between bridges when their ESS drops
-    # (MCD_CAIS_UHA_sn: the state carries the momentum, cmcd_amd.smc_uha; same driver, same result dict)
+    # (the three momentum modes carry rho in the state: MCD_CAIS_UHA_sn cmcd_amd.smc_uha, LDVI cmcd_amd.smc_ldvi, UHA
+    # cmcd_amd.smc_hais; same driver, same result dict.  UHA on lgcp has no segments: cmcd_amd.hais_lgcp runs whole chains)
     smc_on = (config.smc_eval and rank == 0 and config.model in ("funnel", "gmm", "many_gmm") and
-              config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn"))
+              (config.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn", "MCD_U_a-lp-sn",
+                                    "MCD_U_a-lp") or (config.boundmode == "UHA" and config.nbridges >= 1)))
     if smc_on:
         from . import sinkhorn
         if config.boundmode == "MCD_CAIS_UHA_sn":
             from . import smc_uha as smc
+        elif config.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp"):
+            from . import smc_ldvi as smc
+        elif config.boundmode == "UHA":
+            from . import smc_hais as smc
         else:
             from . import smc
 

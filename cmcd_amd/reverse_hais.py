@@ -9,7 +9,8 @@ of ln Z), exp(-w) are the importance weights of the reverse estimate of 1 / Z.  
 so the call can be captured into a graph.  The reference has no counterpart; the arithmetic is written out in include/cmcd_hip.h
 and restated in float64 in tests/reverse_hais_restatement.py.  No CPU fallback.
 
-Not here: chain segments for UHA, lgcp (it has no exact draws), a cooperative kernel form, sharding."""
+Not here: lgcp (it has no exact draws), a cooperative kernel form, sharding.  (Chain segments and the SMC evaluation of this
+boundmode: cmcd_amd.smc_hais.)"""
 import torch
 
 from . import _lib

@@ -11,7 +11,7 @@ not read.  Nothing here reads a device value back to the host, so the call can b
 counterpart; the arithmetic is written out in include/cmcd_hip.h and restated in float64 in tests/reverse_ldvi_restatement.py.
 No CPU fallback.
 
-Not here: chain segments for LDVI, lgcp, a cooperative kernel form, sharding."""
+Not here: lgcp, a cooperative kernel form, sharding.  (Chain segments and the SMC evaluation of these modes: cmcd_amd.smc_ldvi.)"""
 import ctypes as C
 
 import torch

@@ -8,8 +8,8 @@ of the reverse estimate of 1 / Z (`utils.log_reverse_diagnostics`, `resample.imp
 value back to the host, so the call can be captured into a graph.  The reference has no counterpart; the arithmetic is written out
 in include/cmcd_hip.h and restated in float64 NumPy in tests/reverse_uha_restatement.py.  No CPU fallback.
 
-LDVI and the UHA boundmode have reverse chains of their own (`cmcd_amd.reverse_ldvi`, `cmcd_amd.reverse_hais`).
-Not here: lgcp, a cooperative kernel form, sharding; chain segments for LDVI and UHA do not exist."""
+LDVI and the UHA boundmode have reverse chains of their own (`cmcd_amd.reverse_ldvi`, `cmcd_amd.reverse_hais`) and chain segments of
+their own (`cmcd_amd.smc_ldvi`, `cmcd_amd.smc_hais`).  Not here: lgcp, a cooperative kernel form, sharding."""
 import ctypes as C
 
 import torch

@@ -13,8 +13,9 @@ one.  Segments compose bit for bit.  `resample_stage` moves z AND rho with the s
 captured into a graph.  The reference has no counterpart; the arithmetic is restated in float64 NumPy in
 tests/smc_uha_restatement.py.  No CPU fallback.
 
-Not here: segments for LDVI and the UHA boundmode, lgcp, the cooperative kernel forms, sharding.  (The reverse-time chain of this
-mode: cmcd_amd.reverse_uha; LDVI and UHA have reverse chains too, cmcd_amd.reverse_ldvi and cmcd_amd.reverse_hais, but no segments.)"""
+LDVI and the UHA boundmode have segments of their own, `cmcd_amd.smc_ldvi` and `cmcd_amd.smc_hais`: they import `resample_stage`
+and the driver loop (`_drive`) from here.  Not here: lgcp, the cooperative kernel forms, sharding.  (The reverse-time chain of
+this mode: cmcd_amd.reverse_uha.)"""
 import ctypes as C
 
 import torch
@@ -30,10 +31,10 @@ STATE_FIELDS = ("z", "rho", "wpath", "lg", "key")
 MODE = "MCD_CAIS_UHA_sn"
 
 
-def _state_inputs(state, params_flat, dim):
+def _state_inputs(state, params_flat, dim, what="a 2nd-order segment", module="smc_uha"):
     """The checks on a state handed to a segment with k0 > 0 -> (z, rho, wpath, key, n)."""
     if not isinstance(state, dict) or any(k not in state for k in ("z", "rho", "wpath", "key")):
-        raise TypeError("a 2nd-order segment with k0 > 0 starts from the state dict an earlier smc_uha.segment (or resample_stage) "
+        raise TypeError(f"{what} with k0 > 0 starts from the state dict an earlier {module}.segment (or resample_stage) "
                         "returned: z, rho, wpath and key")
     _inputs(None, params_flat, seedless=True)
     return _state_tensors(state, params_flat.device, dim, ("z", "rho", "wpath", "key"))
@@ -112,6 +113,14 @@ def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedul
     stages carry {"k", "wpath", "lg", "ancestors"} as there.  With ess_threshold = 0 nothing is resampled and losses are the single
     segment [0, K)'s, bit for bit.  Each segment runs the prep launch and evaluates the target at its first state again.  No host
     read."""
+    return _drive(segment, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups, cuts,
+                  ess_threshold, seed, trace)
+
+
+def _drive(segment, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups, cuts, ess_threshold,
+           seed, trace):
+    """The driver loop of `smc_bound` for a state with momentum, with the segment call handed in (this module's, smc_ldvi's,
+    smc_hais's): params_fixed[1] is nbridges in all three."""
     K = int(params_fixed[1])
     cuts = default_cuts(K) if cuts is None else [int(c) for c in cuts]
     if any(c <= 0 or c >= K for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):

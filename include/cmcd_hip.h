@@ -272,7 +272,8 @@ int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* layout, int32_t
  * where the call is unsupported).  Every call runs the prep launch.  One kernel form (one wave per 16-particle tile) on gmm,
  * funnel (dim 10) and many_gmm with the nets of the forward call's wave-per-tile 2nd-order kernel (dds 64; geffner on 2 / 4 /
  * 5 / 9 neuron tiles); the overdamped modes (they have cmcd_bound_segment), lgcp and other widths: CMCD_ERR_UNSUPPORTED.
- * No cooperative form, no LDVI / UHA-boundmode segments.  (The reverse-time chain of this mode: cmcd_bound_reverse_uha.) */
+ * No cooperative form.  (LDVI and the UHA boundmode have segment calls of their own, cmcd_bound_segment_ldvi and
+ * cmcd_bound_segment_hais below.  The reverse-time chain of this mode: cmcd_bound_reverse_uha.) */
 int64_t cmcd_segment_uha_workspace_bytes(const cmcd_desc* desc, int64_t n);
 int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* layout, int32_t k0, int32_t k1,
                            const int32_t* seeds /* k0 == 0; else nullable */, int64_t n,
@@ -568,6 +569,96 @@ int cmcd_bound_reverse_hais(int32_t target, int32_t dim, int32_t nbridges, int32
                             void* workspace, int64_t workspace_bytes,
                             float* out_w /*[n]*/, float* out_z0 /*[n*dim]*/, float* out_rho0 /*[n*dim]*/,
                             double* out_stats /*[5]*/, void* stream);
+
+/* ---- Resumable segments of the LDVI forward chain (use_net = 1: "MCD_U_a-lp-sn", use_net = 0: "MCD_U_a-lp"):
+ * cmcd_bound_segment_uha for the first momentum baseline — bridges [k0, k1) from (z, rho, wpath, key).  The Python driver is
+ * cmcd_amd.smc_ldvi, the float64 restatement tests/smc_ldvi_restatement.py.  No analogue in the reference; the arithmetic is
+ * cmcd_ldvi_bound_grad's bridge, unchanged, cut at a bridge.  With eta = gamma eps, sigma = sqrt(2 eta),
+ * gU(z, b) = -(b grad log p(z) + (1 - b) grad log q(z)) (no clip) and the betas, the network s([z; rho], i) and q of
+ * cmcd_ldvi_bound_grad for the same (desc, layout, params) (the leaf `eta` is not read), particle p runs
+ *   k0 == 0:  key chain, z_0 and rho_0 of cmcd_ldvi_bound_grad (= cmcd_bound_segment_uha's);
+ *             wpath = -log q(z_0) - log N(rho_0; 0, I);  gen = gen_0
+ *   k0  > 0:  z = z_inout[p], rho = rho_inout[p], wpath = wpath_inout[p], gen = key_inout[p]   (the forward chain's gen_k0)
+ *   for i = k0 .. k1-1, the forward call's bridge i:
+ *             m_f = rho (1 - eta)                                       (no network in the forward kernel)
+ *             rho' = m_f + sigma xi_i,  xi_i = normal(first(split(gen)))
+ *             rho'' = rho' - eps gU(z, beta_i) / 2;  z' = z + eps rho'';  rho_new = rho'' - eps gU(z', beta_i) / 2
+ *             m_b = rho' (1 - eta) [+ 2 eta s([z; rho'], i)]            (the old z; the network only with use_net = 1)
+ *             wpath += log N(rho; m_b, sigma) - log N(rho'; m_f, sigma);   (z, rho) <- (z', rho_new);
+ *             gen <- second(split(second(split(gen))))
+ *   lg = log gamma_k1(z) + log N(rho; 0, I):  gamma_K = p;  0 < k < K:  log gamma_k = beta_{k-1} log p + (1 - beta_{k-1}) log q
+ *   out:  z_inout[p] = z, rho_inout[p] = rho, wpath_inout[p] = wpath, key_inout[p] = gen_k1, out_lg[p] = lg;
+ *         out_stats[5] = the statistics of cmcd_bound_forward over l := -(wpath + lg).
+ * log p = -inf (the many_gmm floor) gives lg = -inf, never 0 * inf; a NaN stays NaN.  At k1 == nbridges, -(wpath + lg) is the loss
+ * of cmcd_ldvi_bound_grad.  The momentum's density is part of lg for the reason given at cmcd_bound_segment_uha (the leap-frog is
+ * a volume-preserving bijection of (z, rho), so exp(wpath + lg) is a proper weight for gamma_k1(z) N(rho; 0, I)); a resampling
+ * stage restarts its offspring with wpath = -lg[ancestor], moves z AND rho with the same ancestors and leaves key_inout alone.
+ * ONE runtime-bounded rotated loop m = k0 .. k1 with a single site that evaluates (log p, grad log p, grad log q) at z_m (it
+ * closes bridge m - 1, opens bridge m, forms lg at m == k1); the network evaluation of a bridge stays inside the bridge, at one
+ * site.  So [0, k) then [k, K) returns the BITS of [0, K) in z, rho, wpath, lg and the key, at one extra target evaluation per cut.
+ *   0 <= k0 < k1 <= nbridges, else CMCD_ERR_BAD_ARG;  seeds[n] is read when k0 == 0 (null there: CMCD_ERR_BAD_ARG) and may be
+ *   null otherwise.  Buffers as cmcd_bound_segment_uha.  A short or misaligned workspace: CMCD_ERR_WORKSPACE.
+ * desc and layout as cmcd_ldvi_bound_grad reads them.  Workspace of cmcd_segment_ldvi_workspace_bytes (the forward part of
+ * cmcd_ldvi_workspace_bytes; 0 where the call is unsupported).  Every call runs the prep launch.  Every refusal is made on the
+ * host before anything touches the device; no float atomics, repeated calls return equal bits; no host read-back, capturable.
+ * Instances exactly cmcd_ldvi_bound_grad's eight (gmm / many_gmm on 2 and 4 neuron tiles, funnel dim 10 on 5, the three
+ * network-free ones); lgcp ("lgcp" in the message), dds and other widths: CMCD_ERR_UNSUPPORTED.  No cooperative form. */
+int64_t cmcd_segment_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n);
+int cmcd_bound_segment_ldvi(const cmcd_desc* desc, const cmcd_layout* layout, int32_t use_net, int32_t k0, int32_t k1,
+                            const int32_t* seeds /* k0 == 0; else nullable */, int64_t n,
+                            const float* params, int64_t n_params,
+                            const float* target_consts, int64_t n_target,
+                            void* workspace, int64_t workspace_bytes,
+                            float* z_inout /*[n*dim]*/, float* rho_inout /*[n*dim]*/, float* wpath_inout /*[n]*/,
+                            uint32_t* key_inout /*[n*2]*/, float* out_lg /*[n]*/, double* out_stats /*[5]*/, void* stream);
+
+/* ---- Resumable segments of the UHA forward chain (Hamiltonian AIS, cmcd_hais_bound_grad): bridges [k0, k1) from
+ * (z, rho, wpath, key), where rho is the momentum BETWEEN bridges — rho_prev of the write-out at cmcd_hais_bound_grad, the
+ * momentum that left bridge k0 - 1 (s normal(R) at k0 == 0).  The Python driver is cmcd_amd.smc_hais, the float64 restatement
+ * tests/smc_hais_restatement.py.  With s = exp(md), L = lfsteps, gU and the betas of cmcd_hais_bound_grad, particle p runs
+ *   k0 == 0:  key chain, z_0 and rho_prev = s normal(R) of cmcd_hais_bound_grad;  wpath = -log q(z_0);  gen = gen_0
+ *   k0  > 0:  z = z_inout[p], rho_prev = rho_inout[p], wpath = wpath_inout[p], gen = key_inout[p]
+ *   for i = k0 .. k1-1, the forward call's bridge i:
+ *             rho = eta rho_prev + sqrt(1 - eta^2) s xi_i                                       (the refresh)
+ *             r = rho - eps/2 gU(z, beta_i);  z += eps r / s^2;  (L - 1) times:  r -= eps gU(z, beta_i);  z += eps r / s^2
+ *             r -= eps/2 gU(z, beta_i)                                                          (the L-step leap-frog)
+ *             wpath += log N(r; 0, s) - log N(rho; 0, s);  rho_prev = r;  gen <- second(split(second(split(gen))))
+ *   lg = log gamma_k1(z) alone, no momentum term:  gamma_K = p;  0 < k < K:  log gamma_k = beta_{k-1} log p + (1 - beta_{k-1}) log q
+ *   out:  z_inout[p] = z, rho_inout[p] = rho_prev, wpath_inout[p] = wpath, key_inout[p] = gen_k1, out_lg[p] = lg;
+ *         out_stats[5] over l := -(wpath + lg).  At k1 == nbridges, -(wpath + lg) is the loss of cmcd_hais_bound_grad.
+ * Why lg carries no momentum density.  Write M(rho | rho_prev) for the refresh and T_i for the leap-frog of bridge i, a
+ * volume-preserving bijection of (z, rho).  The forward path has density  q(z_0) N(rho_prev,0; 0, s) prod_i M(rho_i | r_{i-1})
+ * (r_{-1} = rho_prev,0, r_i = what T_i leaves), the backward path started at gamma_k(z_k) N(r_{k-1}; 0, s) and run through the
+ * inverted leap-frogs and the refresh  gamma_k(z_k) N(r_{k-1}; 0, s) prod_i M(r_{i-1} | rho_i).  The refresh is reversible with
+ * respect to N(0, s^2):  M(rho | r) N(r; 0, s) = M(r | rho) N(rho; 0, s),  so  M(r_{i-1} | rho_i) / M(rho_i | r_{i-1}) =
+ * N(r_{i-1}; 0, s) / N(rho_i; 0, s)  and the ratio of the two path densities is
+ *     gamma_k(z_k) / q(z_0)  *  N(r_{k-1}) / N(r_{-1})  *  prod_{i<k} N(r_{i-1}) / N(rho_i)
+ *   = gamma_k(z_k) / q(z_0)  *  prod_{i<k} N(r_i; 0, s) / N(rho_i; 0, s):
+ * the momentum densities telescope, the functional has neither an initial nor a final momentum term (as the forward call's has
+ * none), and what is left is exp(wpath + lg) with lg = log gamma_k(z) alone — a proper weight for gamma_k(z) N(rho_prev; 0, s^2)
+ * on the PAIR (z, rho_prev).  That is why the overdamped restart rule wpath_j = -lg[a_j] is still right here (the offspring
+ * of a resampling stage are equally weighted draws of that joint law: wpath + lg = 0), and why a stage must move rho with z:
+ * the law that is resampled is the joint one, and a z with another particle's momentum is not a draw of it.  Keys stay with
+ * their slot.
+ * The kernel is ONE runtime loop over the evaluations m = k0 L .. k1 L with a single site that evaluates (log p, grad log p,
+ * grad log q): the evaluation that closes one bridge opens the next and forms lg at m = k1 L — (k1 - k0) L + 1 target
+ * evaluations per segment, so a cut costs one extra.  [0, k) then [k, K) returns the BITS of [0, K) in z, rho, wpath, lg and
+ * the key.
+ *   0 <= k0 < k1 <= nbridges, else CMCD_ERR_BAD_ARG;  seeds[n] is read when k0 == 0 (null there: CMCD_ERR_BAD_ARG).  Buffers as
+ *   cmcd_bound_segment_uha; a short or misaligned workspace: CMCD_ERR_WORKSPACE.
+ * Targets gmm, many_gmm (dim 2), funnel (dim 10); lgcp ("lgcp" in the message: cmcd_hais_lgcp_bound_grad runs whole chains
+ * only) and every other (target, dim): CMCD_ERR_UNSUPPORTED, 0 from the size query.  nbridges, lfsteps < 1: CMCD_ERR_BAD_ARG;
+ * nbridges > 4096 or nbridges * lfsteps > 2^24: CMCD_ERR_UNSUPPORTED (the forward call's limits).  The workspace holds one
+ * statistics record per 16-particle tile.  One launch plus the merge; every refusal on the host before anything touches the
+ * device; no float atomics, repeated calls return equal bits; no host read-back, capturable. */
+int64_t cmcd_segment_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n);
+int cmcd_bound_segment_hais(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* layout,
+                            int32_t k0, int32_t k1, const int32_t* seeds /* k0 == 0; else nullable */, int64_t n,
+                            const float* params, int64_t n_params,
+                            const float* target_consts, int64_t n_target,
+                            void* workspace, int64_t workspace_bytes,
+                            float* z_inout /*[n*dim]*/, float* rho_inout /*[n*dim]*/, float* wpath_inout /*[n]*/,
+                            uint32_t* key_inout /*[n*2]*/, float* out_lg /*[n]*/, double* out_stats /*[5]*/, void* stream);
 
 /* ---- Optimiser step of the training loop (/root/reference/src/opt.py:14-35,100-116) fused into one launch:
  * g = clip(grad, +-clip); Adam moments (optax.adam: bias correction 1 - b^step, eps outside the root);

@@ -157,12 +157,19 @@ def evaluate(p, tag):
             tag, r["eubo"], r["reverse_ln_Z"], r["reverse_ess"], r["reverse_ess_std"], cfg.n_samples,
             100.0 * r["reverse_ess_frac"], e, r["eubo"]))
 
-    # (the modes and targets of the reverse chain, and MCD_CAIS_UHA_sn through cmcd_amd.smc_uha: the state with momentum)
-    smc_uha_on = len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and cfg.boundmode == "MCD_CAIS_UHA_sn"
-    if cfg.smc_eval and (x_tgt is not None or smc_uha_on):
+    # (by mode and target, not by whether the reverse chain ran: all seven methods on gmm / funnel / many_gmm.  The three momentum
+    # modes carry rho in the state: cmcd_amd.smc_uha, smc_ldvi, smc_hais; UHA on lgcp has no segments)
+    smc_on = len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and \
+        (cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn") or LDVI or
+         (cfg.boundmode == "UHA" and cfg.nbridges >= 1))
+    if cfg.smc_eval and smc_on:
         from cmcd_amd import resample, sinkhorn
-        if smc_uha_on:
+        if cfg.boundmode == "MCD_CAIS_UHA_sn":
             from cmcd_amd import smc_uha as smc
+        elif LDVI:
+            from cmcd_amd import smc_ldvi as smc
+        elif cfg.boundmode == "UHA":
+            from cmcd_amd import smc_hais as smc
         else:
             from cmcd_amd import smc
         G = cfg.n_input_dist_seeds
