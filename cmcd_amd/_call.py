@@ -2,7 +2,11 @@
 the call, its scratch buffer and the claim on prepared tables that buffer may carry.  An entry point checks its tensors
 (`_inputs`, `check_x`), then hands `on_device` a body that takes the buffer (`_workspace`: the refusal of a size query, the LRU,
 the retired claim), the constants (`consts_args`) and the outputs (`_outputs`) and spells out its own C call.  Nothing here
-knows a mode, a target or a descriptor."""
+knows a mode, a target or a descriptor.
+
+The eight reverse-chain and chain-segment entry points go through one more layer, `_chain` (`segment_call`, `reverse_call`): it
+makes these calls in this order for them — tensor checks, the state's tensors, `on_device`, the cached size query, `_workspace`,
+the outputs, the C call — and takes from the module only its gate, its plan and its two C functions with their leading arguments."""
 import torch
 
 from . import _lib

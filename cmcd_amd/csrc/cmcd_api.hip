@@ -242,7 +242,7 @@ static bool layout_inside(const cmcd_desc& d, const cmcd_layout& lay, int64_t n_
 //   segment-uha: the same for MCD_CAIS_UHA_sn (the state carries the momentum); that mode only, no lgcp
 //   reverse-uha: the forward layout once more (the reverse-time chain of MCD_CAIS_UHA_sn); that mode only, no lgcp
 //   reverse-ldvi: the forward layout of LDVI's effective descriptor (cmcd_ldvi_bound_grad's), no gradient part; no lgcp
-//   reverse-hais: [one statistics record per 16-particle tile] (HaisReversePlan below: UHA has no tables and no descriptor)
+//   reverse-hais: [one statistics record per 16-particle tile] (hais_chain_plan below: UHA has no tables and no descriptor)
 //   segment-ldvi, segment-hais: the layouts of reverse-ldvi and reverse-hais (bridges [k0, k1) from a state with momentum)
 //   var-grad:    [forward | gradient workspace | z_0..z_K | loss, z, statistics of the internal forward]   (the last two: work items only)
 //   bound-grad:  [forward | gradient workspace | kept trajectory | work-item scratch]
@@ -498,79 +498,93 @@ static int forward_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int
   return CMCD_OK;
 }
 
+// The arguments every reverse and segment entry point (and cmcd_ldvi_bound_grad) has in common, as the caller gave them
+struct ChainArgs {
+  const int32_t* seeds;
+  int64_t n;
+  const float* params;
+  int64_t n_params;
+  const float* target_consts;
+  int64_t n_target;
+  void* workspace;
+  int64_t workspace_bytes;
+  void* stream_;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  float* ws() const { return static_cast<float*>(workspace); }
+  double* partials(const WsLayout& w) const { return reinterpret_cast<double*>(ws() + w.partials); }
+};
+
 // What cmcd_bound_reverse and cmcd_bound_segment do between their own argument checks and their kernel launch, in this order:
 // plan (refuses the modes and targets without an instance before the layout is looked at), layout, many_gmm constants,
 // workspace, the prep launch (the forward call's tables, formed by the same launch, on every call), and the TrajArgs of a
 // wave-per-tile launch with one statistics record per 16-particle tile.
-static int chain_call_begin(const cmcd_desc& d, const cmcd_layout* lay, PlanKind kind, const int32_t* seeds, int64_t n,
-                            const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
-                            int64_t workspace_bytes, float* out_loss, float* out_z, hipStream_t stream, CallPlan& p, TrajArgs& ta) {
+static int chain_call_begin(const cmcd_desc& d, const cmcd_layout* lay, PlanKind kind, const ChainArgs& a, float* out_loss,
+                            float* out_z, CallPlan& p, TrajArgs& ta) {
   int rc;
-  if ((rc = make_plan(d, n, n_target, kind, false, p)) != CMCD_OK) return rc;
-  if (!layout_inside(d, *lay, n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(d.target, target_consts, n_target)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, p.need)) != CMCD_OK) return rc;
-  float* ws = static_cast<float*>(workspace);
-  launch_prep(p.d, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(d, *lay, n, n_params, n_target));
-  ta = TrajArgs{seeds, params, ws, reinterpret_cast<double*>(ws + p.w.partials), out_loss, out_z, *lay, p.w, n, (int32_t)d.nbridges,
+  if ((rc = make_plan(d, a.n, a.n_target, kind, false, p)) != CMCD_OK) return rc;
+  if (!layout_inside(d, *lay, a.n_params)) return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(d.target, a.target_consts, a.n_target)) != CMCD_OK) return rc;
+  if ((rc = check_workspace(a.workspace, a.workspace_bytes, p.need)) != CMCD_OK) return rc;
+  launch_prep(p.d, *lay, p.w, a.params, a.target_consts, p.n_mix, a.ws(), a.stream,
+              tables_stamp(d, *lay, a.n, a.n_params, a.n_target));
+  ta = TrajArgs{a.seeds, a.params, a.ws(), a.partials(p.w), out_loss, out_z, *lay, p.w, a.n, (int32_t)d.nbridges,
                 d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0, p.d.grad_clipping, nullptr,
                 d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0)};
   return CMCD_OK;
 }
 
-// ... and behind it: merge the statistics
-static int chain_call_end(const TrajArgs& ta, double* out_stats, hipStream_t stream) {
-  launch_finalize(ta.partials, ta.w.n_waves, out_stats, stream, nullptr, 0u);
+// ... and behind the launch of every reverse and segment call (LDVI's forward and gradient call too): merge the `records`
+// statistics records the kernel left at `partials`, one per 16-particle tile
+static int chain_call_end(const double* partials, int64_t records, double* out_stats, hipStream_t stream) {
+  launch_finalize(partials, (int32_t)records, out_stats, stream, nullptr, 0u);
   CMCD_HIP_CHECK(hipGetLastError());
+  return CMCD_OK;
+}
+
+// the checks of every segment call on [k0, k1) and the seeds
+static int segment_range(int32_t k0, int32_t k1, int32_t nbridges, const int32_t* seeds) {
+  if (k0 < 0 || k0 >= k1 || k1 > nbridges)
+    return fail(CMCD_ERR_BAD_ARG, "segment bridges must satisfy 0 <= k0 < k1 <= nbridges (got k1 = %s%lld)", "", k1);
+  if (k0 == 0 && !seeds) return fail(CMCD_ERR_BAD_ARG, "a segment that starts at bridge 0 needs seeds%s");
   return CMCD_OK;
 }
 
 // the reverse-time chain: x[n][dim] target draws -> out_w, out_z0, statistics over l := w (cmcd_reverse.hip).
 // uha: the 2nd-order chain, which also returns the end momentum out_rho0 (cmcd_reverse_uha.hip)
-static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, const float* x, int64_t n,
-                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
-                        int64_t workspace_bytes, float* out_w, float* out_z0, float* out_rho0, double* out_stats, void* stream_,
-                        bool uha) {
+static int reverse_impl(const cmcd_desc* desc, const cmcd_layout* lay, const ChainArgs& a, const float* x, float* out_w,
+                        float* out_z0, float* out_rho0, double* out_stats, bool uha) {
   int rc = check_desc(desc);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || (uha && !out_rho0) || !out_stats)
+  if (!lay || !a.seeds || !x || !a.params || !a.workspace || !out_w || !out_z0 || (uha && !out_rho0) || !out_stats)
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (a.n < 1 || a.n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
   CallPlan p;
   TrajArgs ta;
-  if ((rc = chain_call_begin(*desc, lay, uha ? PLAN_REVERSE_UHA : PLAN_REVERSE, seeds, n, params, n_params, target_consts, n_target,
-                             workspace, workspace_bytes, out_w, out_z0, stream, p, ta)) != CMCD_OK) return rc;
+  if ((rc = chain_call_begin(*desc, lay, uha ? PLAN_REVERSE_UHA : PLAN_REVERSE, a, out_w, out_z0, p, ta)) != CMCD_OK) return rc;
   snprintf(g_kernel_name, sizeof(g_kernel_name), uha ? "reverse_uha_kernel" : "reverse_traj_kernel");
-  rc = uha ? reverse_uha_launch(p.d, p.w, ta, x, out_rho0, stream) : reverse_launch(p.d, p.w, ta, x, stream);
+  rc = uha ? reverse_uha_launch(p.d, p.w, ta, x, out_rho0, a.stream) : reverse_launch(p.d, p.w, ta, x, a.stream);
   if (rc != CMCD_OK) return rc;
-  return chain_call_end(ta, out_stats, stream);
+  return chain_call_end(ta.partials, ta.w.n_waves, out_stats, a.stream);
 }
 
 // bridges [k0, k1) of the forward chain from the state (z, wpath, key); seeds are read when k0 == 0 (cmcd_segment.hip).
 // uha: the 2nd-order chain from (z, rho, wpath, key) (cmcd_segment_uha.hip)
-static int segment_impl(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0, int32_t k1, const int32_t* seeds, int64_t n,
-                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target, void* workspace,
-                        int64_t workspace_bytes, float* z, float* rho, float* wpath, uint32_t* key, float* out_lg,
-                        double* out_stats, void* stream_, bool uha) {
+static int segment_impl(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0, int32_t k1, const ChainArgs& a, float* z,
+                        float* rho, float* wpath, uint32_t* key, float* out_lg, double* out_stats, bool uha) {
   int rc = check_desc(desc);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !params || !workspace || !z || (uha && !rho) || !wpath || !key || !out_lg || !out_stats)
+  if (!lay || !a.params || !a.workspace || !z || (uha && !rho) || !wpath || !key || !out_lg || !out_stats)
     return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  if (k0 < 0 || k0 >= k1 || k1 > desc->nbridges)
-    return fail(CMCD_ERR_BAD_ARG, "segment bridges must satisfy 0 <= k0 < k1 <= nbridges (got k1 = %s%lld)", "", k1);
-  if (k0 == 0 && !seeds) return fail(CMCD_ERR_BAD_ARG, "a segment that starts at bridge 0 needs seeds%s");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (a.n < 1 || a.n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  if ((rc = segment_range(k0, k1, desc->nbridges, a.seeds)) != CMCD_OK) return rc;
   CallPlan p;
   TrajArgs ta;
-  if ((rc = chain_call_begin(*desc, lay, uha ? PLAN_SEGMENT_UHA : PLAN_SEGMENT, seeds, n, params, n_params, target_consts, n_target,
-                             workspace, workspace_bytes, nullptr, nullptr, stream, p, ta)) != CMCD_OK) return rc;
+  if ((rc = chain_call_begin(*desc, lay, uha ? PLAN_SEGMENT_UHA : PLAN_SEGMENT, a, nullptr, nullptr, p, ta)) != CMCD_OK) return rc;
   snprintf(g_kernel_name, sizeof(g_kernel_name), uha ? "segment_uha_kernel" : "segment_traj_kernel");
-  rc = uha ? segment_uha_launch(p.d, p.w, ta, k0, k1, z, rho, wpath, key, out_lg, stream)
-           : segment_launch(p.d, p.w, ta, k0, k1, z, wpath, key, out_lg, stream);
+  rc = uha ? segment_uha_launch(p.d, p.w, ta, k0, k1, z, rho, wpath, key, out_lg, a.stream)
+           : segment_launch(p.d, p.w, ta, k0, k1, z, wpath, key, out_lg, a.stream);
   if (rc != CMCD_OK) return rc;
-  return chain_call_end(ta, out_stats, stream);
+  return chain_call_end(ta.partials, ta.w.n_waves, out_stats, a.stream);
 }
 
 // the VarGrad gradient on the tables (and, for work items and lgcp, the trajectory) in the workspace; kept: left there by
@@ -659,8 +673,8 @@ int cmcd_bound_reverse(const cmcd_desc* desc, const cmcd_layout* lay, const int3
                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
                        void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, double* out_stats,
                        void* stream_) {
-  return reverse_impl(desc, lay, seeds, x, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_w,
-                      out_z0, nullptr, out_stats, stream_, false);
+  return reverse_impl(desc, lay, {seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_}, x, out_w, out_z0,
+                      nullptr, out_stats, false);
 }
 
 int64_t cmcd_reverse_uha_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_REVERSE_UHA); }
@@ -669,8 +683,8 @@ int cmcd_bound_reverse_uha(const cmcd_desc* desc, const cmcd_layout* lay, const 
                            const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
                            void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, float* out_rho0,
                            double* out_stats, void* stream_) {
-  return reverse_impl(desc, lay, seeds, x, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, out_w,
-                      out_z0, out_rho0, out_stats, stream_, true);
+  return reverse_impl(desc, lay, {seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_}, x, out_w, out_z0,
+                      out_rho0, out_stats, true);
 }
 
 int64_t cmcd_segment_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_SEGMENT); }
@@ -679,8 +693,8 @@ int cmcd_bound_segment(const cmcd_desc* desc, const cmcd_layout* lay, int32_t k0
                        const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
                        void* workspace, int64_t workspace_bytes, float* z_inout, float* wpath_inout, uint32_t* key_inout,
                        float* out_lg, double* out_stats, void* stream_) {
-  return segment_impl(desc, lay, k0, k1, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
-                      z_inout, nullptr, wpath_inout, key_inout, out_lg, out_stats, stream_, false);
+  return segment_impl(desc, lay, k0, k1, {seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_},
+                      z_inout, nullptr, wpath_inout, key_inout, out_lg, out_stats, false);
 }
 
 int64_t cmcd_segment_uha_workspace_bytes(const cmcd_desc* desc, int64_t n) { return plan_bytes(desc, n, PLAN_SEGMENT_UHA); }
@@ -689,8 +703,8 @@ int cmcd_bound_segment_uha(const cmcd_desc* desc, const cmcd_layout* lay, int32_
                            const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
                            void* workspace, int64_t workspace_bytes, float* z_inout, float* rho_inout, float* wpath_inout,
                            uint32_t* key_inout, float* out_lg, double* out_stats, void* stream_) {
-  return segment_impl(desc, lay, k0, k1, seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes,
-                      z_inout, rho_inout, wpath_inout, key_inout, out_lg, out_stats, stream_, true);
+  return segment_impl(desc, lay, k0, k1, {seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_},
+                      z_inout, rho_inout, wpath_inout, key_inout, out_lg, out_stats, true);
 }
 
 int cmcd_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, const int32_t* seeds, int64_t n,
@@ -754,195 +768,186 @@ static int ldvi_desc(const cmcd_desc* desc, int32_t use_net, cmcd_desc& e) {
   return CMCD_OK;
 }
 
-int64_t cmcd_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n, int32_t with_grad) {
+// bytes of an LDVI workspace: the plan's forward part (PLAN_REVERSE_LDVI / PLAN_SEGMENT_LDVI: their total), then the gradient
+// workspace of cmcd_ldvi_bound_grad
+static int64_t ldvi_bytes(const cmcd_desc& e, const CallPlan& p, int64_t n, bool use_net, bool with_grad) {
+  return (align4(p.fwd) + (with_grad ? ldvi_grad_floats(e, p.w.HP, n, use_net) : 0)) * 4;
+}
+
+// the three LDVI size queries: 0 for whatever ldvi_desc or the plan of `kind` refuses
+static int64_t ldvi_query(const cmcd_desc* desc, int32_t use_net, int64_t n, PlanKind kind, bool with_grad) {
   cmcd_desc e;
   CallPlan p;
   if (ldvi_desc(desc, use_net, e) != CMCD_OK || n < 1 || n > (int64_t)1 << 31) return 0;
-  if (make_plan(e, n, 0, PLAN_FORWARD, true, p) != CMCD_OK) return 0;
-  return (align4(p.fwd) + (with_grad ? ldvi_grad_floats(e, p.w.HP, n, use_net != 0) : 0)) * 4;
+  if (make_plan(e, n, 0, kind, true, p) != CMCD_OK) return 0;
+  return ldvi_bytes(e, p, n, use_net != 0, with_grad);
+}
+
+// What the three LDVI calls do in front of their launch, chain_call_begin's sibling for a descriptor that ldvi_desc forms:
+// descriptor, null pointers (lay, params and workspace here; other_null: the rest of the entry point's own list), n, for a
+// segment its range = {k0, k1}, layout with the gamma leaf, many_gmm constants, the plan of this call (layout) and of its size
+// query (demand: many_gmm's largest target block), workspace, the prep launch.  -> the effective descriptor and the plan.
+static int ldvi_call_begin(const cmcd_desc* desc, int32_t use_net, const cmcd_layout* lay, const ChainArgs& a, bool other_null,
+                           const int32_t* range, PlanKind kind, bool with_grad, cmcd_desc& e, CallPlan& p) {
+  int rc = ldvi_desc(desc, use_net, e);
+  if (rc != CMCD_OK) return rc;
+  if (!lay || !a.params || !a.workspace || other_null) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  if (a.n < 1 || a.n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
+  if (range && (rc = segment_range(range[0], range[1], e.nbridges, a.seeds)) != CMCD_OK) return rc;
+  if (!layout_inside(e, *lay, a.n_params) || lay->gamma < 0 || lay->gamma >= a.n_params)
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(e.target, a.target_consts, a.n_target)) != CMCD_OK) return rc;
+  CallPlan q;
+  if ((rc = make_plan(e, a.n, a.n_target, kind, false, p)) != CMCD_OK) return rc;
+  if ((rc = make_plan(e, a.n, 0, kind, true, q)) != CMCD_OK) return rc;
+  p.need = ldvi_bytes(e, q, a.n, use_net != 0, with_grad);
+  if ((rc = check_workspace(a.workspace, a.workspace_bytes, p.need)) != CMCD_OK) return rc;
+  launch_prep(e, *lay, p.w, a.params, a.target_consts, p.n_mix, a.ws(), a.stream, tables_stamp(e, *lay, a.n, a.n_params, a.n_target));
+  return CMCD_OK;
+}
+
+int64_t cmcd_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n, int32_t with_grad) {
+  return ldvi_query(desc, use_net, n, PLAN_FORWARD, with_grad != 0);
 }
 
 int cmcd_ldvi_bound_grad(const cmcd_desc* desc, const cmcd_layout* lay, int32_t use_net, const int32_t* seeds, int64_t n,
                          const float* params, int64_t n_params, const float* target_consts, int64_t n_target, float omega,
                          void* workspace, int64_t workspace_bytes, float* out_loss, float* out_z, double* out_stats,
                          float* grad, void* stream_) {
+  const ChainArgs a{seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_};
   cmcd_desc e;
-  int rc = ldvi_desc(desc, use_net, e);
+  CallPlan p;
+  int rc = ldvi_call_begin(desc, use_net, lay, a, !seeds || !out_loss || !out_z || !out_stats, nullptr, PLAN_FORWARD, grad != nullptr,
+                           e, p);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !seeds || !params || !workspace || !out_loss || !out_z || !out_stats)
-    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  if (!layout_inside(e, *lay, n_params) || lay->gamma < 0 || lay->gamma >= n_params)
-    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(e.target, target_consts, n_target)) != CMCD_OK) return rc;
-  CallPlan p, q;   // the layout is this call's, the demand is the size query's (many_gmm: the largest target block)
-  if ((rc = make_plan(e, n, n_target, PLAN_FORWARD, false, p)) != CMCD_OK) return rc;
-  if ((rc = make_plan(e, n, 0, PLAN_FORWARD, true, q)) != CMCD_OK) return rc;
-  const int64_t gfl = grad ? ldvi_grad_floats(e, p.w.HP, n, use_net != 0) : 0;
-  if ((rc = check_workspace(workspace, workspace_bytes, (align4(q.fwd) + gfl) * 4)) != CMCD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  launch_prep(e, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(e, *lay, n, n_params, n_target));
-  rc = ldvi_launch(e, *lay, p.w, use_net != 0, seeds, n, params, n_params, ws, ws + align4(p.fwd), omega, out_loss, out_z, grad,
-                   stream);
+  rc = ldvi_launch(e, *lay, p.w, use_net != 0, seeds, n, params, n_params, a.ws(), a.ws() + align4(p.fwd), omega, out_loss, out_z,
+                   grad, a.stream);
   if (rc != CMCD_OK) return rc;
-  launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
+  return chain_call_end(a.partials(p.w), p.w.n_waves, out_stats, a.stream);
 }
 
 // ---- the reverse-time chains of the two momentum baselines (cmcd_reverse_ldvi.hip, cmcd_reverse_hais.hip)
 int64_t cmcd_reverse_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n) {
-  cmcd_desc e;
-  CallPlan p;
-  if (ldvi_desc(desc, use_net, e) != CMCD_OK || n < 1 || n > (int64_t)1 << 31) return 0;
-  if (make_plan(e, n, 0, PLAN_REVERSE_LDVI, true, p) != CMCD_OK) return 0;
-  return p.total;
+  return ldvi_query(desc, use_net, n, PLAN_REVERSE_LDVI, false);
 }
 
 int cmcd_bound_reverse_ldvi(const cmcd_desc* desc, const cmcd_layout* lay, int32_t use_net, const int32_t* seeds, const float* x,
                             int64_t n, const float* params, int64_t n_params, const float* target_consts, int64_t n_target,
                             void* workspace, int64_t workspace_bytes, float* out_w, float* out_z0, float* out_rho0,
                             double* out_stats, void* stream_) {
+  const ChainArgs a{seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_};
   cmcd_desc e;
-  int rc = ldvi_desc(desc, use_net, e);
+  CallPlan p;
+  int rc = ldvi_call_begin(desc, use_net, lay, a, !seeds || !x || !out_w || !out_z0 || !out_rho0 || !out_stats, nullptr,
+                           PLAN_REVERSE_LDVI, false, e, p);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_rho0 || !out_stats)
-    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  if (!layout_inside(e, *lay, n_params) || lay->gamma < 0 || lay->gamma >= n_params)
-    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(e.target, target_consts, n_target)) != CMCD_OK) return rc;
-  CallPlan p, q;   // the layout is this call's, the demand is the size query's (many_gmm: the largest target block)
-  if ((rc = make_plan(e, n, n_target, PLAN_REVERSE_LDVI, false, p)) != CMCD_OK) return rc;
-  if ((rc = make_plan(e, n, 0, PLAN_REVERSE_LDVI, true, q)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, q.total)) != CMCD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  launch_prep(e, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(e, *lay, n, n_params, n_target));
   snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_ldvi_kernel");
-  rc = reverse_ldvi_launch(e, *lay, p.w, use_net != 0, seeds, x, n, params, ws, out_w, out_z0, out_rho0, stream);
+  rc = reverse_ldvi_launch(e, *lay, p.w, use_net != 0, seeds, x, n, params, a.ws(), out_w, out_z0, out_rho0, a.stream);
   if (rc != CMCD_OK) return rc;
-  launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
+  return chain_call_end(a.partials(p.w), p.w.n_waves, out_stats, a.stream);
 }
 
 // UHA has no descriptor and no prep tables: its plan is the refusals of cmcd_hais_workspace_bytes, in that order, and one
-// statistics record per tile.  -> CMCD_OK and the workspace floats, or the refusal with cmcd_last_error set.
-static int reverse_hais_plan(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int64_t& floats) {
+// statistics record per tile.  The reverse and the segment call differ in their kernel instances and in their words for lgcp
+// and for a missing instance.
+struct HaisChain {
+  bool (*available)(int target, int dim);
+  const char* no_lgcp;
+  const char* no_instance;
+};
+static const HaisChain kReverseHais = {reverse_hais_available,
+                                       "the reverse chain of UHA has no lgcp kernel (lgcp has no exact target draws)%s",
+                                       "no Hamiltonian AIS reverse-chain kernel instance for this (target, dim)%s"};
+static const HaisChain kSegmentHais = {segment_hais_available,
+                                       "chain segments of UHA have no lgcp kernel (cmcd_hais_lgcp.hip runs whole chains)%s",
+                                       "no Hamiltonian AIS segment kernel instance for this (target, dim)%s"};
+struct HaisShape { int32_t target, dim, nbridges, lfsteps; };   // what stands for a descriptor in the UHA calls
+
+// -> CMCD_OK and the workspace floats, or the refusal with cmcd_last_error set
+static int hais_chain_plan(const HaisChain& c, const HaisShape& s, int64_t n, int64_t& floats) {
   floats = 0;
-  if (nbridges < 1 || lfsteps < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges and lfsteps must be >= 1%s");
-  if (n < 1 || n > (int64_t)1 << 31 || dim < 1) return fail(CMCD_ERR_BAD_ARG, "n or dim out of range%s");
-  if (target == CMCD_TARGET_LGCP)
-    return fail(CMCD_ERR_UNSUPPORTED, "the reverse chain of UHA has no lgcp kernel (lgcp has no exact target draws)%s");
-  if (!reverse_hais_available(target, dim))
-    return fail(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS reverse-chain kernel instance for this (target, dim)%s");
-  if (!reverse_hais_shape_ok(nbridges, lfsteps, n))
+  if (s.nbridges < 1 || s.lfsteps < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges and lfsteps must be >= 1%s");
+  if (n < 1 || n > (int64_t)1 << 31 || s.dim < 1) return fail(CMCD_ERR_BAD_ARG, "n or dim out of range%s");
+  if (s.target == CMCD_TARGET_LGCP) return fail(CMCD_ERR_UNSUPPORTED, c.no_lgcp);
+  if (!c.available(s.target, s.dim)) return fail(CMCD_ERR_UNSUPPORTED, c.no_instance);
+  if (!reverse_hais_shape_ok(s.nbridges, s.lfsteps, n))
     return fail(CMCD_ERR_UNSUPPORTED, "nbridges above 4096 or nbridges * lfsteps above 2^24%s");
   floats = reverse_hais_floats(n);
   return CMCD_OK;
 }
 
-int64_t cmcd_reverse_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n) {
+static int64_t hais_chain_query(const HaisChain& c, const HaisShape& s, int64_t n) {
   int64_t floats;
-  return reverse_hais_plan(target, dim, nbridges, lfsteps, n, floats) == CMCD_OK ? floats * 4 : 0;
+  return hais_chain_plan(c, s, n, floats) == CMCD_OK ? floats * 4 : 0;
+}
+
+// What cmcd_bound_reverse_hais and cmcd_bound_segment_hais do in front of their launch: null pointers (lay, params and
+// workspace here; other_null: the rest of the entry point's own list), the plan, for a segment its range = {k0, k1}, the layout,
+// many_gmm constants (-> n_mix), workspace.
+// (cmcd_hais.hip and cmcd_hais_lgcp.hip keep their own copies of the cmcd_hais_layout check: kernel files, their own entry points.)
+static int hais_chain_begin(const HaisChain& c, const HaisShape& s, const cmcd_hais_layout* lay, const ChainArgs& a, bool other_null,
+                            const int32_t* range, int& n_mix) {
+  if (!lay || !a.params || !a.workspace || other_null) return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
+  int64_t floats;
+  int rc = hais_chain_plan(c, s, a.n, floats);
+  if (rc != CMCD_OK) return rc;
+  if (range && (rc = segment_range(range[0], range[1], s.nbridges, a.seeds)) != CMCD_OK) return rc;
+  if (lay->ngrid < 0 || lay->ngrid > 1024) return fail(CMCD_ERR_BAD_ARG, "ngrid out of range (0 .. 1024)%s");
+  auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= a.n_params; };
+  if (!(inside(lay->vd_mean, s.dim) && inside(lay->vd_logdiag, s.dim) && inside(lay->eps, 1) && inside(lay->eta, 1) &&
+        inside(lay->md, s.dim) && inside(lay->mgridref_y, lay->ngrid + 1) && inside(lay->gridref_x, lay->ngrid + 2) &&
+        inside(lay->target_x, s.nbridges)))
+    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  if ((rc = check_many_gmm(s.target, a.target_consts, a.n_target, &n_mix)) != CMCD_OK) return rc;
+  return check_workspace(a.workspace, a.workspace_bytes, floats * 4);
+}
+
+int64_t cmcd_reverse_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n) {
+  return hais_chain_query(kReverseHais, {target, dim, nbridges, lfsteps}, n);
 }
 
 int cmcd_bound_reverse_hais(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* lay,
                             const int32_t* seeds, const float* x, int64_t n, const float* params, int64_t n_params,
                             const float* target_consts, int64_t n_target, void* workspace, int64_t workspace_bytes, float* out_w,
                             float* out_z0, float* out_rho0, double* out_stats, void* stream_) {
-  if (!lay || !seeds || !x || !params || !workspace || !out_w || !out_z0 || !out_rho0 || !out_stats)
-    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  int64_t floats;
-  int rc = reverse_hais_plan(target, dim, nbridges, lfsteps, n, floats);
-  if (rc != CMCD_OK) return rc;
-  if (lay->ngrid < 0 || lay->ngrid > 1024) return fail(CMCD_ERR_BAD_ARG, "ngrid out of range (0 .. 1024)%s");
-  auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
-  if (!(inside(lay->vd_mean, dim) && inside(lay->vd_logdiag, dim) && inside(lay->eps, 1) && inside(lay->eta, 1) &&
-        inside(lay->md, dim) && inside(lay->mgridref_y, lay->ngrid + 1) && inside(lay->gridref_x, lay->ngrid + 2) &&
-        inside(lay->target_x, nbridges)))
-    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  const ChainArgs a{seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_};
   int n_mix = 0;
-  if ((rc = check_many_gmm(target, target_consts, n_target, &n_mix)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, floats * 4)) != CMCD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_hais_kernel");
-  rc = reverse_hais_launch(target, dim, nbridges, lfsteps, *lay, seeds, x, n, params, target_consts, n_mix, ws, out_w, out_z0,
-                           out_rho0, stream);
+  int rc = hais_chain_begin(kReverseHais, {target, dim, nbridges, lfsteps}, lay, a,
+                            !seeds || !x || !out_w || !out_z0 || !out_rho0 || !out_stats, nullptr, n_mix);
   if (rc != CMCD_OK) return rc;
-  launch_finalize(reinterpret_cast<double*>(ws), (int32_t)((n + 15) / 16), out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "reverse_hais_kernel");
+  rc = reverse_hais_launch(target, dim, nbridges, lfsteps, *lay, seeds, x, n, params, target_consts, n_mix, a.ws(), out_w, out_z0,
+                           out_rho0, a.stream);
+  if (rc != CMCD_OK) return rc;
+  return chain_call_end(reinterpret_cast<double*>(workspace), (n + 15) / 16, out_stats, a.stream);
 }
 
 // ---- chain segments of the two momentum baselines (cmcd_segment_ldvi.hip, cmcd_segment_hais.hip): the plans, the layouts and
-// the refusals of their reverse chains, then cmcd_bound_segment_uha's checks on [k0, k1) and the seeds
-static int segment_range(int32_t k0, int32_t k1, int32_t nbridges, const int32_t* seeds) {
-  if (k0 < 0 || k0 >= k1 || k1 > nbridges)
-    return fail(CMCD_ERR_BAD_ARG, "segment bridges must satisfy 0 <= k0 < k1 <= nbridges (got k1 = %s%lld)", "", k1);
-  if (k0 == 0 && !seeds) return fail(CMCD_ERR_BAD_ARG, "a segment that starts at bridge 0 needs seeds%s");
-  return CMCD_OK;
-}
-
+// the refusals of their reverse chains, with segment_range's checks on [k0, k1) and the seeds
 int64_t cmcd_segment_ldvi_workspace_bytes(const cmcd_desc* desc, int32_t use_net, int64_t n) {
-  cmcd_desc e;
-  CallPlan p;
-  if (ldvi_desc(desc, use_net, e) != CMCD_OK || n < 1 || n > (int64_t)1 << 31) return 0;
-  if (make_plan(e, n, 0, PLAN_SEGMENT_LDVI, true, p) != CMCD_OK) return 0;
-  return p.total;
+  return ldvi_query(desc, use_net, n, PLAN_SEGMENT_LDVI, false);
 }
 
 int cmcd_bound_segment_ldvi(const cmcd_desc* desc, const cmcd_layout* lay, int32_t use_net, int32_t k0, int32_t k1,
                             const int32_t* seeds, int64_t n, const float* params, int64_t n_params, const float* target_consts,
                             int64_t n_target, void* workspace, int64_t workspace_bytes, float* z_inout, float* rho_inout,
                             float* wpath_inout, uint32_t* key_inout, float* out_lg, double* out_stats, void* stream_) {
+  const ChainArgs a{seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_};
+  const int32_t range[2] = {k0, k1};
   cmcd_desc e;
-  int rc = ldvi_desc(desc, use_net, e);
+  CallPlan p;
+  int rc = ldvi_call_begin(desc, use_net, lay, a, !z_inout || !rho_inout || !wpath_inout || !key_inout || !out_lg || !out_stats, range,
+                           PLAN_SEGMENT_LDVI, false, e, p);
   if (rc != CMCD_OK) return rc;
-  if (!lay || !params || !workspace || !z_inout || !rho_inout || !wpath_inout || !key_inout || !out_lg || !out_stats)
-    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  if (n < 1 || n > (int64_t)1 << 31) return fail(CMCD_ERR_BAD_ARG, "n out of range%s");
-  if ((rc = segment_range(k0, k1, e.nbridges, seeds)) != CMCD_OK) return rc;
-  if (!layout_inside(e, *lay, n_params) || lay->gamma < 0 || lay->gamma >= n_params)
-    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
-  if ((rc = check_many_gmm(e.target, target_consts, n_target)) != CMCD_OK) return rc;
-  CallPlan p, q;   // the layout is this call's, the demand is the size query's (many_gmm: the largest target block)
-  if ((rc = make_plan(e, n, n_target, PLAN_SEGMENT_LDVI, false, p)) != CMCD_OK) return rc;
-  if ((rc = make_plan(e, n, 0, PLAN_SEGMENT_LDVI, true, q)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, q.total)) != CMCD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  launch_prep(e, *lay, p.w, params, target_consts, p.n_mix, ws, stream, tables_stamp(e, *lay, n, n_params, n_target));
   snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_ldvi_kernel");
-  rc = segment_ldvi_launch(e, *lay, p.w, use_net != 0, k0, k1, seeds, n, params, ws, z_inout, rho_inout, wpath_inout, key_inout,
-                           out_lg, stream);
+  rc = segment_ldvi_launch(e, *lay, p.w, use_net != 0, k0, k1, seeds, n, params, a.ws(), z_inout, rho_inout, wpath_inout, key_inout,
+                           out_lg, a.stream);
   if (rc != CMCD_OK) return rc;
-  launch_finalize(reinterpret_cast<double*>(ws + p.w.partials), p.w.n_waves, out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
-}
-
-// UHA: reverse_hais_plan's refusals with the segment call's words for lgcp and a missing instance
-static int segment_hais_plan(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n, int64_t& floats) {
-  floats = 0;
-  if (nbridges < 1 || lfsteps < 1) return fail(CMCD_ERR_BAD_ARG, "nbridges and lfsteps must be >= 1%s");
-  if (n < 1 || n > (int64_t)1 << 31 || dim < 1) return fail(CMCD_ERR_BAD_ARG, "n or dim out of range%s");
-  if (target == CMCD_TARGET_LGCP)
-    return fail(CMCD_ERR_UNSUPPORTED, "chain segments of UHA have no lgcp kernel (cmcd_hais_lgcp.hip runs whole chains)%s");
-  if (!segment_hais_available(target, dim))
-    return fail(CMCD_ERR_UNSUPPORTED, "no Hamiltonian AIS segment kernel instance for this (target, dim)%s");
-  if (!reverse_hais_shape_ok(nbridges, lfsteps, n))
-    return fail(CMCD_ERR_UNSUPPORTED, "nbridges above 4096 or nbridges * lfsteps above 2^24%s");
-  floats = reverse_hais_floats(n);
-  return CMCD_OK;
+  return chain_call_end(a.partials(p.w), p.w.n_waves, out_stats, a.stream);
 }
 
 int64_t cmcd_segment_hais_workspace_bytes(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, int64_t n) {
-  int64_t floats;
-  return segment_hais_plan(target, dim, nbridges, lfsteps, n, floats) == CMCD_OK ? floats * 4 : 0;
+  return hais_chain_query(kSegmentHais, {target, dim, nbridges, lfsteps}, n);
 }
 
 int cmcd_bound_segment_hais(int32_t target, int32_t dim, int32_t nbridges, int32_t lfsteps, const cmcd_hais_layout* lay, int32_t k0,
@@ -950,30 +955,17 @@ int cmcd_bound_segment_hais(int32_t target, int32_t dim, int32_t nbridges, int32
                             const float* target_consts, int64_t n_target, void* workspace, int64_t workspace_bytes, float* z_inout,
                             float* rho_inout, float* wpath_inout, uint32_t* key_inout, float* out_lg, double* out_stats,
                             void* stream_) {
-  if (!lay || !params || !workspace || !z_inout || !rho_inout || !wpath_inout || !key_inout || !out_lg || !out_stats)
-    return fail(CMCD_ERR_BAD_ARG, "null pointer argument%s");
-  int64_t floats;
-  int rc = segment_hais_plan(target, dim, nbridges, lfsteps, n, floats);
-  if (rc != CMCD_OK) return rc;
-  if ((rc = segment_range(k0, k1, nbridges, seeds)) != CMCD_OK) return rc;
-  if (lay->ngrid < 0 || lay->ngrid > 1024) return fail(CMCD_ERR_BAD_ARG, "ngrid out of range (0 .. 1024)%s");
-  auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n_params; };
-  if (!(inside(lay->vd_mean, dim) && inside(lay->vd_logdiag, dim) && inside(lay->eps, 1) && inside(lay->eta, 1) &&
-        inside(lay->md, dim) && inside(lay->mgridref_y, lay->ngrid + 1) && inside(lay->gridref_x, lay->ngrid + 2) &&
-        inside(lay->target_x, nbridges)))
-    return fail(CMCD_ERR_BAD_ARG, "layout offset missing or outside params_flat%s");
+  const ChainArgs a{seeds, n, params, n_params, target_consts, n_target, workspace, workspace_bytes, stream_};
+  const int32_t range[2] = {k0, k1};
   int n_mix = 0;
-  if ((rc = check_many_gmm(target, target_consts, n_target, &n_mix)) != CMCD_OK) return rc;
-  if ((rc = check_workspace(workspace, workspace_bytes, floats * 4)) != CMCD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_hais_kernel");
-  rc = segment_hais_launch(target, dim, nbridges, lfsteps, *lay, k0, k1, seeds, n, params, target_consts, n_mix, ws, z_inout,
-                           rho_inout, wpath_inout, key_inout, out_lg, stream);
+  int rc = hais_chain_begin(kSegmentHais, {target, dim, nbridges, lfsteps}, lay, a,
+                            !z_inout || !rho_inout || !wpath_inout || !key_inout || !out_lg || !out_stats, range, n_mix);
   if (rc != CMCD_OK) return rc;
-  launch_finalize(reinterpret_cast<double*>(ws), (int32_t)((n + 15) / 16), out_stats, stream, nullptr, 0u);
-  CMCD_HIP_CHECK(hipGetLastError());
-  return CMCD_OK;
+  snprintf(g_kernel_name, sizeof(g_kernel_name), "segment_hais_kernel");
+  rc = segment_hais_launch(target, dim, nbridges, lfsteps, *lay, k0, k1, seeds, n, params, target_consts, n_mix, a.ws(), z_inout,
+                           rho_inout, wpath_inout, key_inout, out_lg, a.stream);
+  if (rc != CMCD_OK) return rc;
+  return chain_call_end(reinterpret_cast<double*>(workspace), (n + 15) / 16, out_stats, a.stream);
 }
 
 int cmcd_vargrad_weights(const float* loss, const double* stats, int64_t n, int64_t n_total, float* omega,

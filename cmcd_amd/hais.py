@@ -18,6 +18,10 @@ initialize = _bm.initialize
 
 
 def _layout(unflatten):
+    """The leaf offsets for the library (read-only there), built once per tree: an Unflatten never changes (as `ldvi._plan`)."""
+    lay = unflatten.__dict__.get("_hais_layout")
+    if lay is not None:
+        return lay
     lay = _lib.HaisLayout(vd_mean=unflatten.offset("vd", "mean"), vd_logdiag=unflatten.offset("vd", "logdiag"),
                           eps=unflatten.offset("eps"), eta=unflatten.offset("eta"), md=unflatten.offset("md"),
                           mgridref_y=unflatten.offset("mgridref_y"), gridref_x=unflatten.offset("gridref_x"),
@@ -26,6 +30,7 @@ def _layout(unflatten):
     if shape is None:
         raise ValueError("params tree has no mgridref_y leaf (use hais.initialize)")
     lay.ngrid = shape[0] - 1
+    unflatten._hais_layout = lay
     return lay
 
 

@@ -163,7 +163,7 @@ def main(config):
     import torch.distributed as dist
     from . import boundingmachine as bm
     from . import mcdboundingmachine as mcdbm
-    from . import opt, parallel, resample, utils
+    from . import _chain, opt, parallel, resample, utils
     from .model_handler import load_model
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -289,14 +289,7 @@ def main(config):
                                      "MCD_U_a-lp-sn", "MCD_U_a-lp") or (config.boundmode == "UHA" and config.eubo_uha)))
     if reverse:
         from .model_handler import exact_target_draws
-        if config.boundmode == "MCD_CAIS_UHA_sn":
-            from . import reverse_uha as rev
-        elif config.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp"):
-            from . import reverse_ldvi as rev
-        elif config.boundmode == "UHA":
-            from . import reverse_hais as rev
-        else:
-            rev = mcdbm
+        rev = _chain.reverse_module(config.boundmode)
         x_tgt = torch.from_numpy(exact_target_draws(config.model, sample_from_target_fn, 3, n, dim)).to(device)   # (seeds 1, 2: the W2 block)
 
         def say_reverse(p, forward_elbo, forward_ln_Z, prefix=""):
@@ -318,14 +311,7 @@ def main(config):
                                     "MCD_U_a-lp") or (config.boundmode == "UHA" and config.nbridges >= 1)))
     if smc_on:
         from . import sinkhorn
-        if config.boundmode == "MCD_CAIS_UHA_sn":
-            from . import smc_uha as smc
-        elif config.boundmode in ("MCD_U_a-lp-sn", "MCD_U_a-lp"):
-            from . import smc_ldvi as smc
-        elif config.boundmode == "UHA":
-            from . import smc_hais as smc
-        else:
-            from . import smc
+        smc = _chain.smc_module(config.boundmode)
 
         def say_smc(p, prefix=""):
             G = config.n_input_dist_seeds

@@ -12,10 +12,11 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib
+from . import _chain, _lib
 from . import variationaldist as vd
 from ._call import (PREP_CALLS, fixed_parameters,      # noqa: F401  (these two, and _outputs, are read through this module)
-                    _fixed, _inputs, _outputs, _prepared, _workspace, _zero_notrain, check_x, consts_args, on_device)
+                    _fixed, _inputs, _outputs, _prepared, _workspace, _zero_notrain, consts_args, on_device)
+from ._chain import eubo_of      # noqa: F401  (its home is _chain; the reverse modules and callers read it here too)
 from .nn import ScoreNet, initialize_network
 
 _SN_MODES = ["MCD_ULA_sn", "MCD_U_e-lp-sna", "MCD_U_a-lp-sna", "MCD_CAIS_sn", "MCD_CAIS_var_sn"]
@@ -322,30 +323,10 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
     path drawn from the target's side; the statistics are taken over l := w.  A non-finite row of x gives w = +inf.
     The reference has no such call.  Overdamped modes on gmm / funnel / many_gmm only (NotImplementedError otherwise)."""
     plan = _plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    seeds, n = _inputs(seeds, params_flat)
-    device, dim = params_flat.device, params_fixed[0]
-    check_x(x, n, dim, device)
-
-    def launch(dev_index, stream, capturing):
-        nbytes = _nbytes(plan, "cmcd_reverse_workspace_bytes", n)
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev",
-                        "no reverse-chain kernel for this configuration", retire=True)
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        w, z0, stats = _outputs(n, dim, device)
-        _lib.check(_lib.lib().cmcd_bound_reverse(
-            C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
-            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), stats.data_ptr(),
-            stream))
-        return w, z0, stats
-
-    return on_device(device, launch)
-
-
-def eubo_of(out):
-    """-> (EUBO = mean(w), (w, z0)) of what a `bound_reverse` of this package returned, (w, z0, [rho0,] stats): the one body
-    of every module's `compute_reverse_bound`."""
-    w, z0, stats = out[0], out[1], out[-1]
-    return (stats[1] / w.numel()).to(torch.float32), (w, z0)
+    L, desc = _lib.lib(), C.byref(plan.desc)
+    return _chain.reverse_call(
+        seeds, x, params_flat, params_fixed[0], False, "rev", "no reverse-chain kernel for this configuration", True,
+        L.cmcd_reverse_workspace_bytes, (desc,), plan.desc_b, L.cmcd_bound_reverse, (desc, C.byref(plan.lay)), log_prob.consts_on)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):

@@ -11,12 +11,9 @@ and restated in float64 in tests/reverse_hais_restatement.py.  No CPU fallback.
 
 Not here: lgcp (it has no exact draws), a cooperative kernel form, sharding.  (Chain segments and the SMC evaluation of this
 boundmode: cmcd_amd.smc_hais.)"""
-import torch
-
-from . import _lib
+from . import _chain, _lib
 from . import hais
-from ._call import check_x, consts_args, _inputs, on_device, _outputs, _workspace
-from .mcdboundingmachine import eubo_of
+from ._chain import eubo_of
 
 __all__ = ["bound_reverse", "compute_reverse_bound"]
 
@@ -35,26 +32,12 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
         raise ValueError(f"target dim {log_prob.dim} != params_fixed dim {dim}")
     if nbridges < 1 or lfsteps < 1:
         raise ValueError(f"nbridges = {nbridges}, lfsteps = {lfsteps}: the reverse chain needs nbridges >= 1 and lfsteps >= 1")
-    seeds, n = _inputs(seeds, params_flat)
-    device = params_flat.device
-    check_x(x, n, dim, device)
-    L = _lib.lib()
-
-    def launch(dev_index, stream, capturing):
-        nbytes = L.cmcd_reverse_hais_workspace_bytes(log_prob.target_id, dim, nbridges, lfsteps, n)
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_hais",
-                        "no Hamiltonian AIS reverse-chain kernel for this target")
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        w, z0, stats = _outputs(n, dim, device)
-        rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
-        lay = hais._layout(unflatten)
-        _lib.check(L.cmcd_bound_reverse_hais(
-            log_prob.target_id, dim, nbridges, lfsteps, lay, seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
-            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(),
-            stats.data_ptr(), stream))
-        return w, z0, rho0, stats
-
-    return on_device(device, launch)
+    L, shape = _lib.lib(), (log_prob.target_id, dim, nbridges, lfsteps)
+    # (the layout struct is formed in front of the C call, behind the checks of seeds, x and the size query)
+    return _chain.reverse_call(
+        seeds, x, params_flat, dim, True, "rev_hais", "no Hamiltonian AIS reverse-chain kernel for this target", False,
+        L.cmcd_reverse_hais_workspace_bytes, shape, shape,
+        L.cmcd_bound_reverse_hais, lambda: (*shape, hais._layout(unflatten)), log_prob.consts_on)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):

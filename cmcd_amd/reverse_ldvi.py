@@ -14,12 +14,9 @@ No CPU fallback.
 Not here: lgcp, a cooperative kernel form, sharding.  (Chain segments and the SMC evaluation of these modes: cmcd_amd.smc_ldvi.)"""
 import ctypes as C
 
-import torch
-
-from . import _lib
+from . import _chain, _lib
 from . import ldvi
-from ._call import check_x, consts_args, _inputs, on_device, _outputs, _workspace
-from .mcdboundingmachine import eubo_of
+from ._chain import eubo_of
 
 __all__ = ["bound_reverse", "compute_reverse_bound"]
 
@@ -34,25 +31,11 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
     forward call only (NotImplementedError otherwise).  eps_schedule / grad_clipping are accepted for the signature and ignored:
     the mode has neither."""
     desc, lay, use_net = ldvi._plan(unflatten, params_fixed, log_prob)
-    seeds, n = _inputs(seeds, params_flat)
-    device, dim = params_flat.device, params_fixed[0]
-    check_x(x, n, dim, device)
-    L = _lib.lib()
-
-    def launch(dev_index, stream, capturing):
-        nbytes = L.cmcd_reverse_ldvi_workspace_bytes(C.byref(desc), use_net, n)
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_ldvi",
-                        "no LDVI reverse-chain kernel for this configuration")
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        w, z0, stats = _outputs(n, dim, device)
-        rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
-        _lib.check(L.cmcd_bound_reverse_ldvi(
-            C.byref(desc), C.byref(lay), use_net, seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
-            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(),
-            stats.data_ptr(), stream))
-        return w, z0, rho0, stats
-
-    return on_device(device, launch)
+    L, dref = _lib.lib(), C.byref(desc)
+    return _chain.reverse_call(
+        seeds, x, params_flat, params_fixed[0], True, "rev_ldvi", "no LDVI reverse-chain kernel for this configuration", False,
+        L.cmcd_reverse_ldvi_workspace_bytes, (dref, use_net), (bytes(desc), use_net),
+        L.cmcd_bound_reverse_ldvi, (dref, C.byref(lay), use_net), log_prob.consts_on)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):

@@ -12,11 +12,8 @@ LDVI and the UHA boundmode have reverse chains of their own (`cmcd_amd.reverse_l
 their own (`cmcd_amd.smc_ldvi`, `cmcd_amd.smc_hais`).  Not here: lgcp, a cooperative kernel form, sharding."""
 import ctypes as C
 
-import torch
-
-from . import _lib
+from . import _chain, _lib
 from . import mcdboundingmachine as mcdbm
-from ._call import check_x, consts_args, _inputs, on_device, _outputs, _workspace
 
 __all__ = ["bound_reverse", "compute_reverse_bound"]
 
@@ -30,28 +27,15 @@ def bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_
     gmm / funnel / many_gmm only (NotImplementedError otherwise; the overdamped modes: `mcdboundingmachine.bound_reverse`).
     eps_schedule / grad_clipping are accepted for the signature and ignored, as by the forward call of this mode."""
     plan = mcdbm._plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    seeds, n = _inputs(seeds, params_flat)
-    device, dim = params_flat.device, params_fixed[0]
-    check_x(x, n, dim, device)
-
-    def launch(dev_index, stream, capturing):
-        nbytes = mcdbm._nbytes(plan, "cmcd_reverse_uha_workspace_bytes", n)
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "rev_uha",
-                        "no 2nd-order reverse-chain kernel for this configuration", retire=True)
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        w, z0, stats = _outputs(n, dim, device)
-        rho0 = torch.empty((n, dim), dtype=torch.float32, device=device)
-        _lib.check(_lib.lib().cmcd_bound_reverse_uha(
-            C.byref(plan.desc), C.byref(plan.lay), seeds.data_ptr(), x.data_ptr(), n, params_flat.data_ptr(),
-            params_flat.numel(), cptr, cnum, ws.data_ptr(), ws.numel(), w.data_ptr(), z0.data_ptr(), rho0.data_ptr(),
-            stats.data_ptr(), stream))
-        return w, z0, rho0, stats
-
-    return on_device(device, launch)
+    L, desc = _lib.lib(), C.byref(plan.desc)
+    return _chain.reverse_call(
+        seeds, x, params_flat, params_fixed[0], True, "rev_uha", "no 2nd-order reverse-chain kernel for this configuration", True,
+        L.cmcd_reverse_uha_workspace_bytes, (desc,), plan.desc_b, L.cmcd_bound_reverse_uha, (desc, C.byref(plan.lay)),
+        log_prob.consts_on)
 
 
 def compute_reverse_bound(seeds, x, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
     """-> (EUBO = mean(w), (w, z0)) of `bound_reverse`: E[w] >= ln Z, the upper half of the bracket whose lower half is
     -compute_bound(...)[0].  +inf when a row of x is non-finite or a chain diverged, never NaN."""
-    return mcdbm.eubo_of(bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
-                                       eps_schedule=eps_schedule, grad_clipping=grad_clipping))
+    return _chain.eubo_of(bound_reverse(seeds, x, params_flat, unflatten, params_fixed, log_prob,
+                                        eps_schedule=eps_schedule, grad_clipping=grad_clipping))

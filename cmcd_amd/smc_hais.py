@@ -16,18 +16,14 @@ a graph.  The reference has no counterpart; the arithmetic is restated in float6
 fallback.
 
 Not here: lgcp (`cmcd_amd.hais_lgcp` runs whole chains only), a cooperative kernel form, sharding of segments."""
-import torch
-
-from . import _lib
+from . import _chain, _lib
 from . import hais
-from ._call import consts_args, _inputs, on_device, _workspace
-from .smc import default_cuts, losses_of
-from .smc_uha import STATE_FIELDS, _drive, _state_inputs, resample_stage
+from ._chain import default_cuts, losses_of
+from .smc_uha import STATE_FIELDS, _missing, resample_stage
 
 __all__ = ["STATE_FIELDS", "segment", "losses_of", "resample_stage", "default_cuts", "smc_bound"]
 
-
-_nbytes = {}      # (target, dim, nbridges, lfsteps, n) -> cmcd_segment_hais_workspace_bytes
+_MISSING = _missing("a UHA segment", "smc_hais")
 
 
 def _fixed(params_fixed, log_prob):
@@ -54,45 +50,15 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     `stats` are the five statistics over -(wpath + lg).  gmm / funnel / many_gmm only (NotImplementedError otherwise, lgcp
     included; the MCD modes: `cmcd_amd.smc`, `cmcd_amd.smc_uha`, `cmcd_amd.smc_ldvi`).  eps_schedule / grad_clipping are
     accepted for the signature and ignored: the mode has neither."""
-    dim, nbridges, lfsteps = _fixed(params_fixed, log_prob)
+    shape = _fixed(params_fixed, log_prob)
     k0, k1 = int(k0), int(k1)
-    device = params_flat.device
-    if k0 == 0:
-        seeds, n = _inputs(state, params_flat)
-        z = torch.empty((n, dim), dtype=torch.float32, device=device)
-        rho = torch.empty((n, dim), dtype=torch.float32, device=device)
-        wpath = torch.empty(n, dtype=torch.float32, device=device)
-        key = torch.empty((n, 2), dtype=torch.int32, device=device)
-    else:
-        seeds = None
-        z, rho, wpath, key, n = _state_inputs(state, params_flat, dim, "a UHA segment", "smc_hais")
-    L = _lib.lib()
-    # the offsets of an Unflatten never change: the layout is built once per tree (these calls are bound by the host at the small
-    # shapes, where a state's five output tensors cost more than the forward call's two: profiles/r22_segment_ldvi_hais.txt)
-    lay = unflatten.__dict__.get("_smc_hais_layout")
-    if lay is None:
-        lay = unflatten._smc_hais_layout = hais._layout(unflatten)
-
-    def launch(dev_index, stream, capturing):
-        shape = (log_prob.target_id, dim, nbridges, lfsteps, n)
-        nbytes = _nbytes.get(shape)
-        if nbytes is None:      # the size query is a pure function of the shape; a refusal (0) is asked again, for its message
-            nbytes = L.cmcd_segment_hais_workspace_bytes(*shape)
-            if nbytes > 0:
-                _nbytes[shape] = nbytes
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "seg_hais",
-                        "no Hamiltonian AIS segment kernel for this target")      # (no prep tables in this mode: nothing to retire)
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        lg = torch.empty(n, dtype=torch.float32, device=device)
-        stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
-        _lib.check(L.cmcd_bound_segment_hais(
-            log_prob.target_id, dim, nbridges, lfsteps, lay, k0, k1, seeds.data_ptr() if seeds is not None else None, n,
-            params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
-            ws.data_ptr(), ws.numel(), z.data_ptr(), rho.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(),
-            stats.data_ptr(), stream))
-        return {"z": z, "rho": rho, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
-
-    return on_device(device, launch)
+    L, shape = _lib.lib(), (log_prob.target_id, *shape)
+    # the offsets of an Unflatten never change: hais._layout builds the struct once per tree.  (No prep tables in this mode:
+    # nothing to retire)
+    return _chain.segment_call(
+        state, k0, k1, params_flat, shape[1], True, _MISSING, "seg_hais", "no Hamiltonian AIS segment kernel for this target",
+        False, L.cmcd_segment_hais_workspace_bytes, shape, shape,
+        L.cmcd_bound_segment_hais, (*shape, hais._layout(unflatten), k0, k1), log_prob.consts_on)
 
 
 def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False, *, groups=1,
@@ -102,5 +68,5 @@ def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedul
     that left the last bridge.  With ess_threshold = 0 nothing is resampled and losses are the single segment [0, K)'s, bit for
     bit.  No host read."""
     _fixed(params_fixed, log_prob)
-    return _drive(segment, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups, cuts,
-                  ess_threshold, seed, trace)
+    return _chain.drive(segment, True, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups,
+                        cuts, ess_threshold, seed, trace)

@@ -15,17 +15,15 @@ restated in float64 NumPy in tests/smc_ldvi_restatement.py.  No CPU fallback.
 Not here: lgcp, a cooperative kernel form, sharding of segments."""
 import ctypes as C
 
-import torch
-
-from . import _lib
+from . import _chain, _lib
 from . import ldvi
-from ._call import consts_args, _inputs, on_device, _workspace
-from .smc import default_cuts, losses_of
-from .smc_uha import STATE_FIELDS, _drive, _state_inputs, resample_stage
+from ._chain import default_cuts, losses_of
+from .smc_uha import STATE_FIELDS, _missing, resample_stage
 
 __all__ = ["STATE_FIELDS", "segment", "losses_of", "resample_stage", "default_cuts", "smc_bound"]
 
 MODES = ldvi.MODES
+_MISSING = _missing("an LDVI segment", "smc_ldvi")
 
 
 def _refuse_other_modes(params_fixed):
@@ -45,34 +43,12 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     the signature and ignored: the mode has neither."""
     _refuse_other_modes(params_fixed)
     desc, lay, use_net = ldvi._plan(unflatten, params_fixed, log_prob)
-    dim, k0, k1 = params_fixed[0], int(k0), int(k1)
-    device = params_flat.device
-    if k0 == 0:
-        seeds, n = _inputs(state, params_flat)
-        z = torch.empty((n, dim), dtype=torch.float32, device=device)
-        rho = torch.empty((n, dim), dtype=torch.float32, device=device)
-        wpath = torch.empty(n, dtype=torch.float32, device=device)
-        key = torch.empty((n, 2), dtype=torch.int32, device=device)
-    else:
-        seeds = None
-        z, rho, wpath, key, n = _state_inputs(state, params_flat, dim, "an LDVI segment", "smc_ldvi")
-    L = _lib.lib()
-
-    def launch(dev_index, stream, capturing):
-        nbytes = L.cmcd_segment_ldvi_workspace_bytes(C.byref(desc), use_net, n)
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "seg_ldvi",
-                        "no LDVI segment kernel for this configuration")
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        lg = torch.empty(n, dtype=torch.float32, device=device)
-        stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
-        _lib.check(L.cmcd_bound_segment_ldvi(
-            C.byref(desc), C.byref(lay), use_net, k0, k1, seeds.data_ptr() if seeds is not None else None, n,
-            params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
-            ws.data_ptr(), ws.numel(), z.data_ptr(), rho.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(),
-            stats.data_ptr(), stream))
-        return {"z": z, "rho": rho, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
-
-    return on_device(device, launch)
+    k0, k1 = int(k0), int(k1)
+    L, dref = _lib.lib(), C.byref(desc)
+    return _chain.segment_call(
+        state, k0, k1, params_flat, params_fixed[0], True, _MISSING, "seg_ldvi", "no LDVI segment kernel for this configuration",
+        False, L.cmcd_segment_ldvi_workspace_bytes, (dref, use_net), (bytes(desc), use_net),
+        L.cmcd_bound_segment_ldvi, (dref, C.byref(lay), use_net, k0, k1), log_prob.consts_on)
 
 
 def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False, *, groups=1,
@@ -81,5 +57,5 @@ def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedul
     Same arguments, same result dict (ln_Z, losses, z, rho, resampled, ess; with trace=True the stages).  With ess_threshold = 0
     nothing is resampled and losses are the single segment [0, K)'s, bit for bit.  No host read."""
     _refuse_other_modes(params_fixed)
-    return _drive(segment, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups, cuts,
-                  ess_threshold, seed, trace)
+    return _chain.drive(segment, True, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups,
+                        cuts, ess_threshold, seed, trace)

@@ -14,16 +14,13 @@ captured into a graph.  The reference has no counterpart; the arithmetic is rest
 tests/smc_uha_restatement.py.  No CPU fallback.
 
 LDVI and the UHA boundmode have segments of their own, `cmcd_amd.smc_ldvi` and `cmcd_amd.smc_hais`: they import `resample_stage`
-and the driver loop (`_drive`) from here.  Not here: lgcp, the cooperative kernel forms, sharding.  (The reverse-time chain of
-this mode: cmcd_amd.reverse_uha.)"""
+from here, and all four families share one call path and one driver loop (cmcd_amd._chain).  Not here: lgcp, the cooperative
+kernel forms, sharding.  (The reverse-time chain of this mode: cmcd_amd.reverse_uha.)"""
 import ctypes as C
 
-import torch
-
-from . import _lib, resample
+from . import _chain, _lib
 from . import mcdboundingmachine as mcdbm
-from ._call import consts_args, _inputs, on_device, _workspace
-from .smc import _state_tensors, default_cuts, losses_of
+from ._chain import default_cuts, losses_of
 
 __all__ = ["STATE_FIELDS", "segment", "losses_of", "resample_stage", "default_cuts", "smc_bound"]
 
@@ -31,13 +28,13 @@ STATE_FIELDS = ("z", "rho", "wpath", "lg", "key")
 MODE = "MCD_CAIS_UHA_sn"
 
 
-def _state_inputs(state, params_flat, dim, what="a 2nd-order segment", module="smc_uha"):
-    """The checks on a state handed to a segment with k0 > 0 -> (z, rho, wpath, key, n)."""
-    if not isinstance(state, dict) or any(k not in state for k in ("z", "rho", "wpath", "key")):
-        raise TypeError(f"{what} with k0 > 0 starts from the state dict an earlier {module}.segment (or resample_stage) "
-                        "returned: z, rho, wpath and key")
-    _inputs(None, params_flat, seedless=True)
-    return _state_tensors(state, params_flat.device, dim, ("z", "rho", "wpath", "key"))
+def _missing(what="a 2nd-order segment", module="smc_uha"):
+    """The TypeError text of this module's, smc_ldvi's and smc_hais's segment for what is no state with momentum."""
+    return (f"{what} with k0 > 0 starts from the state dict an earlier {module}.segment (or resample_stage) returned: z, rho, wpath "
+            "and key")
+
+
+_MISSING = _missing()
 
 
 def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False):
@@ -49,33 +46,12 @@ def segment(state, k0, k1, params_flat, unflatten, params_fixed, log_prob, eps_s
     plan = mcdbm._plan(unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
     if params_fixed[2] != MODE:
         raise NotImplementedError(f"cmcd_amd.smc_uha runs {MODE} only (boundmode {params_fixed[2]!r}: cmcd_amd.smc)")
-    dim, k0, k1 = params_fixed[0], int(k0), int(k1)
-    device = params_flat.device
-    if k0 == 0:
-        seeds, n = _inputs(state, params_flat)
-        z = torch.empty((n, dim), dtype=torch.float32, device=device)
-        rho = torch.empty((n, dim), dtype=torch.float32, device=device)
-        wpath = torch.empty(n, dtype=torch.float32, device=device)
-        key = torch.empty((n, 2), dtype=torch.int32, device=device)
-    else:
-        seeds = None
-        z, rho, wpath, key, n = _state_inputs(state, params_flat, dim)
-
-    def launch(dev_index, stream, capturing):
-        nbytes = mcdbm._nbytes(plan, "cmcd_segment_uha_workspace_bytes", n)
-        ws = _workspace(dev_index, device, stream, capturing, nbytes, "seg_uha",
-                        "no 2nd-order segment kernel for this configuration", retire=True)
-        cptr, cnum = consts_args(log_prob.consts_on(device))
-        lg = torch.empty(n, dtype=torch.float32, device=device)
-        stats = torch.empty(_lib.NSTATS, dtype=torch.float64, device=device)
-        _lib.check(_lib.lib().cmcd_bound_segment_uha(
-            C.byref(plan.desc), C.byref(plan.lay), k0, k1, seeds.data_ptr() if seeds is not None else None, n,
-            params_flat.data_ptr(), params_flat.numel(), cptr, cnum,
-            ws.data_ptr(), ws.numel(), z.data_ptr(), rho.data_ptr(), wpath.data_ptr(), key.data_ptr(), lg.data_ptr(),
-            stats.data_ptr(), stream))
-        return {"z": z, "rho": rho, "wpath": wpath, "lg": lg, "key": key, "stats": stats, "k": k1}
-
-    return on_device(device, launch)
+    k0, k1 = int(k0), int(k1)
+    L, desc = _lib.lib(), C.byref(plan.desc)
+    return _chain.segment_call(
+        state, k0, k1, params_flat, params_fixed[0], True, _MISSING, "seg_uha", "no 2nd-order segment kernel for this configuration",
+        True, L.cmcd_segment_uha_workspace_bytes, (desc,), plan.desc_b,
+        L.cmcd_bound_segment_uha, (desc, C.byref(plan.lay), k0, k1), log_prob.consts_on)
 
 
 def resample_stage(state, groups=1, ess_threshold=0.5, seed=0):
@@ -83,27 +59,7 @@ def resample_stage(state, groups=1, ess_threshold=0.5, seed=0):
     (wpath_j = -lg[a_j]); a resampled group takes z AND rho from its ancestors — ONE resampling launch on the rows [z | rho] of
     width 2 dim.  KEYS STAY WITH THEIR SLOT.  Every other group is passed through unchanged (identity ancestors).
     -> (new state, {"resampled"[groups] bool, "ess"[groups], "ln_Z_increment"[groups] f64, "ancestors"[N] int64})."""
-    if "rho" not in state:
-        raise TypeError("a 2nd-order state carries the momentum: state['rho'] is missing")
-    wpath, lg, z, rho = state["wpath"], state["lg"], state["z"], state["rho"]
-    n, groups = wpath.numel(), int(groups)
-    if groups < 1 or n % groups != 0:
-        raise ValueError("N must be a multiple of groups")
-    m = n // groups
-    dim = z.shape[1]
-    zr_res, index, st = resample.resample(losses_of(state), torch.cat([z, rho], dim=1), groups=groups, seed=seed)
-    trig = (st["ess"] < float(ess_threshold) * m) & (st["diverged"] == 0) & (st["n_finite"] > 0)
-    mask = trig.repeat_interleave(m)
-    index = index.to(torch.int64)
-    ancestors = torch.where(mask, index, torch.arange(n, dtype=torch.int64, device=wpath.device))
-    lg_anc = lg[ancestors]
-    new = {k: v for k, v in state.items() if k != "stats"}      # (the statistics described the weights before this stage)
-    new["z"] = torch.where(mask[:, None], zr_res[:, :dim], z)
-    new["rho"] = torch.where(mask[:, None], zr_res[:, dim:], rho)
-    new["wpath"] = torch.where(mask, -lg_anc, wpath)
-    new["lg"] = lg_anc
-    inc = torch.where(trig, st["ln_Z"], torch.zeros_like(st["ln_Z"]))
-    return new, {"resampled": trig, "ess": st["ess"], "ln_Z_increment": inc, "ancestors": ancestors}
+    return _chain.resample_stage(state, groups, ess_threshold, seed, momentum=True)
 
 
 def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule=None, grad_clipping=False, *, groups=1,
@@ -113,43 +69,5 @@ def smc_bound(seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedul
     stages carry {"k", "wpath", "lg", "ancestors"} as there.  With ess_threshold = 0 nothing is resampled and losses are the single
     segment [0, K)'s, bit for bit.  Each segment runs the prep launch and evaluates the target at its first state again.  No host
     read."""
-    return _drive(segment, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups, cuts,
-                  ess_threshold, seed, trace)
-
-
-def _drive(segment, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups, cuts, ess_threshold,
-           seed, trace):
-    """The driver loop of `smc_bound` for a state with momentum, with the segment call handed in (this module's, smc_ldvi's,
-    smc_hais's): params_fixed[1] is nbridges in all three."""
-    K = int(params_fixed[1])
-    cuts = default_cuts(K) if cuts is None else [int(c) for c in cuts]
-    if any(c <= 0 or c >= K for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):
-        raise ValueError(f"cuts must be ascending bridges inside (0, {K})")
-    seeds, n = _inputs(seeds, params_flat)
-    groups = int(groups)
-    if groups < 1 or n % groups != 0:
-        raise ValueError("N must be a multiple of groups")
-    args = (params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping)
-    edges = cuts + [K]
-    state = segment(seeds, 0, edges[0], *args)
-    ln_z = torch.zeros(groups, dtype=torch.float64, device=params_flat.device)
-    resampled, ess, stages = [], [], []
-    for c, nxt in zip(cuts, edges[1:]):
-        arrived = state
-        state, info = resample_stage(state, groups, ess_threshold, seed + c)
-        ln_z = ln_z + info["ln_Z_increment"]
-        resampled.append(info["resampled"])
-        ess.append(info["ess"])
-        if trace:
-            stages.append({"k": c, "wpath": arrived["wpath"], "lg": arrived["lg"], "ancestors": info["ancestors"]})
-        state = segment(state, c, nxt, *args)
-    losses = losses_of(state)
-    final = resample.importance_stats(losses, groups)
-    ess.append(final["ess"])
-    out = {"ln_Z": ln_z + final["ln_Z"], "losses": losses, "z": state["z"], "rho": state["rho"],
-           "resampled": torch.stack(resampled) if resampled else torch.zeros((0, groups), dtype=torch.bool, device=losses.device),
-           "ess": torch.stack(ess)}
-    if trace:
-        stages.append({"k": K, "wpath": state["wpath"], "lg": state["lg"], "ancestors": None})
-        out["trace"] = stages
-    return out
+    return _chain.drive(segment, True, seeds, params_flat, unflatten, params_fixed, log_prob, eps_schedule, grad_clipping, groups,
+                        cuts, ess_threshold, seed, trace)

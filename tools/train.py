@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 import torch
 from cmcd_amd import boundingmachine as bm
 from cmcd_amd import mcdboundingmachine as mcdbm
-from cmcd_amd import opt, utils
+from cmcd_amd import _chain, opt, utils
 from cmcd_amd.model_handler import load_model
 
 ap = argparse.ArgumentParser()
@@ -130,14 +130,7 @@ if len(res) > 2 and cfg.model in ("funnel", "gmm", "many_gmm") and RANK == 0 and
         (cfg.boundmode in ("MCD_CAIS_sn", "MCD_CAIS_var_sn", "MCD_ULA", "MCD_ULA_sn", "MCD_CAIS_UHA_sn") or LDVI or
          (cfg.boundmode == "UHA" and cfg.eubo_uha)):
     from cmcd_amd.model_handler import exact_target_draws
-    if cfg.boundmode == "MCD_CAIS_UHA_sn":      # the chain carries a momentum: its own call, same diagnostics on w
-        from cmcd_amd import reverse_uha as rev
-    elif LDVI:
-        from cmcd_amd import reverse_ldvi as rev
-    elif cfg.boundmode == "UHA":
-        from cmcd_amd import reverse_hais as rev
-    else:
-        rev = mcdbm
+    rev = _chain.reverse_module(cfg.boundmode)      # (the momentum modes: their own call, same diagnostics on w)
     x_tgt = torch.from_numpy(exact_target_draws(cfg.model, res[2], 3, cfg.n_samples * cfg.n_input_dist_seeds, dim)).cuda()
 
 
@@ -164,14 +157,7 @@ def evaluate(p, tag):
          (cfg.boundmode == "UHA" and cfg.nbridges >= 1))
     if cfg.smc_eval and smc_on:
         from cmcd_amd import resample, sinkhorn
-        if cfg.boundmode == "MCD_CAIS_UHA_sn":
-            from cmcd_amd import smc_uha as smc
-        elif LDVI:
-            from cmcd_amd import smc_ldvi as smc
-        elif cfg.boundmode == "UHA":
-            from cmcd_amd import smc_hais as smc
-        else:
-            from cmcd_amd import smc
+        smc = _chain.smc_module(cfg.boundmode)
         G = cfg.n_input_dist_seeds
         out = smc.smc_bound(eval_seeds, p, unflatten, fixed, log_prob_model, eps_schedule=cfg.eps_schedule,
                             grad_clipping=cfg.grad_clipping, groups=G, seed=cfg.seed)
