@@ -104,6 +104,15 @@ int launch_net_tails(const cmcd_desc& d, int din, int eps_schedule, const cmcd_l
                      int HP, float* dds_tail, float* grad, void* stream);
 
 // cmcd_lgcp.hip: the d = 1600 path (per-bridge launch sequence)
+// mu0 is a model constant, log(126) - 0.5 * 1.91 (model_handler.py:346); the state updates read the device copy in tc, the GEMMs
+// take it as the operand shift
+constexpr float kLgcpMu0 = 3.8812819069514780f;
+// the workspace carve-up of cmcd_lgcp.hip and cmcd_lgcp_wide.hip: offsets in floats, every slot a multiple of four
+struct WsBump {
+  int64_t o;
+  int64_t take(int64_t cnt) { const int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; }
+  void align_double() { o = (o + 1) & ~int64_t(1); }
+};
 int64_t lgcp_workspace_floats(const cmcd_desc& d, int64_t n, int64_t base);
 // tables_ready (cmcd_bound_forward_prepared): the workspace still holds the first-layer bias table and the packed weight copies
 // of the same parameters — those launches are skipped (the per-call zeroing of the operands is not)

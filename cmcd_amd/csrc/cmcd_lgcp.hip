@@ -1351,11 +1351,26 @@ struct LgcpWs {
   LgcpLane lane[kLanes];
 };
 
-// the no-split-K forward serves operands of up to 1664 inputs (kNskChunks) whose state part is whole 16-column tiles;
-// desc.reserved == 3 pins the split-K sequence (A / B measurements, tests)
-static bool lgcp_nsk_ok(const cmcd_desc& d) {
-  const int D = d.dim, IN = D + d.emb_dim;
-  return d.reserved != 3 && D % 16 == 0 && IN <= 16 * kNskChunks && d.mode != CMCD_MODE_CAIS_UHA_SN;
+// The shape facts of a call, once: the network sees a state of width ZW (D, or 2 D on [z; rho] in the 2nd-order mode) and is
+// IN = ZW + E wide; cb*: 64-column blocks of the split-K GEMM, t*: 16-column tiles of the no-split-K GEMM, nch: 16-deep chunks of
+// a packed operand (one or two rounds of kNskChunks).
+struct LgcpShape {
+  int D, ZW, E, IN, K;
+  int cbD, cbIN, cbZW, tD, tIN, tZW;
+  int rounds, nch;
+  // the no-split-K GEMM serves a state of whole 16-column tiles and operands of up to 1664 inputs per round; desc.reserved == 3
+  // pins the split-K sequence (A / B measurements, tests)
+  bool nsk;
+};
+static LgcpShape lgcp_shape(const cmcd_desc& d) {
+  LgcpShape s;
+  s.D = d.dim; s.rounds = d.mode == CMCD_MODE_CAIS_UHA_SN ? 2 : 1; s.ZW = s.rounds * s.D;
+  s.E = d.emb_dim; s.IN = s.ZW + s.E; s.K = d.nbridges;
+  s.cbD = (s.D + 63) / 64; s.cbIN = (s.IN + 63) / 64; s.cbZW = (s.ZW + 63) / 64;
+  s.tD = s.D / 16; s.tIN = (s.IN + 15) / 16; s.tZW = s.ZW / 16;
+  s.nch = s.rounds * kNskChunks;
+  s.nsk = d.reserved != 3 && s.D % 16 == 0 && s.D <= 16 * kNskChunks && s.IN <= 16 * s.nch;
+  return s;
 }
 
 static int lgcp_lanes(int64_t n) {
@@ -1364,27 +1379,27 @@ static int lgcp_lanes(int64_t n) {
 }
 
 static LgcpWs lgcp_ws(const cmcd_desc& d, int64_t n, int64_t base) {
-  const int64_t D = d.dim, IN = D + d.emb_dim, K = d.nbridges;
+  const LgcpShape s = lgcp_shape(d);
+  const int64_t D = s.D, IN = s.IN, K = s.K;
   LgcpWs w;
-  int64_t o = base;
-  auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; };
+  WsBump b{base};
   auto take_lane_head = [&](LgcpLane& l) {
-    l.x = take(kMP * D); l.xp = take(kMP * D);
-    l.u1 = take(kMP * IN); l.u2 = take(kMP * IN); l.pre1 = take(kMP * IN); l.pre2 = take(kMP * IN);
-    l.kr = take(kSplit * kMP * D); l.slab1 = take(kSplit * kMP * IN); l.slab2 = take(kSplit * kMP * IN);
-    l.sn = take(kSplit * kMP * D);
-    l.w = take(kMP); l.keys = take(2 * kMP); l.gkey = take(4 * kMP);
+    l.x = b.take(kMP * D); l.xp = b.take(kMP * D);
+    l.u1 = b.take(kMP * IN); l.u2 = b.take(kMP * IN); l.pre1 = b.take(kMP * IN); l.pre2 = b.take(kMP * IN);
+    l.kr = b.take(kSplit * kMP * D); l.slab1 = b.take(kSplit * kMP * IN); l.slab2 = b.take(kSplit * kMP * IN);
+    l.sn = b.take(kSplit * kMP * D);
+    l.w = b.take(kMP); l.keys = b.take(2 * kMP); l.gkey = b.take(4 * kMP);
   };
   auto take_lane_tail = [&](LgcpLane& l) {
-    l.slots = take(3 * ((D + 63) / 64) * kMP);             // wslot | fkslot | lpslot
-    l.counters = take(((D + 63) / 64) + ((IN + 63) / 64)); // int arrival counters of the widest launch
+    l.slots = b.take(3 * s.cbD * kMP);            // wslot | fkslot | lpslot
+    l.counters = b.take(s.cbD + s.cbIN);          // int arrival counters of the widest launch
   };
-  w.bias1 = take((K + 1) * IN);
+  w.bias1 = b.take((K + 1) * IN);
   take_lane_head(w.lane[0]);
-  w.gktab = take(2 * K * n);
+  w.gktab = b.take(2 * K * n);
   take_lane_tail(w.lane[0]);
-  o = (o + 1) & ~int64_t(1);
-  w.partials = take(n * CMCD_NSTATS * 2);
+  b.align_double();
+  w.partials = b.take(n * CMCD_NSTATS * 2);
   for (int l = 1; l < kLanes; ++l) {
     if (l < lgcp_lanes(n)) {
       take_lane_head(w.lane[l]);
@@ -1394,31 +1409,182 @@ static LgcpWs lgcp_ws(const cmcd_desc& d, int64_t n, int64_t base) {
     }
   }
   w.w1p = w.w2p = w.w3p = w.kip = 0;
-  if (lgcp_nsk_ok(d)) {
-    const int64_t tIN = (IN + 15) / 16, tD = D / 16, per_tile = (int64_t)kNskChunks * 256;
-    w.w1p = take(tIN * per_tile); w.w2p = take(tIN * per_tile); w.w3p = take(tD * per_tile); w.kip = take(tD * per_tile);
+  if (s.nsk) {
+    const int64_t per_tile = (int64_t)kNskChunks * 256;
+    w.w1p = b.take(s.tIN * per_tile); w.w2p = b.take(s.tIN * per_tile); w.w3p = b.take(s.tD * per_tile); w.kip = b.take(s.tD * per_tile);
     for (int l = 0; l < kLanes; ++l)
-      w.lane[l].nsk = (l < lgcp_lanes(n) || l == 0) ? take(kNskOps * kNskOperand + 3 * tD * kMP) : w.lane[0].nsk;
+      w.lane[l].nsk = (l < lgcp_lanes(n) || l == 0) ? b.take(kNskOps * kNskOperand + 3 * s.tD * kMP) : w.lane[0].nsk;
   }
-  w.total = o;
+  w.total = b.o;
   return w;
 }
 
-struct LgcpUhaWs;
-static LgcpUhaWs lgcp_uha_ws(const cmcd_desc& d, int64_t n, int64_t base);
-static int64_t lgcp_uha_ws_total(const cmcd_desc& d, int64_t n, int64_t base);
-// r04: tables of the gradient workspace that the forward's consumers fill when it runs for a gradient call (lgcp_keep below
-// lgcp_grad_ws): [(K+1) n][IN] pre1, u1, pre2, u2 and [(K+1) n][D] kr, sn.  `on` is false when the forward does not run on the
-// no-split-K GEMM or the tables would pass 1 GB: the reverse sweep then recomputes every evaluation as it did in r01 - r03.
-struct LgcpKeep { float *pre1, *u1, *pre2, *u2, *kr, *sn; bool on; };
-static LgcpKeep lgcp_keep(const cmcd_desc& d, int64_t n, float* gws);
+// The 2nd-order mode's forward workspace (the sequence: header above lgcp_uha_forward)
+struct LgcpUhaWs {
+  int64_t bias1;                                   // [K+1][IN]
+  int64_t zr, zrp, zn, rpp;                        // [kMP][2D], [kMP][2D], [kMP][D], [kMP][D]
+  int64_t u1, u2, pre1, pre2;                      // [kMP][IN]
+  int64_t slab1, slab2, sn, kr;                    // [kSplit][kMP][IN] x2, [kSplit][kMP][D] x2
+  int64_t w, fk, keys, gkey, counters, partials, total;
+  // r04, no-split-K form: packed weights (W1[:2d] | W2 | W3 | K^-1 with 2 kNskChunks chunks per tile: K^-1 zero beyond d) and
+  // packed operands zr | zrp | u1 | u2 | zn (2 kNskOperand floats each)
+  int64_t w1p, w2p, w3p, kip, ops;
+};
 
-static int lgcp_uha_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, const int32_t* seeds, int64_t n,
-                            const float* params, const float* tc, float* ws, float* out_loss, float* out_z,
-                            double** partials_out, float* traj, hipStream_t stream, float* keep_gws);
-// the 2nd-order sequence's kept tables: [2 K n][IN] pre1, u1, pre2, u2 and [2 K n][D] sn (rows 2 i: s([z_i; rho_i], i), 2 i + 1:
-// s([z_i; rho'_i], i)), [(K+1) n][D] kr (K^-1 (z_e - mu0))
-static LgcpKeep lgcp_uha_keep(const cmcd_desc& d, int64_t n, float* gws);
+static LgcpUhaWs lgcp_uha_ws(const cmcd_desc& d, int64_t n, int64_t base) {
+  const LgcpShape s = lgcp_shape(d);
+  const int64_t D = s.D, IN = s.IN, K = s.K;
+  LgcpUhaWs w;
+  WsBump b{base};
+  w.bias1 = b.take((K + 1) * IN);
+  w.zr = b.take(kMP * 2 * D); w.zrp = b.take(kMP * 2 * D); w.zn = b.take(kMP * D); w.rpp = b.take(kMP * D);
+  w.u1 = b.take(kMP * IN); w.u2 = b.take(kMP * IN); w.pre1 = b.take(kMP * IN); w.pre2 = b.take(kMP * IN);
+  w.slab1 = b.take(kSplit * kMP * IN); w.slab2 = b.take(kSplit * kMP * IN);
+  w.sn = b.take(kSplit * kMP * D); w.kr = b.take(kSplit * kMP * D);
+  w.w = b.take(kMP); w.fk = b.take(kMP); w.keys = b.take(2 * kMP); w.gkey = b.take(2 * kMP);
+  w.counters = b.take(s.cbD + s.cbIN);
+  b.align_double();
+  w.partials = b.take(n * CMCD_NSTATS * 2);
+  w.w1p = w.w2p = w.w3p = w.kip = w.ops = 0;
+  if (s.nsk) {
+    const int64_t big = (int64_t)s.nch * 256;
+    w.w1p = b.take(s.tIN * big); w.w2p = b.take(s.tIN * big); w.w3p = b.take(s.tD * big); w.kip = b.take(s.tD * big);
+    w.ops = b.take(5 * 2 * kNskOperand);
+  }
+  w.total = b.o;
+  return w;
+}
+
+// What both reverse sweeps (lgcp_grad, lgcp_uha_grad) share: the transposed weights, the buffers of one network backward, the
+// row tables of the deferred contractions (R rows: (K + 1) n, or 2 K n in the 2nd-order mode) and what the forward keeps.
+struct LgcpSweepWs {
+  int64_t wt1, wt2, wt3;                       // transposed weights: W1^T (1st order: all IN rows; 2nd: W1[:2D]^T), W2^T, W3^T
+  int64_t dO, v;                               // [kMP][D]
+  int64_t hv, dxf;                             // [kSplit][kMP][D] ([kSplit][kMP][2D] dxf in the 2nd-order mode)
+  int64_t du2s, ts;                            // [kSplit][kMP][IN] slabs of the two IN-wide backward GEMMs
+  int64_t du2, du1, da2, da1;                  // [kMP][IN]
+  int64_t gmu_acc, glam_acc;                   // [kMP][D]
+  int64_t U1, U2, DA1, DA2;                    // [R][IN]
+  int64_t DO;                                  // [R][D]
+  int64_t S, S2, gbeta, geps, gb2;             // tables
+  int64_t counters;                            // arrival counters of the fused GEMMs (ints)
+  int64_t zero_lo, zero_hi;                    // range to clear per call
+  // r04: tables the forward's consumers fill when it runs for a gradient call (lgcp_keep): [R][IN] pre1, pre2 (u1 / u2 go to U1 /
+  // U2), [R][D] sn and kr ([(K+1) n][D] kr in the 2nd-order mode); 0 floats when `keep` is off
+  int64_t kpre1, kpre2, kkr, ksn;
+  bool keep;
+  int64_t bops, wt3p, wt2p, wt1p;              // keep: packed dO | v | da2 | da1 operands and packed W3^T, W2^T, W1[:ZW]^T
+  int64_t total;
+};
+
+// `on` is false when the forward does not run on the no-split-K GEMM or the tables would pass 1 GB: the reverse sweep then
+// recomputes every evaluation as it did in r01 - r03.  2nd-order mode: rows 2 i: s([z_i; rho_i], i), 2 i + 1: s([z_i; rho'_i], i);
+// kr [(K+1) n][D] (K^-1 (z_e - mu0))
+struct LgcpKeep { float *pre1 = nullptr, *u1 = nullptr, *pre2 = nullptr, *u2 = nullptr, *kr = nullptr, *sn = nullptr; bool on = false; };
+static LgcpKeep lgcp_keep(const LgcpSweepWs& g, float* gws) {
+  if (!g.keep) return LgcpKeep{};
+  return LgcpKeep{gws + g.kpre1, gws + g.U1, gws + g.kpre2, gws + g.U2, gws + g.kkr, gws + g.ksn, true};
+}
+
+// buffers of one forward recompute (two sets: evaluation e-1 is recomputed on a side stream while the backward
+// pass of evaluation e reads the other set; 2nd-order mode: evaluation A = s([z; rho]), B = s([z; rho']), zin their operands)
+struct LgcpFwdSet {
+  int64_t zin, kr, slab1, pre1, u1, slab2, pre2, u2, sn;
+};
+
+struct LgcpGradWs : LgcpSweepWs {
+  int64_t lamn, lam_part, gE, gprev;           // [kMP][D]
+  int64_t gfac;                                // [K+1] per-evaluation terms
+  int64_t adjpart, gb_lo, ge_lo, gb_hi, ge_hi; // adjoint step partial sums; the four [K+1] slots are unused since the reduction
+                                               // forms gbeta / geps itself (kept: the workspace layout is unchanged)
+  LgcpFwdSet fs[2];
+};
+
+static LgcpGradWs lgcp_grad_ws(const cmcd_desc& d, int64_t n) {
+  const LgcpShape s = lgcp_shape(d);
+  const int64_t D = s.D, IN = s.IN, K = s.K, R = (K + 1) * n;
+  LgcpGradWs w;
+  WsBump b{0};
+  w.wt1 = b.take(IN * IN); w.wt2 = b.take(IN * IN); w.wt3 = b.take(D * IN);
+  w.dO = b.take(kMP * D); w.v = b.take(kMP * D); w.lam_part = b.take(kMP * D); w.gprev = b.take(kMP * D);
+  w.hv = b.take(kSplit * kMP * D); w.dxf = b.take(kSplit * kMP * D);
+  w.du2s = b.take(kSplit * kMP * IN); w.ts = b.take(kSplit * kMP * IN);
+  w.du2 = b.take(kMP * IN); w.du1 = b.take(kMP * IN); w.da2 = b.take(kMP * IN); w.da1 = b.take(kMP * IN);
+  w.U1 = b.take(R * IN); w.U2 = b.take(R * IN); w.DA1 = b.take(R * IN); w.DA2 = b.take(R * IN); w.DO = b.take(R * D);
+  for (LgcpFwdSet& f : w.fs) {
+    f.zin = 0;
+    f.kr = b.take(kSplit * kMP * D); f.slab1 = b.take(kSplit * kMP * IN); f.pre1 = b.take(kMP * IN);
+    f.u1 = b.take(kMP * IN); f.slab2 = b.take(kSplit * kMP * IN); f.pre2 = b.take(kMP * IN); f.u2 = b.take(kMP * IN);
+    f.sn = b.take(kSplit * kMP * D);
+  }
+  w.zero_lo = b.o;
+  w.lamn = b.take(kMP * D); w.gE = b.take(kMP * D);
+  w.gmu_acc = b.take(kMP * D); w.glam_acc = b.take(kMP * D);
+  w.S = b.take((K + 1) * IN); w.S2 = b.take((K + 1) * IN);
+  w.gbeta = b.take(K); w.geps = b.take(K); w.gfac = b.take(K + 1); w.gb2 = b.take(IN);
+  w.counters = b.take(2 * (s.cbD + s.cbIN));     // side stream's set | caller's stream's set
+  w.zero_hi = b.o;
+  w.adjpart = b.take((K + 1) * n * s.cbD * 8);
+  w.gb_lo = b.take(K + 1); w.ge_lo = b.take(K + 1); w.gb_hi = b.take(K + 1); w.ge_hi = b.take(K + 1);
+  // the forward's kept activations (behind everything else: the layout above does not move when they are off)
+  w.keep = s.nsk && R * (2 * IN + 2 * D) <= (int64_t(1) << 28);
+  w.kpre1 = b.take(w.keep ? R * IN : 0); w.kpre2 = b.take(w.keep ? R * IN : 0);
+  w.kkr = b.take(w.keep ? R * D : 0); w.ksn = b.take(w.keep ? R * D : 0);
+  w.bops = b.take(w.keep ? 4 * kNskOperand : 0);
+  w.wt3p = b.take(w.keep ? s.tIN * kNskChunks * 256 : 0); w.wt2p = b.take(w.keep ? s.tIN * kNskChunks * 256 : 0);
+  w.wt1p = b.take(w.keep ? s.tD * kNskChunks * 256 : 0);
+  w.total = b.o;
+  return w;
+}
+
+struct LgcpUhaGradWs : LgcpSweepWs {
+  LgcpFwdSet fs[2];                             // evaluation A = s([z; rho]), B = s([z; rho'])
+  int64_t kr;                                   // [kSplit][kMP][D]
+  int64_t arp, gb, lrn, arppc;                  // [kMP][D]
+  int64_t XIN;                                  // [2 K n][2D]
+  int64_t lz, lr;                               // [kMP][D]
+  int64_t geta, gepsd;                          // [kMP]
+  int64_t sc;                                   // [(K+1)][n][8]
+  int64_t kip1;                                 // keep: packed K^-1 (one round)
+};
+
+static LgcpUhaGradWs lgcp_uha_grad_ws(const cmcd_desc& d, int64_t n) {
+  const LgcpShape s = lgcp_shape(d);
+  const int64_t D = s.D, IN = s.IN, K = s.K, R = 2 * K * n;
+  LgcpUhaGradWs w;
+  WsBump b{0};
+  w.wt1 = b.take(IN * 2 * D); w.wt2 = b.take(IN * IN); w.wt3 = b.take(D * IN);
+  for (LgcpFwdSet& f : w.fs) {
+    f.kr = 0;
+    f.zin = b.take(kMP * 2 * D); f.slab1 = b.take(kSplit * kMP * IN); f.pre1 = b.take(kMP * IN); f.u1 = b.take(kMP * IN);
+    f.slab2 = b.take(kSplit * kMP * IN); f.pre2 = b.take(kMP * IN); f.u2 = b.take(kMP * IN); f.sn = b.take(kSplit * kMP * D);
+  }
+  w.kr = b.take(kSplit * kMP * D); w.hv = b.take(kSplit * kMP * D);
+  w.v = b.take(kMP * D); w.dO = b.take(kMP * D); w.arp = b.take(kMP * D); w.gb = b.take(kMP * D); w.lrn = b.take(kMP * D);
+  w.arppc = b.take(kMP * D);
+  w.du2s = b.take(kSplit * kMP * IN); w.ts = b.take(kSplit * kMP * IN);
+  w.du2 = b.take(kMP * IN); w.du1 = b.take(kMP * IN); w.da2 = b.take(kMP * IN); w.da1 = b.take(kMP * IN);
+  w.dxf = b.take(kSplit * kMP * 2 * D);
+  w.XIN = b.take(R * 2 * D); w.U1 = b.take(R * IN); w.U2 = b.take(R * IN); w.DA1 = b.take(R * IN); w.DA2 = b.take(R * IN);
+  w.DO = b.take(R * D);
+  w.zero_lo = b.o;
+  w.lz = b.take(kMP * D); w.lr = b.take(kMP * D); w.gmu_acc = b.take(kMP * D); w.glam_acc = b.take(kMP * D);
+  w.geta = b.take(kMP); w.gepsd = b.take(kMP);
+  w.S = b.take((K + 1) * IN); w.S2 = b.take((K + 1) * IN); w.gb2 = b.take(IN); w.gbeta = b.take(K); w.geps = b.take(K);
+  w.counters = b.take(s.cbD + s.cbIN);
+  w.sc = b.take((K + 1) * n * 8);
+  w.zero_hi = b.o;
+  // the forward's kept activations (behind everything else, outside the cleared range)
+  w.keep = s.nsk && R * (2 * IN + D) + (K + 1) * n * D <= (int64_t(1) << 28);
+  w.kpre1 = b.take(w.keep ? R * IN : 0); w.kpre2 = b.take(w.keep ? R * IN : 0);
+  w.ksn = b.take(w.keep ? R * D : 0); w.kkr = b.take(w.keep ? (K + 1) * n * D : 0);
+  const int64_t c1 = kNskChunks * 256, c2 = 2 * c1;
+  w.bops = b.take(w.keep ? 6 * kNskOperand : 0);        // dO, v: kNskOperand each; da2, da1: 2 kNskOperand each
+  w.wt3p = b.take(w.keep ? s.tIN * c1 : 0); w.wt2p = b.take(w.keep ? s.tIN * c2 : 0); w.wt1p = b.take(w.keep ? s.tZW * c2 : 0);
+  w.kip1 = b.take(w.keep ? s.tD * c1 : 0);
+  w.total = b.o;
+  return w;
+}
 
 // desc.reserved (the kernel-variant hook of tests / probes): 1 pins the 32-row passes, 2 the wide-batch path
 bool lgcp_use_wide(const cmcd_desc& d, int64_t n, bool keeps_trajectory) {
@@ -1427,10 +1593,14 @@ bool lgcp_use_wide(const cmcd_desc& d, int64_t n, bool keeps_trajectory) {
 }
 
 int64_t lgcp_workspace_floats(const cmcd_desc& d, int64_t n, int64_t base) {
-  if (d.mode == CMCD_MODE_CAIS_UHA_SN) return lgcp_uha_ws_total(d, n, base);
+  if (d.mode == CMCD_MODE_CAIS_UHA_SN) return lgcp_uha_ws(d, n, base).total;
   // a gradient call keeps the trajectory and stays on the 32-row passes: the query covers whichever form the call takes
   const int64_t narrow = lgcp_ws(d, n, base).total;
   return lgcp_use_wide(d, n, false) ? std::max(narrow, lgcp_wide_workspace_floats(d, n, base)) : narrow;
+}
+
+int64_t lgcp_grad_workspace_floats(const cmcd_desc& d, int64_t n) {
+  return d.mode == CMCD_MODE_CAIS_UHA_SN ? lgcp_uha_grad_ws(d, n).total : lgcp_grad_ws(d, n).total;
 }
 
 int lgcp_launch_prep(const cmcd_desc& d, const cmcd_layout& lay, const float* params, float* bias1, void* stream) {
@@ -1440,16 +1610,16 @@ int lgcp_launch_prep(const cmcd_desc& d, const cmcd_layout& lay, const float* pa
   return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
 }
 
-static int lgcp_gemm_attrs() {
-  const int gemm_lds = int(size_t(kStage * kAsLd + kQuarters * kMP * 64) * 4);
+constexpr int kGemmLds = int(size_t(kStage * kAsLd + kQuarters * kMP * 64) * 4);   // dynamic LDS of every lgcp_gemm_kernel launch
+static bool lgcp_gemm_attrs() {
   const void* fns[5] = {reinterpret_cast<const void*>(lgcp_gemm_kernel<EPI_ACTB>),
                         reinterpret_cast<const void*>(lgcp_gemm_kernel<EPI_NONE>),
                         reinterpret_cast<const void*>(lgcp_gemm_kernel<EPI_ACT>),
                         reinterpret_cast<const void*>(lgcp_gemm_kernel<EPI_STEP>),
                         reinterpret_cast<const void*>(lgcp_gemm_kernel<EPI_STEP_NONET>)};
   for (const void* fn : fns)
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds) != hipSuccess) return -1;
-  return gemm_lds;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmLds) != hipSuccess) return false;
+  return true;
 }
 
 // Up to three ranges of 32-bit words (float tables and the int arrival counters alike) start from zero.  A launch, not
@@ -1472,251 +1642,82 @@ static int lgcp_zero(hipStream_t stream, void* p0, int64_t n0, void* p1 = nullpt
   return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
 }
 
-int lgcp_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, const int32_t* seeds, int64_t n,
-                 const float* params, const float* tc, float* ws, float* out_loss, float* out_z,
-                 double** partials_out, float* traj, void* stream_, bool tables_ready, float* keep_gws) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (d.mode == CMCD_MODE_CAIS_UHA_SN)
-    return lgcp_uha_forward(d, lay, sw, seeds, n, params, tc, ws, out_loss, out_z, partials_out, traj, stream, keep_gws);
-  if (lgcp_use_wide(d, n, traj != nullptr))
-    return lgcp_wide_forward(d, lay, sw, seeds, n, params, tc, ws, out_loss, out_z, partials_out, stream_, tables_ready);
-  const int D = d.dim, E = d.emb_dim, IN = D + E, K = d.nbridges;
-  const LgcpWs w = lgcp_ws(d, n, sw.total_floats);
-  if (d.mode != CMCD_MODE_ULA && !tables_ready) {   // MCD_ULA has no network leaves at all
-    LgcpPrepArgs pa{params, ws + w.bias1, lay, D, E, K, IN};
-    hipLaunchKernelGGL(lgcp_prep_kernel, dim3((IN + 255) / 256, K + 1), dim3(256), 0, stream, pa);
-  }
-  const int gemm_lds = lgcp_gemm_attrs();
-  if (gemm_lds < 0) return CMCD_ERR_HIP;
-  // r04: the forward runs on the no-split-K GEMM (header above lgcp_nsk_kernel); weights re-packed once per call
-  const bool nsk = lgcp_nsk_ok(d);
-  const int tIN = (IN + 15) / 16, tD = D / 16;
-  if (nsk && !tables_ready) {
-    NskPackArgs pk{};
-    int np = 0;
-    auto pack = [&](const float* src, int Kr, int Nr, int64_t dst, int nt) {
-      pk.src[np] = src; pk.dst[np] = ws + dst; pk.K[np] = Kr; pk.N[np] = Nr; pk.ntile[np] = nt; ++np;
-    };
-    pack(tc, D, D, w.kip, tD);
-    if (d.mode != CMCD_MODE_ULA) {
-      pack(params + lay.g_w1, D, IN, w.w1p, tIN);     // the state rows W1[:d] only: the embedding rows are in bias1
-      pack(params + lay.g_w2, IN, IN, w.w2p, tIN);
-      pack(params + lay.g_w3, IN, D, w.w3p, tD);
-    }
-    const int64_t groups = (int64_t)tIN * kNskChunks * 64;
-    hipLaunchKernelGGL(lgcp_nsk_pack_kernel, dim3((unsigned)((groups + 255) / 256), np), dim3(256), 0, stream, pk);
-  }
-  const float* kinv = tc;
-  double* partials = reinterpret_cast<double*>(ws + w.partials);
-  *partials_out = partials;
-  // mu0 is a model constant, log(126) - 0.5 * 1.91 (model_handler.py:346); the state update reads the device copy in
-  // tc, the GEMM takes it as the operand shift
-  const float mu0 = 3.8812819069514780f;
-  const dim3 gblock(64 * kGemmWaves), gblock_step(64 * (kGemmWaves + 1));
-  const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64;
-
-  // Passes of <= kMP particles are independent chains of 3 (K + 1) latency-bound launches: up to kLanes of them run side
-  // by side, lane 0 on the caller's stream, the others on per-thread side streams forked from / joined to it by events
-  // (capturable in a graph, like the reverse sweep's two streams).  One pass (the named N = 20 batch): no side stream.
-  const int lanes = lgcp_lanes(n);
-  // side streams and events belong to ONE device: keyed by the current device (a host thread may drive several GPUs)
-  struct SideSet { hipStream_t side[kLanes]; hipEvent_t ev_join[kLanes]; hipEvent_t ev_fork; };
+// Side streams and events belong to ONE device: the calling thread's slot of the current device (a host thread may drive
+// several GPUs); nullptr when the device cannot be told.  The owners create their streams and events on first use.
+struct LgcpDevSlot {
+  struct { hipStream_t side[kLanes]; hipEvent_t ev_join[kLanes]; hipEvent_t ev_fork; } fwd;   // lgcp_forward's lanes
+  struct { hipStream_t side; hipEvent_t ev_fwd[2], ev_bwd[2], ev_fork; } sweep;               // lgcp_grad's recompute stream
+};
+static LgcpDevSlot* lgcp_dev_slot() {
   constexpr int kMaxDev = 16;
-  static thread_local SideSet sets[kMaxDev] = {};
+  static thread_local LgcpDevSlot slots[kMaxDev] = {};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return CMCD_ERR_HIP;
-  SideSet& ss = sets[dev];
-  hipStream_t* side = ss.side;
-  hipEvent_t* ev_join = ss.ev_join;
-  hipEvent_t& ev_fork = ss.ev_fork;
-  if (lanes > 1 && !ev_fork) {
-    for (int l = 1; l < kLanes; ++l) {
-      if (hipStreamCreateWithFlags(&side[l], hipStreamNonBlocking) != hipSuccess) return CMCD_ERR_HIP;
-      if (hipEventCreateWithFlags(&ev_join[l], hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
-    }
-    if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
+  return &slots[dev];
+}
+
+// one launch of the no-split-K GEMM: the MERGED instance is a run-time choice, the grid its caller's (the grid rules differ)
+template <int KIND, int ROUNDS = 1>
+static void lgcp_nsk_launch(bool merged, dim3 grid, hipStream_t st, const NskArgs& na) {
+  if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<KIND, true, ROUNDS>), grid, dim3(64 * kGemmWaves), 0, st, na);
+  else hipLaunchKernelGGL((lgcp_nsk_kernel<KIND, false, ROUNDS>), grid, dim3(64 * kGemmWaves), 0, st, na);
+}
+// ... and of the split-K GEMM on `nblk` column blocks (the state-update consumers carry the key chain's extra wave)
+template <int EPI>
+static void lgcp_gemm_launch(int nblk, hipStream_t st, const GemmArgs& g) {
+  constexpr int waves = kGemmWaves + ((EPI == EPI_STEP || EPI == EPI_STEP_NONET) ? 1 : 0);
+  hipLaunchKernelGGL(lgcp_gemm_kernel<EPI>, dim3(nblk, kSplit), dim3(64 * waves), kGemmLds, st, g);
+}
+
+// packed copies of up to four weight matrices in one launch (lgcp_nsk_pack_kernel); nch / ld = 0: the kernel's defaults
+struct NskPack {
+  NskPackArgs a{};
+  int n = 0;
+  void add(const float* src, float* dst, int K, int N, int ntile, int nch = 0, int ld = 0) {
+    a.src[n] = src; a.dst[n] = dst; a.K[n] = K; a.N[n] = N; a.ntile[n] = ntile; a.nch[n] = nch; a.ld[n] = ld; ++n;
   }
-  if (lanes > 1 && hipEventRecord(ev_fork, stream) != hipSuccess) return CMCD_ERR_HIP;   // behind the prep launch
-  // from here on the side streams are forked from the caller's stream: every exit joins them again (an un-joined fork
-  // would invalidate a graph capture and leave work of this call running behind the caller's back)
-  bool forked[kLanes] = {false, false, false, false};
-  auto join_all = [&]() {
-    bool ok = true;
-    for (int l = 1; l < lanes; ++l) {
-      if (!forked[l]) continue;
-      ok = hipEventRecord(ev_join[l], side[l]) == hipSuccess && ok;
-      ok = hipStreamWaitEvent(stream, ev_join[l], 0) == hipSuccess && ok;
-    }
-    return ok;
+  void launch(const LgcpShape& s, hipStream_t st) const {
+    const int64_t groups = (int64_t)s.tIN * s.nch * 64;
+    hipLaunchKernelGGL(lgcp_nsk_pack_kernel, dim3((unsigned)((groups + 255) / 256), n), dim3(256), 0, st, a);
+  }
+};
+
+// One evaluation of the network on the split-K GEMM: three launches, the two activations as fused consumers.
+//   L1  zin W1[:ZW] -> pre1 slabs -> u1 = [zin; emb] + softplus(pre1 + bias1)
+//   L2  u1 W2       -> pre2 slabs -> u2 = u1 + softplus(pre2 + b2)
+//   L3  u2 W3       -> sn slabs; `step`: the state update of g.step as their consumer (the forward), else none (the sweeps'
+//                      recompute, the 2nd-order forward: an element-wise kernel sums the slabs)
+// The K^-1 product (a - mu0) K^-1 -> kr slabs needs only the state, so it rides as a second segment in the launch its caller
+// names: L2 / segment 1 in the forward (the LIGHTEST launch of the three — r02: it used to double L1's grid to 408 workgroups;
+// the GEMM kernel now fits two workgroups per CU, so L2's 408 run side by side: L1 15 -> ~10 us, L2 9 -> ~11 us), L1 / segment 0
+// in the sweep's recompute, L1 / segment 1 for z' of the 2nd-order forward.  g: M, counters (and step) are the caller's.
+struct LgcpNetBufs { float *slab1, *pre1, *u1, *slab2, *pre2, *u2, *sn; };
+struct LgcpKinvRider { int launch, seg; const float* a; float* out; };    // launch 0 / 1 = L1 / L2; seg: its segment there
+static void lgcp_net_splitk(const LgcpShape& s, const cmcd_layout& lay, const float* params, const float* kinv, GemmArgs& g,
+                            const float* zin, const float* bias1_row, const float* emb_row, const LgcpNetBufs& b,
+                            const LgcpKinvRider* rider, bool step, hipStream_t st) {
+  // places the launch's own product (K extent km, nb column blocks) and the rider beside it, if it rides here -> grid width
+  // (GemmArgs: Kdim is segment 0's K extent; Kdim1 is segment 1's, with 0 meaning "the same as Kdim")
+  auto place = [&](int launch, const GemmSeg& own, int km, int nb) {
+    g.seg[0] = own; g.Kdim = km; g.Kdim1 = 0; g.nblk0 = nb; g.epi_seg = -1;
+    if (!rider || rider->launch != launch) return nb;
+    const GemmSeg kr{rider->a, kinv, rider->out, s.D, s.D, s.D, s.D, kLgcpMu0};
+    g.seg[1 - rider->seg] = own; g.seg[rider->seg] = kr;
+    if (rider->seg == 0) { g.Kdim = s.D; g.Kdim1 = km != s.D ? km : 0; g.nblk0 = s.cbD; }
+    else g.Kdim1 = s.D != km ? s.D : 0;
+    g.epi_seg = 1 - rider->seg;       // the activation is the consumer of the launch's own segment only
+    return nb + s.cbD;
   };
-  auto bail = [&]() { join_all(); return (int)CMCD_ERR_HIP; };
-
-  int* counters[kLanes];
-  for (int l = 0; l < lanes; ++l) {
-    hipStream_t st_l = l == 0 ? stream : side[l];
-    if (l > 0) {
-      if (hipStreamWaitEvent(st_l, ev_fork, 0) != hipSuccess) return bail();
-      forked[l] = true;
-    }
-    counters[l] = reinterpret_cast<int*>(ws + w.lane[l].counters);     // (cleared with the lane's first pass below)
-  }
-  const int ula = d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0);
-  const LgcpKeep keep = keep_gws ? lgcp_keep(d, n, keep_gws) : LgcpKeep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
-  // groups of `lanes` passes; inside a group the launches are enqueued evaluation by evaluation, round-robin over the
-  // lanes, so that the chains advance together (the same weights are in flight for all of them)
-  for (int64_t gbase = 0; gbase < n; gbase += (int64_t)lanes * kMP) {
-    GemmArgs g[kLanes];
-    int M[kLanes], live = 0;
-    for (int l = 0; l < lanes; ++l) {
-      const int64_t base = gbase + (int64_t)l * kMP;
-      if (base >= n) break;
-      ++live;
-      hipStream_t st_l = l == 0 ? stream : side[l];
-      const LgcpLane& wl = w.lane[l];
-      M[l] = (int)((n - base) < kMP ? (n - base) : kMP);
-      // packed operands: the padding (rows >= M, inputs >= IN) must read as zeros; slots start at zero; the lane's arrival
-      // counters once per call (every lane is live in the first group).  One launch on the lane's stream (lgcp_zero_kernel).
-      if (lgcp_zero(st_l, ws + wl.slots, 3 * (int64_t)cbD * kMP,
-                    nsk ? ws + wl.nsk : nullptr, nsk ? kNskOps * kNskOperand + 3 * (int64_t)tD * kMP : 0,
-                    gbase == 0 ? counters[l] : nullptr, gbase == 0 ? cbD + cbIN : 0) != CMCD_OK)
-        return bail();
-      LgcpStateArgs st{};
-      st.seeds = seeds + base; st.params = params; st.tc = tc; st.x = nsk ? ws + wl.nsk : ws + wl.x; st.packed = nsk ? 1 : 0;
-      st.w = ws + wl.w; st.keys = reinterpret_cast<uint32_t*>(ws + wl.keys);
-      st.gkey = reinterpret_cast<uint32_t*>(ws + wl.gkey); st.gktab = reinterpret_cast<uint32_t*>(ws + w.gktab);
-      st.lay = lay; st.M = M[l]; st.D = D;
-      st.traj = traj; st.n_total = n; st.base = base;
-      hipLaunchKernelGGL(lgcp_init_kernel, dim3(M[l]), dim3(256), 0, st_l, st);
-
-      g[l] = GemmArgs{};
-      g[l].M = M[l]; g[l].counters = counters[l];
-      g[l].act.x = ws + wl.x; g[l].act.D = D; g[l].act.IN = IN;
-      StepEpi& se = g[l].step;
-      se.params = params; se.tc = tc; se.sched = ws + sw.sched; se.x = ws + wl.x; se.xp = ws + wl.xp;
-      se.kr = ws + wl.kr; se.b3 = params + lay.g_b3; se.factor = params + lay.g_factor;
-      se.gen = reinterpret_cast<uint32_t*>(ws + wl.keys); se.gkey = reinterpret_cast<uint32_t*>(ws + wl.gkey);
-      se.gktab = reinterpret_cast<uint32_t*>(ws + w.gktab);
-      se.wslot = ws + wl.slots; se.fkslot = se.wslot + cbD * kMP; se.lpslot = se.fkslot + cbD * kMP;
-      if (nsk) {   // one slot row per 16-column tile
-        se.wslot = ws + wl.nsk + kNskOps * kNskOperand; se.fkslot = se.wslot + tD * kMP; se.lpslot = se.fkslot + tD * kMP;
-      }
-      se.out_z = out_z + base * D; se.traj = traj; se.n_total = n; se.base = base; se.lay = lay;
-      se.D = D; se.K = K; se.var_mode = d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0; se.grad_clipping = d.grad_clipping;
-      se.ula = ula;
-    }
-    for (int i = 0; i <= K; ++i) {
-      // CAIS: s(z_i, i) serves both kernels; MCD_ULA_sn: s(z_i, i - 1) serves the backward kernel only
-      const int it = ula == 2 ? (i > 0 ? i - 1 : 0) : i;
-      const int ie = it < K ? it : K - 1;
-      for (int l = 0; l < live; ++l) {
-        hipStream_t st_l = l == 0 ? stream : side[l];
-        const LgcpLane& wl = w.lane[l];
-        GemmArgs& gl = g[l];
-        gl.step.i = i;
-        if (nsk) {
-          // evaluation i reads z_i from buffer i % 3, z_{i-1} from (i + 2) % 3 and writes z_{i+1} into (i + 1) % 3
-          float* const sb = ws + wl.nsk;
-          float* const xA = sb + (i % 3) * kNskOperand;
-          float* const u1A = sb + 3 * kNskOperand, *u2A = u1A + kNskOperand, *krA = u2A + kNskOperand;
-          NskArgs na{};
-          na.M = M[l]; na.D = D; na.IN = IN; na.xA = xA; na.xpA = sb + ((i + 2) % 3) * kNskOperand;
-          na.xnA = sb + ((i + 1) % 3) * kNskOperand; na.krA = krA; na.krOut = krA; na.step = gl.step;
-          // 17 .. 20 particles (the named batch): one workgroup per column tile serves both row blocks (16x16x4 + 4x4x1);
-          // otherwise one workgroup per (tile, 16-row half).  State-update launches carry one extra workgroup (key chain).
-          // Measured at N = 20 (profiles/r04_f_lgcp_nsk_per_launch_n20.txt): merged helps the launch that is otherwise two
-          // workgroups per CU (B: 9.96 -> 7.44 us) and costs the two that are one per CU either way (A 6.48 -> 7.08, C 7.64 ->
-          // 8.40: half as many CUs pull the bytes), so only launch B takes it.
-          const bool can_merge = M[l] > 16 && M[l] <= 20;
-          auto launch = [&](bool step, int tiles, bool want_merged = false) {
-            const bool merged = can_merge && want_merged;
-            const unsigned gy = (!merged && M[l] > 16) ? 2 : 1;
-            dim3 grid((unsigned)tiles + (step ? 1 : 0), gy);
-            na.pair_gx = 0;
-            if (gy == 2 && lgcp_xcd_pairs()) {   // both row halves of a column tile on one XCD (NskArgs::pair_gx)
-              na.pair_gx = (int)grid.x;
-              grid = dim3(16u * ((grid.x + 7) / 8), 1);
-            }
-            if (step) {
-              if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<1, true>), grid, gblock, 0, st_l, na);
-              else hipLaunchKernelGGL((lgcp_nsk_kernel<1, false>), grid, gblock, 0, st_l, na);
-            } else {
-              if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<0, true>), grid, gblock, 0, st_l, na);
-              else hipLaunchKernelGGL((lgcp_nsk_kernel<0, false>), grid, gblock, 0, st_l, na);
-            }
-          };
-          // (gradient calls: this evaluation's rows of the kept tables)
-          const int64_t krow = (int64_t)i * n + gbase + (int64_t)l * kMP;
-          if (ula == 1) {   // MCD_ULA: one launch per evaluation, (x - mu0) K^-1 with the state update as its consumer
-            na.seg[0] = NskSeg{xA, ws + w.kip, D, NSK_STEP_NONET, mu0}; na.nt0 = tD;
-            if (keep.on) na.keepKr = keep.kr + krow * D;
-            launch(true, tD);
-            continue;
-          }
-          // A: x W1[:D] -> u1 = [x; emb_i] + softplus(. + bias1_i)
-          na.seg[0] = NskSeg{xA, ws + w.w1p, IN, NSK_ACT1, 0.f}; na.nt0 = tIN;
-          na.bias = ws + w.bias1 + (int64_t)it * IN; na.emb = params + lay.g_emb + (int64_t)ie * E; na.outA = u1A;
-          if (keep.on) { na.keepPre = keep.pre1 + krow * IN; na.keepU = keep.u1 + krow * IN; }
-          launch(false, tIN);
-          // B: u1 W2 -> u2 = u1 + softplus(. + b2)   |   (x - mu0) K^-1 -> kr
-          na.seg[0] = NskSeg{u1A, ws + w.w2p, IN, NSK_ACT2, 0.f};
-          na.seg[1] = NskSeg{xA, ws + w.kip, D, NSK_KR, mu0};
-          na.bias = params + lay.g_b2; na.uA = u1A; na.outA = u2A;
-          if (keep.on) { na.keepPre = keep.pre2 + krow * IN; na.keepU = keep.u2 + krow * IN; na.keepKr = keep.kr + krow * D; }
-          launch(false, tIN + tD, true);
-          // C: u2 W3 -> the state update of evaluation i on the tile's elements
-          na.seg[0] = NskSeg{u2A, ws + w.w3p, D, NSK_STEP, 0.f}; na.nt0 = tD;
-          na.keepPre = nullptr; na.keepU = nullptr; na.keepKr = nullptr;
-          if (keep.on) na.keepSn = keep.sn + krow * D;
-          launch(true, tD);
-          continue;
-        }
-        if (ula == 1) {   // MCD_ULA: one launch per evaluation, [x - mu0] Kinv with the state update as its consumer
-          // the state is this launch's operand: z_i / z_{i-1} / z_{i+1} rotate through x, xp and the (unused: no network)
-          // u1 buffer instead of an in-place update that a slower workgroup of another column block could still be loading
-          float* const sb3[3] = {ws + wl.x, ws + wl.xp, ws + wl.u1};
-          gl.step.x = sb3[i % 3]; gl.step.xp = sb3[(i + 2) % 3]; gl.step.xn = sb3[(i + 1) % 3];
-          gl.Kdim = D; gl.Kdim1 = 0;
-          gl.seg[0] = GemmSeg{gl.step.x, kinv, ws + wl.kr, D, D, D, D, mu0};
-          gl.nblk0 = cbD; gl.epi_seg = -1;
-          hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_STEP_NONET>, dim3(cbD, kSplit), gblock_step, gemm_lds, st_l, gl);
-          continue;
-        }
-        // A: x W1[:D] -> pre1 slabs -> u1 = [x; emb_i] + softplus(pre1 + bias1_i)            (fused consumer)
-        gl.Kdim = D; gl.Kdim1 = 0;
-        gl.seg[0] = GemmSeg{ws + wl.x, params + lay.g_w1, ws + wl.slab1, IN, D, IN, IN};
-        gl.nblk0 = cbIN; gl.epi_seg = -1;
-        gl.act.mode = 1; gl.act.bias = ws + w.bias1 + (int64_t)it * IN; gl.act.emb = params + lay.g_emb + (int64_t)ie * E;
-        gl.act.sum_out = ws + wl.pre1; gl.act.u_prev = nullptr; gl.act.u_out = ws + wl.u1;
-        hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACT>, dim3(cbIN, kSplit), gblock, gemm_lds, st_l, gl);
-        // B: u1 W2 -> pre2 slabs -> u2 = u1 + softplus(pre2 + b2)                             (fused consumer)
-        //    [x - mu0] Kinv -> kr slabs (summed by the state update in launch C): this product needs only the state, so
-        //    it rides in the LIGHTEST launch of the three (r02: it used to double launch A's grid to 408 workgroups; the
-        //    GEMM kernel now fits two workgroups per CU, so B's 408 run side by side: A 15 -> ~10 us, B 9 -> ~11 us)
-        gl.Kdim = IN; gl.Kdim1 = D;
-        gl.seg[0] = GemmSeg{ws + wl.u1, params + lay.g_w2, ws + wl.slab2, IN, IN, IN, IN};
-        gl.seg[1] = GemmSeg{ws + wl.x, kinv, ws + wl.kr, D, D, D, D, mu0};
-        gl.nblk0 = cbIN; gl.epi_seg = 0;
-        gl.act.mode = 2; gl.act.bias = params + lay.g_b2; gl.act.sum_out = ws + wl.pre2; gl.act.u_prev = ws + wl.u1;
-        gl.act.u_out = ws + wl.u2;
-        hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACT>, dim3(cbIN + cbD, kSplit), gblock, gemm_lds, st_l, gl);
-        gl.Kdim1 = 0;
-        // C: u2 W3 -> sn slabs -> state update of evaluation i on the block's columns
-        gl.seg[0] = GemmSeg{ws + wl.u2, params + lay.g_w3, ws + wl.sn, D, IN, D, D};
-        gl.nblk0 = cbD;
-        hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_STEP>, dim3(cbD, kSplit), gblock_step, gemm_lds, st_l, gl);
-      }
-    }
-    for (int l = 0; l < live; ++l) {
-      hipStream_t st_l = l == 0 ? stream : side[l];
-      const int64_t base = gbase + (int64_t)l * kMP;
-      const StepEpi& se = g[l].step;
-      LgcpFinalArgs fa{ws + w.lane[l].w, se.wslot, se.lpslot, tc, out_loss + base, partials + base * CMCD_NSTATS, M[l], D,
-                       nsk ? tD : cbD};
-      hipLaunchKernelGGL(lgcp_final_kernel, dim3(M[l]), dim3(64), 0, st_l, fa);
-    }
-  }
-  if (!join_all()) return CMCD_ERR_HIP;
-  return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
+  g.act.x = zin; g.act.D = s.ZW; g.act.IN = s.IN;
+  int nblk = place(0, GemmSeg{zin, params + lay.g_w1, b.slab1, s.IN, s.ZW, s.IN, s.IN}, s.ZW, s.cbIN);
+  g.act.mode = 1; g.act.bias = bias1_row; g.act.emb = emb_row; g.act.sum_out = b.pre1; g.act.u_prev = nullptr; g.act.u_out = b.u1;
+  lgcp_gemm_launch<EPI_ACT>(nblk, st, g);
+  nblk = place(1, GemmSeg{b.u1, params + lay.g_w2, b.slab2, s.IN, s.IN, s.IN, s.IN}, s.IN, s.cbIN);
+  g.act.mode = 2; g.act.bias = params + lay.g_b2; g.act.sum_out = b.pre2; g.act.u_prev = b.u1; g.act.u_out = b.u2;
+  lgcp_gemm_launch<EPI_ACT>(nblk, st, g);
+  nblk = place(2, GemmSeg{b.u2, params + lay.g_w3, b.sn, s.D, s.IN, s.D, s.D}, s.IN, s.cbD);
+  if (step) { g.epi_seg = 0; lgcp_gemm_launch<EPI_STEP>(nblk, st, g); }     // (the state update belongs to segment 0, the only one)
+  else lgcp_gemm_launch<EPI_NONE>(nblk, st, g);
 }
 
 
@@ -1774,33 +1775,31 @@ __global__ __launch_bounds__(256) void lgcp_mfvi_finish_kernel(LgcpMfviArgs a) {
   }
 }
 
-int64_t lgcp_mfvi_workspace_floats(int D, int64_t n, bool with_grad) {
-  int64_t o = 0;
-  auto take = [&](int64_t cnt) { o += (cnt + 3) & ~int64_t(3); };
-  take(kMP * (int64_t)D); take(kSplit * kMP * (int64_t)D);
-  take(kMP); take(2 * kMP);
-  take(n * CMCD_NSTATS * 2);
-  if (with_grad) take(n * 2 * (int64_t)D);
-  return o;
+struct LgcpMfviWs { int64_t x, kr, w, keys, partials, gb, total; };
+static LgcpMfviWs lgcp_mfvi_ws(int64_t D, int64_t n, bool with_grad) {
+  LgcpMfviWs w;
+  WsBump b{0};
+  w.x = b.take(kMP * D); w.kr = b.take(kSplit * kMP * D);
+  w.w = b.take(kMP); w.keys = b.take(2 * kMP);
+  w.partials = b.take(n * CMCD_NSTATS * 2);
+  w.gb = with_grad ? b.take(n * 2 * D) : 0;
+  w.total = b.o;
+  return w;
 }
+
+int64_t lgcp_mfvi_workspace_floats(int D, int64_t n, bool with_grad) { return lgcp_mfvi_ws(D, n, with_grad).total; }
 
 int lgcp_mfvi(int D, int64_t o_mean, int64_t o_logdiag, const int32_t* seeds, int64_t n, const float* params,
               const float* tc, float* ws, float* out_loss, float* out_z, double** partials_out, float** gbuf_out,
               bool with_grad, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int64_t o = 0;
-  auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; };
-  const int64_t ox = take(kMP * (int64_t)D), okr = take(kSplit * kMP * (int64_t)D);
-  const int64_t ow = take(kMP), okeys = take(2 * kMP);
-  const int64_t opart = take(n * CMCD_NSTATS * 2);
-  const int64_t ogb = with_grad ? take(n * 2 * (int64_t)D) : 0;
-  double* partials = reinterpret_cast<double*>(ws + opart);
-  float* gbuf = with_grad ? ws + ogb : nullptr;
+  const LgcpMfviWs w = lgcp_mfvi_ws(D, n, with_grad);
+  const int64_t ox = w.x, okr = w.kr, ow = w.w, okeys = w.keys;
+  double* partials = reinterpret_cast<double*>(ws + w.partials);
+  float* gbuf = with_grad ? ws + w.gb : nullptr;
   *partials_out = partials;
   *gbuf_out = gbuf;
-  const int gemm_lds = lgcp_gemm_attrs();
-  if (gemm_lds < 0) return CMCD_ERR_HIP;
-  const float mu0 = 3.8812819069514780f;
+  if (!lgcp_gemm_attrs()) return CMCD_ERR_HIP;
   const int cbD = (D + 63) / 64;
   cmcd_layout lay{};
   lay.vd_mean = o_mean; lay.vd_logdiag = o_logdiag;
@@ -1813,9 +1812,9 @@ int lgcp_mfvi(int D, int64_t o_mean, int64_t o_logdiag, const int32_t* seeds, in
     hipLaunchKernelGGL(lgcp_init_kernel, dim3(M), dim3(256), 0, stream, st);
     GemmArgs g{};
     g.M = M; g.Kdim = D;
-    g.seg[0] = GemmSeg{ws + ox, tc, ws + okr, D, D, D, D, mu0};
+    g.seg[0] = GemmSeg{ws + ox, tc, ws + okr, D, D, D, D, kLgcpMu0};
     g.nblk0 = cbD;
-    hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), dim3(64 * kGemmWaves), gemm_lds, stream, g);
+    lgcp_gemm_launch<EPI_NONE>(cbD, stream, g);
     LgcpMfviArgs fa{params, tc, ws + ox, ws + okr, ws + ow, out_loss + base, out_z + base * D,
                     partials + base * CMCD_NSTATS, gbuf ? gbuf + base * 2 * D : nullptr, o_mean, D};
     hipLaunchKernelGGL(lgcp_mfvi_finish_kernel, dim3(M), dim3(256), 0, stream, fa);
@@ -1976,366 +1975,99 @@ __global__ void lgcp_colsum_kernel(const float* __restrict__ A, int64_t R, int C
   out[j] = accumulate ? out[j] + v : v;
 }
 
-// buffers of one forward recompute (two sets: evaluation e-1 is recomputed on a side stream while the backward
-// pass of evaluation e reads the other set)
-struct LgcpFwdSet {
-  int64_t kr, slab1, pre1, u1, slab2, pre2, u2, sn;
-};
-
-struct LgcpGradWs {
-  int64_t wt1, wt2, wt3;                       // transposed weights
-  int64_t lamn, lam_part, gE, gprev, dO, v;    // [kMP][D]
-  int64_t hv, dxf;                             // [kSplit][kMP][D]
-  int64_t du2s, ts;                            // [kSplit][kMP][IN] slabs of the two IN-wide backward GEMMs
-  int64_t du2, du1, da2, da1;                  // [kMP][IN]
-  int64_t gmu_acc, glam_acc;                   // [kMP][D]
-  int64_t U1, U2, DA1, DA2;                    // [(K+1) n][IN]
-  int64_t kpre1, kpre2, kkr, ksn;              // [(K+1) n][IN] x 2, [(K+1) n][D] x 2: kept by the forward (lgcp_keep); 0 floats when off
-  bool keep;
-  int64_t bops, wt3p, wt2p, wt1p;              // keep: packed dO | v | da2 | da1 operands and packed W3^T, W2^T, W1[:D]^T
-  int64_t DO;                                  // [(K+1) n][D]
-  int64_t S, S2, gbeta, geps, gfac, gb2;       // tables (gfac: [K+1] per-evaluation terms)
-  int64_t adjpart, gb_lo, ge_lo, gb_hi, ge_hi; // adjoint step partial sums; the four [K+1] slots are unused since the reduction
-                                               // forms gbeta / geps itself (kept: the workspace layout is unchanged)
-  int64_t counters;                            // arrival counters of the side stream's fused GEMMs (ints)
-  int64_t zero_lo, zero_hi;                    // range to clear per call
-  LgcpFwdSet fs[2];
-  int64_t total;
-};
-
-static LgcpGradWs lgcp_grad_ws(const cmcd_desc& d, int64_t n) {
-  const int64_t D = d.dim, IN = D + d.emb_dim, K = d.nbridges, R = (K + 1) * n;
-  LgcpGradWs w;
-  int64_t o = 0;
-  auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; };
-  w.wt1 = take(IN * IN); w.wt2 = take(IN * IN); w.wt3 = take(D * IN);
-  w.dO = take(kMP * D); w.v = take(kMP * D); w.lam_part = take(kMP * D); w.gprev = take(kMP * D);
-  w.hv = take(kSplit * kMP * D); w.dxf = take(kSplit * kMP * D);
-  w.du2s = take(kSplit * kMP * IN); w.ts = take(kSplit * kMP * IN);
-  w.du2 = take(kMP * IN); w.du1 = take(kMP * IN); w.da2 = take(kMP * IN); w.da1 = take(kMP * IN);
-  w.U1 = take(R * IN); w.U2 = take(R * IN); w.DA1 = take(R * IN); w.DA2 = take(R * IN); w.DO = take(R * D);
-  for (int b = 0; b < 2; ++b) {
-    LgcpFwdSet& f = w.fs[b];
-    f.kr = take(kSplit * kMP * D); f.slab1 = take(kSplit * kMP * IN); f.pre1 = take(kMP * IN);
-    f.u1 = take(kMP * IN); f.slab2 = take(kSplit * kMP * IN); f.pre2 = take(kMP * IN); f.u2 = take(kMP * IN);
-    f.sn = take(kSplit * kMP * D);
-  }
-  w.zero_lo = o;
-  w.lamn = take(kMP * D); w.gE = take(kMP * D);
-  w.gmu_acc = take(kMP * D); w.glam_acc = take(kMP * D);
-  w.S = take((K + 1) * IN); w.S2 = take((K + 1) * IN);
-  w.gbeta = take(K); w.geps = take(K); w.gfac = take(K + 1); w.gb2 = take(IN);
-  w.counters = take(2 * ((D + 63) / 64 + (IN + 63) / 64));     // side stream's set | caller's stream's set
-  w.zero_hi = o;
-  w.adjpart = take((K + 1) * n * ((D + 63) / 64) * 8);
-  w.gb_lo = take(K + 1); w.ge_lo = take(K + 1); w.gb_hi = take(K + 1); w.ge_hi = take(K + 1);
-  // the forward's kept activations (behind everything else: the layout above does not move when they are off)
-  w.keep = lgcp_nsk_ok(d) && d.mode != CMCD_MODE_CAIS_UHA_SN && R * (2 * IN + 2 * D) <= (int64_t(1) << 28);
-  w.kpre1 = take(w.keep ? R * IN : 0); w.kpre2 = take(w.keep ? R * IN : 0);
-  w.kkr = take(w.keep ? R * D : 0); w.ksn = take(w.keep ? R * D : 0);
-  {
-    const int64_t tIN = (IN + 15) / 16, tD = D / 16;
-    w.bops = take(w.keep ? 4 * kNskOperand : 0);
-    w.wt3p = take(w.keep ? tIN * kNskChunks * 256 : 0); w.wt2p = take(w.keep ? tIN * kNskChunks * 256 : 0);
-    w.wt1p = take(w.keep ? tD * kNskChunks * 256 : 0);
-  }
-  w.total = o;
-  return w;
+// ------------------------------------------------------------------------------------------
+// what the two reverse sweeps (lgcp_grad, lgcp_uha_grad) share on the host
+// ------------------------------------------------------------------------------------------
+// transposed weight copies: the backward GEMMs are then the forward kernel on W^T.  w1_rows: the rows of W1 that are transposed
+// (all IN in lgcp_grad, the ZW state rows in lgcp_uha_grad)
+static void lgcp_transpose_weights(const LgcpShape& s, const cmcd_layout& lay, const float* params, const LgcpSweepWs& g, float* gws,
+                                   int w1_rows, hipStream_t stream) {
+  const dim3 tb(32, 8);
+  const int IN = s.IN, D = s.D;
+  hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (w1_rows + 31) / 32), tb, 0, stream, params + lay.g_w1,
+                     gws + g.wt1, w1_rows, IN, IN, w1_rows);
+  hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w2,
+                     gws + g.wt2, IN, IN, IN, IN);
+  hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((D + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w3,
+                     gws + g.wt3, IN, D, D, IN);
 }
 
-static LgcpKeep lgcp_keep(const cmcd_desc& d, int64_t n, float* gws) {
-  const LgcpGradWs g = lgcp_grad_ws(d, n);
-  if (!g.keep) return LgcpKeep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
-  return LgcpKeep{gws + g.kpre1, gws + g.U1, gws + g.kpre2, gws + g.U2, gws + g.kkr, gws + g.ksn, true};
-}
-
-static int64_t lgcp_uha_grad_ws_total(const cmcd_desc& d, int64_t n);
-static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, int64_t n, const float* params,
-                         int64_t n_params, const float* tc, float* ws, const float* traj, float* gws, float omega,
-                         float* grad, hipStream_t stream);
-
-int64_t lgcp_grad_workspace_floats(const cmcd_desc& d, int64_t n) {
-  if (d.mode == CMCD_MODE_CAIS_UHA_SN) return lgcp_uha_grad_ws_total(d, n);
-  return lgcp_grad_ws(d, n).total;
-}
-
-int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, int64_t n, const float* params,
-              int64_t n_params, const float* tc, float* ws, const float* traj, float* gws, float omega,
-              const float* omega_vec, bool bptt, float* grad, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (d.mode == CMCD_MODE_CAIS_UHA_SN) {
-    if (!bptt || omega_vec) return CMCD_ERR_UNSUPPORTED;   // the mode has no stop_gradient variant
-    return lgcp_uha_grad(d, lay, sw, n, params, n_params, tc, ws, traj, gws, omega, grad, stream);
-  }
-  const int D = d.dim, E = d.emb_dim, IN = D + E, K = d.nbridges;
-  const LgcpWs w = lgcp_ws(d, n, sw.total_floats);
-  const LgcpGradWs g = lgcp_grad_ws(d, n);
-  if (lgcp_zero(stream, grad, n_params, gws + g.zero_lo, g.zero_hi - g.zero_lo) != CMCD_OK) return CMCD_ERR_HIP;
-  const int ula = d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0);
-  const bool net = ula != 1;
-  // transposed weight copies: the backward GEMMs are then the forward kernel on W^T
-  if (net) {
-    const dim3 tb(32, 8);
-    hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w1,
-                       gws + g.wt1, IN, IN, IN, IN);
-    hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w2,
-                       gws + g.wt2, IN, IN, IN, IN);
-    hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((D + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w3,
-                       gws + g.wt3, IN, D, D, IN);
-  }
-  const int gemm_lds = lgcp_gemm_attrs();
-  if (gemm_lds < 0) return CMCD_ERR_HIP;
-  const float* kinv = tc;
-  const float mu0 = 3.8812819069514780f;
-  const dim3 gblock(64 * kGemmWaves);
-  const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64;
-  // r04: with the activations kept, passes of <= 20 particles run the three backward products on the no-split-K GEMM too
-  // (lgcp_nsk_kernel<3, ..>: the backward activation as the consumer, column sums by the tile's one workgroup); the packed
-  // W3^T / W2^T / W1[:D]^T copies are made once per call, K^-1 is the forward's packed copy
-  const int tIN = (IN + 15) / 16, tD = D / 16;
-  const bool nskb_ok = g.keep && net;
-  if (nskb_ok) {
-    NskPackArgs pk{};
-    pk.src[0] = gws + g.wt3; pk.dst[0] = gws + g.wt3p; pk.K[0] = D; pk.N[0] = IN; pk.ntile[0] = tIN;
-    pk.src[1] = gws + g.wt2; pk.dst[1] = gws + g.wt2p; pk.K[1] = IN; pk.N[1] = IN; pk.ntile[1] = tIN;
-    pk.src[2] = gws + g.wt1; pk.dst[2] = gws + g.wt1p; pk.K[2] = IN; pk.N[2] = D; pk.ntile[2] = tD; pk.ld[2] = IN;   // first D columns of W1^T
-    const int64_t groups = (int64_t)tIN * kNskChunks * 64;
-    hipLaunchKernelGGL(lgcp_nsk_pack_kernel, dim3((unsigned)((groups + 255) / 256), 3), dim3(256), 0, stream, pk);
-  }
-  // Two streams: the forward recompute of evaluation e-1 (side stream, its own buffer set) overlaps the adjoint /
-  // backward launches of evaluation e (caller's stream).  Every kernel here is launch-latency-bound, so the two
-  // chains run side by side; events order the hand-overs (fork / join, capturable in a graph).
-  struct GradSide { hipStream_t side; hipEvent_t ev_fwd[2], ev_bwd[2], ev_fork; };
-  constexpr int kMaxDev = 16;
-  static thread_local GradSide gsets[kMaxDev] = {};   // keyed by device, like the forward's side streams
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return CMCD_ERR_HIP;
-  hipStream_t& side = gsets[dev].side;
-  hipEvent_t* ev_fwd = gsets[dev].ev_fwd;
-  hipEvent_t* ev_bwd = gsets[dev].ev_bwd;
-  hipEvent_t& ev_fork = gsets[dev].ev_fork;
-  if (!side) {
-    if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) return CMCD_ERR_HIP;
-    for (int b = 0; b < 2; ++b) {
-      if (hipEventCreateWithFlags(&ev_fwd[b], hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
-      if (hipEventCreateWithFlags(&ev_bwd[b], hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
-    }
-    if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
-  }
-  // r04: the forward kept pre1 / u1 / pre2 / u2 / kr / sn of every evaluation (lgcp_keep): nothing to recompute, one stream
-  const LgcpKeep keep = lgcp_keep(d, n, gws);
-  const bool kept = keep.on;
-  // bias1 rows are still in the forward workspace (lgcp_forward's prep)
-  for (int64_t base = 0; base < n; base += kMP) {
-    const int M = (int)((n - base) < kMP ? (n - base) : kMP);
-    const bool nskb = nskb_ok && kept && M <= 20;      // (21 .. 32 particles: two workgroups per column tile — the split-K form)
-    float* const dOp = gws + g.bops, *vp = dOp + kNskOperand, *da2p = vp + kNskOperand, *da1p = da2p + kNskOperand;
-    {
-      // lambda / g (lamn | gE) and the accumulators (gmu_acc | glam_acc) start from zero for every pass (the first one's by the
-      // call's clear above); the padding of the packed operands (rows >= M, inputs past the contraction) must read as zeros
-      const int64_t pair = base > 0 ? 2 * ((kMP * (int64_t)D + 3) & ~int64_t(3)) : 0;
-      if (lgcp_zero(stream, gws + g.lamn, pair, gws + g.gmu_acc, pair, nskb ? dOp : nullptr, nskb ? 4 * (int64_t)kNskOperand : 0) != CMCD_OK)
-        return CMCD_ERR_HIP;
-    }
-    if (!kept && (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess)) return CMCD_ERR_HIP;
-
-    // forward recompute at z_e into buffer set e & 1, on stream st: the forward path's three launches (activations
-    // fused into the GEMMs; the third has no consumer here: the adjoint step sums its slabs)
-    int* side_counters = reinterpret_cast<int*>(gws + g.counters);
-    int* main_counters = side_counters + cbD + cbIN;
-    auto forward_at = [&](int e, hipStream_t st) {
-      const LgcpFwdSet& f = g.fs[e & 1];
-      const int er = ula == 2 ? (e > 0 ? e - 1 : 0) : e;       // MCD_ULA_sn: s(z_e, e - 1)
-      const int ie = er < K ? er : K - 1;
-      const float* xe = traj + ((int64_t)e * n + base) * D;
-      GemmArgs gm{};
-      gm.M = M; gm.counters = side_counters;
-      gm.act.x = xe; gm.act.D = D; gm.act.IN = IN;
-      gm.Kdim = D;
-      gm.seg[0] = GemmSeg{xe, kinv, gws + f.kr, D, D, D, D, mu0};
-      if (!net) {   // MCD_ULA: the target's K^-1 product is all there is to recompute
-        gm.nblk0 = cbD;
-        hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), gblock, gemm_lds, st, gm);
-        return;
-      }
-      gm.seg[1] = GemmSeg{xe, params + lay.g_w1, gws + f.slab1, IN, D, IN, IN};
-      gm.nblk0 = cbD; gm.epi_seg = 1;
-      gm.act.mode = 1; gm.act.bias = ws + w.bias1 + (int64_t)er * IN; gm.act.emb = params + lay.g_emb + (int64_t)ie * E;
-      gm.act.sum_out = gws + f.pre1; gm.act.u_prev = nullptr; gm.act.u_out = gws + f.u1;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACT>, dim3(cbD + cbIN, kSplit), gblock, gemm_lds, st, gm);
-      gm.Kdim = IN;
-      gm.seg[0] = GemmSeg{gws + f.u1, params + lay.g_w2, gws + f.slab2, IN, IN, IN, IN};
-      gm.nblk0 = cbIN; gm.epi_seg = -1;
-      gm.act.mode = 2; gm.act.bias = params + lay.g_b2; gm.act.sum_out = gws + f.pre2; gm.act.u_prev = gws + f.u1;
-      gm.act.u_out = gws + f.u2;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACT>, dim3(cbIN, kSplit), gblock, gemm_lds, st, gm);
-      gm.seg[0] = GemmSeg{gws + f.u2, params + lay.g_w3, gws + f.sn, D, IN, D, D};
-      gm.nblk0 = cbD;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), gblock, gemm_lds, st, gm);
-    };
-
-    if (!kept) {
-      forward_at(K, side);
-      if (hipEventRecord(ev_fwd[K & 1], side) != hipSuccess) return CMCD_ERR_HIP;
-    }
-    for (int e = K; e >= 0; --e) {
-      if (!kept) {
-        if (e > 0) {  // next evaluation's recompute: its buffer set was last read by the backward pass of e+1
-          if (e + 1 <= K && hipStreamWaitEvent(side, ev_bwd[(e - 1) & 1], 0) != hipSuccess) return CMCD_ERR_HIP;
-          forward_at(e - 1, side);
-          if (hipEventRecord(ev_fwd[(e - 1) & 1], side) != hipSuccess) return CMCD_ERR_HIP;
-        }
-        if (hipStreamWaitEvent(stream, ev_fwd[e & 1], 0) != hipSuccess) return CMCD_ERR_HIP;
-      }
-      const LgcpFwdSet& f = g.fs[e & 1];
-      const int64_t row0 = (int64_t)e * n + base;
-      // this evaluation's activations: the recompute's buffer set, or its rows of the tables the forward kept
-      const float* e_kr = kept ? keep.kr + row0 * D : gws + f.kr;
-      const float* e_sn = kept ? keep.sn + row0 * D : gws + f.sn;
-      const float* e_pre1 = kept ? keep.pre1 + row0 * IN : gws + f.pre1;
-      const float* e_pre2 = kept ? keep.pre2 + row0 * IN : gws + f.pre2;
-      const float* e_u1 = kept ? keep.u1 + row0 * IN : gws + f.u1;
-      const float* e_u2 = kept ? keep.u2 + row0 * IN : gws + f.u2;
-      GemmArgs gm{};
-      gm.M = M;
-      // ---- adjoint step (of evaluation ev: its kr / sn are the recompute's buffers, or rows of the kept tables)
-      auto adj_args = [&](int ev) {
-        const int64_t rv = (int64_t)ev * n + base;
-        LgcpAdjArgs aa{};
-        aa.params = params; aa.tc = tc; aa.sched = ws + sw.sched; aa.traj = traj;
-        aa.kr = kept ? keep.kr + rv * D : e_kr; aa.sn = kept ? keep.sn + rv * D : e_sn;
-        aa.nslab = kept ? 1 : kSplit;
-        aa.b3 = params + lay.g_b3; aa.factor = params + lay.g_factor; aa.lamn = gws + g.lamn; aa.gE = gws + g.gE;
-        aa.gprev = gws + g.gprev; aa.dO = gws + g.dO; aa.v = gws + g.v; aa.lam_part = gws + g.lam_part;
-        aa.gmu_acc = gws + g.gmu_acc; aa.glam_acc = gws + g.glam_acc; aa.part = gws + g.adjpart;
-        aa.DObig = gws + g.DO; aa.lay = lay; aa.n = n; aa.base = base;
-        aa.M = M; aa.D = D; aa.K = K; aa.e = ev; aa.grad_clipping = d.grad_clipping; aa.omega = omega;
-        aa.ula = ula; aa.omega_vec = omega_vec; aa.bptt = bptt ? 1 : 0; aa.var_mode = d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0;
-        if (nskb) { aa.dOp = dOp; aa.vp = vp; }
-        return aa;
-      };
-      // kept + reparameterised: the step of evaluation e was fused behind lambda_{e+1} by the previous iteration
-      const bool fuse = kept && bptt;
-      if (!(fuse && e < K)) hipLaunchKernelGGL(lgcp_adj_step_kernel, dim3(cbD, M), dim3(64), 0, stream, adj_args(e));
-      if (!net) {   // MCD_ULA: lambda_e = lam_part - H_p v, one GEMM
-        gm.Kdim = D; gm.Kdim1 = 0;
-        gm.seg[0] = GemmSeg{gws + g.v, kinv, gws + g.hv, D, D, D, D};
-        gm.nblk0 = cbD;
-        hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), gblock, gemm_lds, stream, gm);
-        LgcpLamArgs la{};
-        la.params = params; la.tc = tc; la.traj = traj; la.dxf = nullptr; la.hv = gws + g.hv; la.du1 = nullptr;
-        la.v = gws + g.v; la.lam_part = gws + g.lam_part; la.gprev = gws + g.gprev; la.lamn = gws + g.lamn;
-        la.gE = gws + g.gE; la.gmu_acc = gws + g.gmu_acc; la.glam_acc = gws + g.glam_acc; la.lay = lay; la.n = n;
-        la.base = base; la.M = M; la.D = D; la.IN = IN; la.e = e; la.omega = omega; la.no_net = 1;
-        if (fuse && e > 0) hipLaunchKernelGGL(lgcp_lam_adj_kernel, dim3(cbD, M), dim3(64), 0, stream, la, adj_args(e - 1));
-        else hipLaunchKernelGGL(lgcp_lam_finish_kernel, dim3((M * D + 255) / 256), dim3(256), 0, stream, la);
-        if (!kept && hipEventRecord(ev_bwd[e & 1], stream) != hipSuccess) return CMCD_ERR_HIP;
-        continue;
-      }
-      const int er_b = ula == 2 ? (e > 0 ? e - 1 : 0) : e;       // the time index the network saw at this evaluation
-      if (nskb) {
-        const bool merged = M > 16;
-        auto launch3 = [&](NskArgs& na, int tiles) {
-          if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<3, true>), dim3((unsigned)tiles, 1), gblock, 0, stream, na);
-          else hipLaunchKernelGGL((lgcp_nsk_kernel<3, false>), dim3((unsigned)tiles, 1), gblock, 0, stream, na);
-        };
-        NskArgs na{};
-        na.M = M; na.D = D; na.IN = IN;
-        // d u2 = d o W3^T, d a2 = d u2 sigmoid(pre2)
-        na.seg[0] = NskSeg{dOp, gws + g.wt3p, IN, 0, 0.f}; na.nt0 = tIN;
-        na.bPre = e_pre2; na.bDuPrev = nullptr; na.bDu = gws + g.du2; na.outA = da2p; na.bDaBig = gws + g.DA2 + row0 * IN;
-        na.bSumA = gws + g.gb2; na.bSumU = nullptr;
-        launch3(na, tIN);
-        // d u1 = d u2 + d a2 W2^T, d a1 = d u1 sigmoid(pre1)
-        na.seg[0] = NskSeg{da2p, gws + g.wt2p, IN, 0, 0.f};
-        na.bPre = e_pre1; na.bDuPrev = gws + g.du2; na.bDu = gws + g.du1; na.outA = da1p; na.bDaBig = gws + g.DA1 + row0 * IN;
-        na.bSumA = gws + g.S + (int64_t)er_b * IN; na.bSumU = gws + g.S2 + (int64_t)er_b * IN;
-        launch3(na, tIN);
-        if (!bptt) continue;
-        // d a1 W1[:D]^T | v K^-1: plain products, row-major
-        NskArgs nb{};
-        nb.M = M; nb.D = D; nb.IN = IN;
-        nb.seg[0] = NskSeg{da1p, gws + g.wt1p, D, NSK_OUT, 0.f}; nb.nt0 = tD; nb.outN = gws + g.dxf;
-        nb.seg[1] = NskSeg{vp, ws + w.kip, D, NSK_KR, 0.f}; nb.krOutN = gws + g.hv;
-        if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<0, true>), dim3((unsigned)(2 * tD), 1), gblock, 0, stream, nb);
-        else hipLaunchKernelGGL((lgcp_nsk_kernel<0, false>), dim3((unsigned)(2 * tD), 1), gblock, 0, stream, nb);
-        LgcpLamArgs la{};
-        la.params = params; la.tc = tc; la.traj = traj; la.dxf = gws + g.dxf; la.hv = gws + g.hv; la.du1 = gws + g.du1;
-        la.v = gws + g.v; la.lam_part = gws + g.lam_part; la.gprev = gws + g.gprev; la.lamn = gws + g.lamn;
-        la.gE = gws + g.gE; la.gmu_acc = gws + g.gmu_acc; la.glam_acc = gws + g.glam_acc; la.lay = lay; la.n = n;
-        la.base = base; la.M = M; la.D = D; la.IN = IN; la.e = e; la.omega = omega; la.nslab = 1;
-        if (fuse && e > 0) hipLaunchKernelGGL(lgcp_lam_adj_kernel, dim3(cbD, M), dim3(64), 0, stream, la, adj_args(e - 1));
-        else hipLaunchKernelGGL(lgcp_lam_finish_kernel, dim3((M * D + 255) / 256), dim3(256), 0, stream, la);
-        continue;
-      }
-      // ---- net backward: d u2 = d o W3^T, then d a2 = d u2 sigmoid(pre2) as the GEMM's consumer
-      gm.counters = main_counters; gm.epi_seg = -1;
-      gm.Kdim = D;
-      gm.seg[0] = GemmSeg{gws + g.dO, gws + g.wt3, gws + g.du2s, IN, D, IN, IN};
-      gm.nblk0 = cbIN;
-      LgcpActbArgs& ab = gm.actb;
-      ab.pre = e_pre2; ab.du_prev = nullptr; ab.u_src = e_u2;
-      ab.du_out = gws + g.du2; ab.da_out = gws + g.da2; ab.da_big = gws + g.DA2; ab.u_big = kept ? nullptr : gws + g.U2;
-      ab.gb = gws + g.gb2; ab.row0 = row0; ab.IN = IN; ab.mode = 2;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACTB>, dim3(cbIN, kSplit), gblock, gemm_lds, stream, gm);
-      // d u1 = d u2 + d a2 W2^T, d a1 = d u1 sigmoid(pre1)
-      gm.Kdim = IN;
-      gm.seg[0] = GemmSeg{gws + g.da2, gws + g.wt2, gws + g.ts, IN, IN, IN, IN};
-      gm.nblk0 = cbIN;
-      ab.pre = e_pre1; ab.du_prev = gws + g.du2; ab.u_src = e_u1;
-      ab.du_out = gws + g.du1; ab.da_out = gws + g.da1; ab.da_big = gws + g.DA1; ab.u_big = kept ? nullptr : gws + g.U1;
-      {
-        const int er = ula == 2 ? (e > 0 ? e - 1 : 0) : e;     // the time index the network saw at this evaluation
-        ab.S = gws + g.S + (int64_t)er * IN; ab.S2 = gws + g.S2 + (int64_t)er * IN; ab.mode = 1;
-      }
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACTB>, dim3(cbIN, kSplit), gblock, gemm_lds, stream, gm);
-      if (!bptt) {   // z detached: no lambda, no Hessian product; this evaluation's buffers are free after actb
-        if (!kept && hipEventRecord(ev_bwd[e & 1], stream) != hipSuccess) return CMCD_ERR_HIP;
-        continue;
-      }
-      gm.Kdim = IN; gm.Kdim1 = D;                       // two independent products, one launch
-      gm.seg[0] = GemmSeg{gws + g.da1, gws + g.wt1, gws + g.dxf, D, IN, IN, D};
-      gm.seg[1] = GemmSeg{gws + g.v, kinv, gws + g.hv, D, D, D, D};
-      gm.nblk0 = cbD;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(2 * cbD, kSplit), gblock, gemm_lds, stream, gm);
-      gm.Kdim1 = 0;
-      LgcpLamArgs la{};
-      la.params = params; la.tc = tc; la.traj = traj; la.dxf = gws + g.dxf; la.hv = gws + g.hv; la.du1 = gws + g.du1;
-      la.v = gws + g.v; la.lam_part = gws + g.lam_part; la.gprev = gws + g.gprev; la.lamn = gws + g.lamn;
-      la.gE = gws + g.gE; la.gmu_acc = gws + g.gmu_acc; la.glam_acc = gws + g.glam_acc; la.lay = lay; la.n = n;
-      la.base = base; la.M = M; la.D = D; la.IN = IN; la.e = e; la.omega = omega;
-      if (fuse && e > 0) hipLaunchKernelGGL(lgcp_lam_adj_kernel, dim3(cbD, M), dim3(64), 0, stream, la, adj_args(e - 1));
-      else hipLaunchKernelGGL(lgcp_lam_finish_kernel, dim3((M * D + 255) / 256), dim3(256), 0, stream, la);
-      if (!kept && hipEventRecord(ev_bwd[e & 1], stream) != hipSuccess) return CMCD_ERR_HIP;
-    }
-    // q gradients of this pass: sum over its particles, accumulated into grad
-    hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, gws + g.gmu_acc, (int64_t)M, D, D,
-                       grad + lay.vd_mean, 1.0f, 1);
-    hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, gws + g.glam_acc, (int64_t)M, D, D,
-                       grad + lay.vd_logdiag, 1.0f, 1);
-  }
-  // ---- deferred parameter contractions over all (K+1) n rows
-  const int64_t R = (int64_t)(K + 1) * n;
-  if (net) {
-  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, dim3((IN + 127) / 128, (IN + 127) / 128, kTnSplit), dim3(256), 0, stream, gws + g.U1, gws + g.DA2,
+// the deferred parameter contractions over all R rows of the tables; xin: the network's state inputs [R][ZW]
+static void lgcp_param_contractions(const LgcpShape& s, const cmcd_layout& lay, const LgcpSweepWs& g, float* gws, const float* xin,
+                                    int64_t R, float* grad, hipStream_t stream) {
+  const int IN = s.IN, D = s.D, ZW = s.ZW;
+  auto tn = [&](int n_cols, int m_cols) { return dim3((n_cols + 127) / 128, (m_cols + 127) / 128, kTnSplit); };
+  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, tn(IN, IN), dim3(256), 0, stream, gws + g.U1, gws + g.DA2,
                      grad + lay.g_w2, R, IN, IN, IN, IN, IN);                                   // dW2 = U1^T dA2
-  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, dim3((D + 127) / 128, (IN + 127) / 128, kTnSplit), dim3(256), 0, stream, gws + g.U2, gws + g.DO,
+  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, tn(D, IN), dim3(256), 0, stream, gws + g.U2, gws + g.DO,
                      grad + lay.g_w3, R, IN, D, IN, D, D);                                      // dW3 = U2^T dO
-  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, dim3((IN + 127) / 128, (D + 127) / 128, kTnSplit), dim3(256), 0, stream, traj, gws + g.DA1,
-                     grad + lay.g_w1, R, D, IN, D, IN, IN);                                     // dW1[:D] = X^T dA1
+  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, tn(IN, ZW), dim3(256), 0, stream, xin, gws + g.DA1,
+                     grad + lay.g_w1, R, ZW, IN, ZW, IN, IN);                                   // dW1[:ZW] = X^T dA1
   hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, gws + g.DO, R, D, D, grad + lay.g_b3, 1.0f, 0);
   hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((IN + 255) / 256), dim3(256), 0, stream, gws + g.gb2, (int64_t)1, IN, IN, grad + lay.g_b2, 1.0f, 0);
+}
+
+// q gradients of one pass: sum over its M particles, accumulated into grad
+static void lgcp_q_grad_sums(const LgcpShape& s, const cmcd_layout& lay, const LgcpSweepWs& g, float* gws, int M, float* grad,
+                             hipStream_t stream) {
+  hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((s.D + 255) / 256), dim3(256), 0, stream, gws + g.gmu_acc, (int64_t)M, s.D, s.D,
+                     grad + lay.vd_mean, 1.0f, 1);
+  hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((s.D + 255) / 256), dim3(256), 0, stream, gws + g.glam_acc, (int64_t)M, s.D, s.D,
+                     grad + lay.vd_logdiag, 1.0f, 1);
+}
+
+// The backward of one network evaluation from the cotangent in dO down to d a1 (the third product, d a1 W1[:ZW]^T, is its
+// caller's: the two sweeps pair it differently):
+//   d u2 = d o W3^T,          d a2 = d u2 sigmoid(pre2)     (column sums into d b2)
+//   d u1 = d u2 + d a2 W2^T,  d a1 = d u1 sigmoid(pre1)     (column sums into rows `ti` of S / S2)
+// with the activation as each product's consumer; d a2 / d a1 also go to row `row` of the deferred contractions' tables.
+// nskb: on the no-split-K GEMM (kept activations, passes of <= 20 particles; operands dO | v | da2 | da1 packed in g.bops);
+// else on the split-K GEMM, g its caller's arguments (M, counters), which also keeps u1 / u2 unless the forward did.
+struct LgcpEvalActs { const float *pre1, *u1, *pre2, *u2; };
+// the sweep's packed operands in g.bops: dO | v (one round: D inputs) | da2 | da1 (`rounds` rounds: IN inputs)
+struct LgcpBackOps {
+  float *dO, *v, *da2, *da1;
+  int64_t floats;
+  LgcpBackOps(const LgcpShape& s, const LgcpSweepWs& g, float* gws)
+      : dO(gws + g.bops), v(dO + kNskOperand), da2(v + kNskOperand), da1(da2 + s.rounds * kNskOperand),
+        floats((2 + 2 * s.rounds) * kNskOperand) {}
+};
+static void lgcp_net_backward(const LgcpShape& s, const LgcpSweepWs& g, float* gws, int M, bool nskb, bool kept,
+                              const LgcpEvalActs& e, int64_t row, int ti, GemmArgs& gm, hipStream_t stream) {
+  const int IN = s.IN;
+  float* const S = gws + g.S + (int64_t)ti * IN, *S2 = gws + g.S2 + (int64_t)ti * IN;
+  if (nskb) {
+    const bool merged = M > 16;
+    const LgcpBackOps ops(s, g, gws);
+    float* const dOp = ops.dO, *da2p = ops.da2, *da1p = ops.da1;
+    NskArgs na{};
+    na.M = M; na.D = s.ZW; na.IN = IN; na.nch_out = s.nch;
+    na.seg[0] = NskSeg{dOp, gws + g.wt3p, IN, 0, 0.f}; na.nt0 = s.tIN;           // (one round: the contraction is D long)
+    na.bPre = e.pre2; na.bDuPrev = nullptr; na.bDu = gws + g.du2; na.outA = da2p; na.bDaBig = gws + g.DA2 + row * IN;
+    na.bSumA = gws + g.gb2; na.bSumU = nullptr;
+    lgcp_nsk_launch<3>(merged, dim3((unsigned)s.tIN, 1), stream, na);
+    na.seg[0] = NskSeg{da2p, gws + g.wt2p, IN, 0, 0.f}; na.seg[0].nch = s.nch;
+    na.bPre = e.pre1; na.bDuPrev = gws + g.du2; na.bDu = gws + g.du1; na.outA = da1p; na.bDaBig = gws + g.DA1 + row * IN;
+    na.bSumA = S; na.bSumU = S2;
+    if (s.rounds == 2) lgcp_nsk_launch<3, 2>(merged, dim3((unsigned)s.tIN, 1), stream, na);
+    else lgcp_nsk_launch<3>(merged, dim3((unsigned)s.tIN, 1), stream, na);
+    return;
   }
-  {
-    const int slots = (int)(n * cbD);
-    LgcpAdjRedArgs ra{gws + g.adjpart, ws + sw.sched, gws + g.gbeta, gws + g.geps, gws + g.gfac, K, slots};
-    hipLaunchKernelGGL(lgcp_adj_reduce_kernel, dim3(K + 1), dim3(64), 0, stream, ra);
-  }
-  if (net)
-    hipLaunchKernelGGL(lgcp_colsum_kernel, dim3(1), dim3(256), 0, stream, gws + g.gfac, (int64_t)(K + 1), 1, 1, grad + lay.g_factor, 1.0f, 0);
-  int rc = launch_geffner_tails(d, lay, sw, params, gws, g.S, g.S2, g.gbeta, g.geps, IN, grad, stream_, net);
-  if (rc != CMCD_OK) return rc;
-  return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
+  gm.epi_seg = -1;
+  gm.Kdim = s.D;
+  gm.seg[0] = GemmSeg{gws + g.dO, gws + g.wt3, gws + g.du2s, IN, s.D, IN, IN};
+  gm.nblk0 = s.cbIN;
+  LgcpActbArgs& ab = gm.actb;
+  ab.pre = e.pre2; ab.du_prev = nullptr; ab.u_src = e.u2;
+  ab.du_out = gws + g.du2; ab.da_out = gws + g.da2; ab.da_big = gws + g.DA2; ab.u_big = kept ? nullptr : gws + g.U2;
+  ab.gb = gws + g.gb2; ab.row0 = row; ab.IN = IN; ab.mode = 2;
+  lgcp_gemm_launch<EPI_ACTB>(s.cbIN, stream, gm);
+  gm.Kdim = IN;
+  gm.seg[0] = GemmSeg{gws + g.da2, gws + g.wt2, gws + g.ts, IN, IN, IN, IN};
+  ab.pre = e.pre1; ab.du_prev = gws + g.du2; ab.u_src = e.u1;
+  ab.du_out = gws + g.du1; ab.da_out = gws + g.da1; ab.da_big = gws + g.DA1; ab.u_big = kept ? nullptr : gws + g.U1;
+  ab.S = S; ab.S2 = S2; ab.mode = 1;
+  lgcp_gemm_launch<EPI_ACTB>(s.cbIN, stream, gm);
 }
 
 // =============================================================================================================
@@ -2352,46 +2084,6 @@ int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, in
 //   F2  m_b, log-weight increment, ub(z'), rho_new, key chain; at the last bridge log N(rho_K; 0, 1) + log p(z_K)
 // Passes of <= 32 particles run one after the other on the caller's stream.
 // =============================================================================================================
-struct LgcpUhaWs {
-  int64_t bias1;                                   // [K+1][IN]
-  int64_t zr, zrp, zn, rpp;                        // [kMP][2D], [kMP][2D], [kMP][D], [kMP][D]
-  int64_t u1, u2, pre1, pre2;                      // [kMP][IN]
-  int64_t slab1, slab2, sn, kr;                    // [kSplit][kMP][IN] x2, [kSplit][kMP][D] x2
-  int64_t w, fk, keys, gkey, counters, partials, total;
-  // r04, no-split-K form: packed weights (W1[:2d] | W2 | W3 | K^-1 with 2 kNskChunks chunks per tile: K^-1 zero beyond d) and
-  // packed operands zr | zrp | u1 | u2 | zn (2 kNskOperand floats each)
-  int64_t w1p, w2p, w3p, kip, ops;
-};
-
-// the 2nd-order sequence on the no-split-K kernel: widths up to 2 * 1664 inputs; desc.reserved == 3 pins the split-K sequence
-static bool lgcp_uha_nsk_ok(const cmcd_desc& d) {
-  const int D = d.dim, IN = 2 * D + d.emb_dim;
-  return d.reserved != 3 && D % 16 == 0 && D <= 16 * kNskChunks && IN <= 32 * kNskChunks;
-}
-
-static LgcpUhaWs lgcp_uha_ws(const cmcd_desc& d, int64_t n, int64_t base) {
-  const int64_t D = d.dim, IN = 2 * D + d.emb_dim, K = d.nbridges;
-  LgcpUhaWs w;
-  int64_t o = base;
-  auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; };
-  w.bias1 = take((K + 1) * IN);
-  w.zr = take(kMP * 2 * D); w.zrp = take(kMP * 2 * D); w.zn = take(kMP * D); w.rpp = take(kMP * D);
-  w.u1 = take(kMP * IN); w.u2 = take(kMP * IN); w.pre1 = take(kMP * IN); w.pre2 = take(kMP * IN);
-  w.slab1 = take(kSplit * kMP * IN); w.slab2 = take(kSplit * kMP * IN);
-  w.sn = take(kSplit * kMP * D); w.kr = take(kSplit * kMP * D);
-  w.w = take(kMP); w.fk = take(kMP); w.keys = take(2 * kMP); w.gkey = take(2 * kMP);
-  w.counters = take(((D + 63) / 64) + ((IN + 63) / 64));
-  o = (o + 1) & ~int64_t(1);
-  w.partials = take(n * CMCD_NSTATS * 2);
-  w.w1p = w.w2p = w.w3p = w.kip = w.ops = 0;
-  if (lgcp_uha_nsk_ok(d)) {
-    const int64_t tIN = (IN + 15) / 16, tD = D / 16, big = (int64_t)2 * kNskChunks * 256;
-    w.w1p = take(tIN * big); w.w2p = take(tIN * big); w.w3p = take(tD * big); w.kip = take(tD * big);
-    w.ops = take(5 * 2 * kNskOperand);
-  }
-  w.total = o;
-  return w;
-}
 
 struct LgcpUhaStepArgs {
   const int32_t* seeds;      // [M] (this pass; init only)
@@ -2618,86 +2310,71 @@ __global__ __launch_bounds__(64 * NW) void lgcp_uha_close_kernel(LgcpUhaStepArgs
   }
 }
 
-// the network on [zin | .] (lda = 2 D) at time index i: L1, L2, L3 of the header; `extra` (nullable): a second segment
-// of the first launch, (extra - mu0) K^-1 -> kr slabs
-static void lgcp_uha_net(const cmcd_desc& d, const cmcd_layout& lay, const float* params, const float* kinv, int M, int i,
-                         const float* zin, const float* bias1, float* slab1, float* pre1, float* u1, float* slab2, float* pre2,
-                         float* u2, float* sn, const float* extra, float* kr, int* counters, int gemm_lds, hipStream_t st) {
-  const int D = d.dim, E = d.emb_dim, IN = 2 * D + E;
-  const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64;
-  const float mu0 = 3.8812819069514780f;
-  const dim3 gblock(64 * kGemmWaves);
-  GemmArgs g{};
-  g.M = M; g.counters = counters;
-  g.act.x = zin; g.act.D = 2 * D; g.act.IN = IN;
-  g.Kdim = 2 * D; g.Kdim1 = extra ? D : 0;
-  g.seg[0] = GemmSeg{zin, params + lay.g_w1, slab1, IN, 2 * D, IN, IN};
-  if (extra) g.seg[1] = GemmSeg{extra, kinv, kr, D, D, D, D, mu0};
-  g.nblk0 = cbIN; g.epi_seg = extra ? 0 : -1;
-  g.act.mode = 1; g.act.bias = bias1 + (int64_t)i * IN; g.act.emb = params + lay.g_emb + (int64_t)i * E;
-  g.act.sum_out = pre1; g.act.u_prev = nullptr; g.act.u_out = u1;
-  hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACT>, dim3(cbIN + (extra ? cbD : 0), kSplit), gblock, gemm_lds, st, g);
-  g.Kdim = IN; g.Kdim1 = 0; g.epi_seg = -1;
-  g.seg[0] = GemmSeg{u1, params + lay.g_w2, slab2, IN, IN, IN, IN};
-  g.nblk0 = cbIN;
-  g.act.mode = 2; g.act.bias = params + lay.g_b2; g.act.sum_out = pre2; g.act.u_prev = u1; g.act.u_out = u2;
-  hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACT>, dim3(cbIN, kSplit), gblock, gemm_lds, st, g);
-  g.seg[0] = GemmSeg{u2, params + lay.g_w3, sn, D, IN, D, D};
-  g.nblk0 = cbD;
-  hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), gblock, gemm_lds, st, g);
-}
+// what a 2nd-order forward call was handed, with its workspace plan
+struct LgcpUhaCall {
+  const cmcd_layout& lay; const WsLayout& sw; const LgcpUhaWs& w;
+  const int32_t* seeds; int64_t n;
+  const float *params, *tc;
+  float *ws, *out_loss, *out_z;
+  double* partials;
+  float* traj;
+  hipStream_t stream;
+};
 
-static int64_t lgcp_uha_ws_total(const cmcd_desc& d, int64_t n, int64_t base) { return lgcp_uha_ws(d, n, base).total; }
+// the arguments of the element-wise kernels for the pass of M particles at `base`; zr / zrp / zn: row-major in the workspace
+// (split-K form: kr / sn are kSplit slabs) or packed operands (no-split-K form: one row-major array each)
+static LgcpUhaStepArgs lgcp_uha_step_args(const LgcpShape& s, const LgcpUhaCall& c, int64_t base, int M, float* zr, float* zrp,
+                                          float* zn, bool packed) {
+  float* const ws = c.ws;
+  const LgcpUhaWs& w = c.w;
+  LgcpUhaStepArgs sa{};
+  sa.seeds = c.seeds + base; sa.params = c.params; sa.tc = c.tc; sa.sched = ws + c.sw.sched;
+  sa.zr = zr; sa.zrp = zrp; sa.zn = zn; sa.rpp = ws + w.rpp; sa.kr = ws + w.kr; sa.sn = ws + w.sn;
+  sa.w = ws + w.w; sa.fk = ws + w.fk; sa.gen = reinterpret_cast<uint32_t*>(ws + w.keys);
+  sa.gkey = reinterpret_cast<uint32_t*>(ws + w.gkey);
+  sa.out_loss = c.out_loss + base; sa.out_z = c.out_z + base * s.D; sa.partials = c.partials + base * CMCD_NSTATS;
+  sa.traj = c.traj; sa.n_total = c.n; sa.base = base; sa.lay = c.lay; sa.M = M; sa.D = s.D; sa.K = s.K; sa.i = 0;
+  sa.packed = packed ? 1 : 0; sa.nslab = packed ? 1 : kSplit;
+  return sa;
+}
 
 // The 2nd-order sequence on the no-split-K GEMM (r04; header above lgcp_nsk_kernel): the same eight launches per bridge, the six
 // GEMMs on 16 x 16 tiles over the whole contraction — 3200 / 3220 inputs are two rounds of 13 chunks per wave — with packed
 // operands; the K^-1 product of z' rides in L6 (100 + 100 tiles) instead of L4 (202 + 100 would not fit the chip at one
-// workgroup per CU in the 17 .. 20-particle form); F1 / F2 read ONE product array each instead of summing eight slabs.
-static int lgcp_uha_forward_nsk(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, const LgcpUhaWs& w,
-                                const int32_t* seeds, int64_t n, const float* params, const float* tc, float* ws, float* out_loss,
-                                float* out_z, double* partials, float* traj, hipStream_t stream, float* keep_gws) {
-  const int D = d.dim, E = d.emb_dim, IN = 2 * D + E, K = d.nbridges;
-  const int tIN = (IN + 15) / 16, tD = D / 16, big = 2 * kNskChunks;
-  const LgcpKeep keep = keep_gws ? lgcp_uha_keep(d, n, keep_gws) : LgcpKeep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
-  const float mu0 = 3.8812819069514780f;
-  {
-    NskPackArgs pk{};
-    pk.src[0] = params + lay.g_w1; pk.dst[0] = ws + w.w1p; pk.K[0] = 2 * D; pk.N[0] = IN; pk.ntile[0] = tIN; pk.nch[0] = big;
-    pk.src[1] = params + lay.g_w2; pk.dst[1] = ws + w.w2p; pk.K[1] = IN; pk.N[1] = IN; pk.ntile[1] = tIN; pk.nch[1] = big;
-    pk.src[2] = params + lay.g_w3; pk.dst[2] = ws + w.w3p; pk.K[2] = IN; pk.N[2] = D; pk.ntile[2] = tD; pk.nch[2] = big;
-    pk.src[3] = tc; pk.dst[3] = ws + w.kip; pk.K[3] = D; pk.N[3] = D; pk.ntile[3] = tD; pk.nch[3] = big;   // zero rows beyond D
-    const int64_t groups = (int64_t)tIN * big * 64;
-    hipLaunchKernelGGL(lgcp_nsk_pack_kernel, dim3((unsigned)((groups + 255) / 256), 4), dim3(256), 0, stream, pk);
-  }
+// workgroup per CU in the 17 .. 20-particle form); F1 is the consumer of L3; F1 / F2 read ONE product array each instead of
+// summing eight slabs.
+static int lgcp_uha_forward_nsk(const LgcpShape& s, const LgcpUhaCall& c, const LgcpKeep& keep) {
+  const int D = s.D, E = s.E, IN = s.IN, K = s.K, tIN = s.tIN, tD = s.tD, big = s.nch;
+  const cmcd_layout& lay = c.lay;
+  const LgcpUhaWs& w = c.w;
+  const float* const params = c.params, *tc = c.tc;
+  float* const ws = c.ws;
+  const int64_t n = c.n;
+  hipStream_t stream = c.stream;
+  NskPack pk;
+  pk.add(params + lay.g_w1, ws + w.w1p, 2 * D, IN, tIN, big);
+  pk.add(params + lay.g_w2, ws + w.w2p, IN, IN, tIN, big);
+  pk.add(params + lay.g_w3, ws + w.w3p, IN, D, tD, big);
+  pk.add(tc, ws + w.kip, D, D, tD, big);   // zero rows beyond D
+  pk.launch(s, stream);
   float* const zrA = ws + w.ops, *zrpA = zrA + 2 * kNskOperand, *u1A = zrpA + 2 * kNskOperand, *u2A = u1A + 2 * kNskOperand;
   float* const znA = u2A + 2 * kNskOperand;
-  const dim3 gblock(64 * kGemmWaves);
   for (int64_t base = 0; base < n; base += kMP) {
     const int M = (int)((n - base) < kMP ? (n - base) : kMP);
     // the padding of the packed operands (rows >= M, inputs >= IN) must read as zeros
     if (hipMemsetAsync(zrA, 0, sizeof(float) * (5 * 2 * kNskOperand), stream) != hipSuccess) return CMCD_ERR_HIP;
-    LgcpUhaStepArgs sa{};
-    sa.seeds = seeds + base; sa.params = params; sa.tc = tc; sa.sched = ws + sw.sched;
-    sa.zr = zrA; sa.zrp = zrpA; sa.zn = znA; sa.rpp = ws + w.rpp; sa.kr = ws + w.kr; sa.sn = ws + w.sn;
-    sa.w = ws + w.w; sa.fk = ws + w.fk; sa.gen = reinterpret_cast<uint32_t*>(ws + w.keys);
-    sa.gkey = reinterpret_cast<uint32_t*>(ws + w.gkey);
-    sa.out_loss = out_loss + base; sa.out_z = out_z + base * D; sa.partials = partials + base * CMCD_NSTATS;
-    sa.traj = traj; sa.n_total = n; sa.base = base; sa.lay = lay; sa.M = M; sa.D = D; sa.K = K; sa.i = 0;
-    sa.packed = 1; sa.nslab = 1;
+    LgcpUhaStepArgs sa = lgcp_uha_step_args(s, c, base, M, zrA, zrpA, znA, true);
     hipLaunchKernelGGL(lgcp_uha_init_kernel, dim3(M), dim3(256), 0, stream, sa);
+    // 17 .. 20 particles: one workgroup per column tile (16x16x4 + 4x4x1 on the same weight registers) — at these widths the
+    // weights are the bytes, so every launch takes the form that fetches them once
     const bool can_merge = M > 16 && M <= 20;
-    auto launch = [&](NskArgs& na, int tiles) {
-      // 17 .. 20 particles: one workgroup per column tile (16x16x4 + 4x4x1 on the same weight registers) — at these widths the
-      // weights are the bytes, so every launch takes the form that fetches them once
-      if (can_merge) hipLaunchKernelGGL((lgcp_nsk_kernel<0, true, 2>), dim3((unsigned)tiles, 1), gblock, 0, stream, na);
-      else hipLaunchKernelGGL((lgcp_nsk_kernel<0, false, 2>), dim3((unsigned)tiles, M > 16 ? 2 : 1), gblock, 0, stream, na);
-    };
-    auto kinv_seg = [&]() { NskSeg sg{znA, ws + w.kip, D, NSK_KR, mu0}; sg.nch = big; return sg; };
+    auto grid = [&](int tiles) { return dim3((unsigned)tiles, !can_merge && M > 16 ? 2 : 1); };
+    auto kinv_seg = [&]() { NskSeg sg{znA, ws + w.kip, D, NSK_KR, kLgcpMu0}; sg.nch = big; return sg; };
     {   // K^-1 (z_0 - mu0)
       NskArgs na{};
       na.M = M; na.D = 2 * D; na.IN = IN; na.seg[0] = kinv_seg(); na.nt0 = tD; na.krOutN = ws + w.kr;
       if (keep.on) na.keepKr = keep.kr + base * D;
-      launch(na, tD);
+      lgcp_nsk_launch<0, 2>(can_merge, grid(tD), stream, na);
     }
     float* const fkslot = ws + w.slab1;      // [D / 16][kMP] (the split-K form's slab region is free here)
     sa.fkslot = fkslot;
@@ -2711,11 +2388,11 @@ static int lgcp_uha_forward_nsk(const cmcd_desc& d, const cmcd_layout& lay, cons
       // (gradient calls: this evaluation's rows of the kept tables — 2 i for [z; rho], 2 i + 1 for [z; rho'])
       const int64_t krow = (int64_t)(2 * i + (with_kinv ? 1 : 0)) * n + base;
       if (keep.on) { na.keepPre = keep.pre1 + krow * IN; na.keepU = keep.u1 + krow * IN; }
-      launch(na, tIN);
+      lgcp_nsk_launch<0, 2>(can_merge, grid(tIN), stream, na);
       na.seg[0] = NskSeg{u1A, ws + w.w2p, IN, NSK_ACT2, 0.f}; na.seg[0].nch = big;
       na.bias = params + lay.g_b2; na.uA = u1A; na.outA = u2A;
       if (keep.on) { na.keepPre = keep.pre2 + krow * IN; na.keepU = keep.u2 + krow * IN; }
-      launch(na, tIN);
+      lgcp_nsk_launch<0, 2>(can_merge, grid(tIN), stream, na);
       na.seg[0] = NskSeg{u2A, ws + w.w3p, D, with_kinv ? NSK_OUT : NSK_UHA_MID, 0.f}; na.seg[0].nch = big; na.nt0 = tD;
       na.outN = ws + w.sn;
       na.keepPre = nullptr; na.keepU = nullptr;
@@ -2723,15 +2400,14 @@ static int lgcp_uha_forward_nsk(const cmcd_desc& d, const cmcd_layout& lay, cons
       if (with_kinv) {
         na.seg[1] = kinv_seg(); na.krOutN = ws + w.kr;
         if (keep.on) na.keepKr = keep.kr + ((int64_t)(i + 1) * n + base) * D;   // K^-1 (z_{i+1} - mu0)
-        launch(na, 2 * tD);
+        lgcp_nsk_launch<0, 2>(can_merge, grid(2 * tD), stream, na);
         return;
       }
       NskArgs::UhaMid& um = na.um;
-      um.params = params; um.tc = tc; um.sched = ws + sw.sched; um.zr = zrA; um.zrp = zrpA; um.zn = znA; um.rpp = ws + w.rpp;
-      um.kr = ws + w.kr; um.gkey = reinterpret_cast<const uint32_t*>(ws + w.gkey); um.fkslot = fkslot; um.traj = traj;
+      um.params = params; um.tc = tc; um.sched = ws + c.sw.sched; um.zr = zrA; um.zrp = zrpA; um.zn = znA; um.rpp = ws + w.rpp;
+      um.kr = ws + w.kr; um.gkey = reinterpret_cast<const uint32_t*>(ws + w.gkey); um.fkslot = fkslot; um.traj = c.traj;
       um.n_total = n; um.base = base; um.lay = lay; um.D = D; um.K = K; um.i = i;
-      if (can_merge) hipLaunchKernelGGL((lgcp_nsk_kernel<2, true, 2>), dim3((unsigned)tD, 1), gblock, 0, stream, na);
-      else hipLaunchKernelGGL((lgcp_nsk_kernel<2, false, 2>), dim3((unsigned)tD, M > 16 ? 2 : 1), gblock, 0, stream, na);
+      lgcp_nsk_launch<2, 2>(can_merge, grid(tD), stream, na);
     };
     for (int i = 0; i < K; ++i) {
       sa.i = i;
@@ -2743,55 +2419,258 @@ static int lgcp_uha_forward_nsk(const cmcd_desc& d, const cmcd_layout& lay, cons
   return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
 }
 
+// The 2nd-order forward: the prep launch, then the no-split-K form above or the split-K form here — the eight launches of the
+// header, lgcp_net_splitk twice per bridge with z' riding in L4.
 static int lgcp_uha_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, const int32_t* seeds, int64_t n,
                             const float* params, const float* tc, float* ws, float* out_loss, float* out_z,
                             double** partials_out, float* traj, hipStream_t stream, float* keep_gws) {
-  const int D = d.dim, E = d.emb_dim, IN = 2 * D + E, K = d.nbridges;
+  const LgcpShape s = lgcp_shape(d);
+  const int D = s.D, E = s.E, IN = s.IN, K = s.K;
   const LgcpUhaWs w = lgcp_uha_ws(d, n, sw.total_floats);
   LgcpPrepArgs pa{params, ws + w.bias1, lay, 2 * D, E, K, IN};   // bias1_i = b1 + emb_i W1[2d:, :]
   hipLaunchKernelGGL(lgcp_prep_kernel, dim3((IN + 255) / 256, K + 1), dim3(256), 0, stream, pa);
-  if (lgcp_uha_nsk_ok(d)) {
-    double* partials_n = reinterpret_cast<double*>(ws + w.partials);
-    *partials_out = partials_n;
-    return lgcp_uha_forward_nsk(d, lay, sw, w, seeds, n, params, tc, ws, out_loss, out_z, partials_n, traj, stream, keep_gws);
-  }
-  const int gemm_lds = lgcp_gemm_attrs();
-  if (gemm_lds < 0) return CMCD_ERR_HIP;
   double* partials = reinterpret_cast<double*>(ws + w.partials);
   *partials_out = partials;
-  const float mu0 = 3.8812819069514780f;
-  const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64;
+  const LgcpUhaCall c{lay, sw, w, seeds, n, params, tc, ws, out_loss, out_z, partials, traj, stream};
+  if (s.nsk) return lgcp_uha_forward_nsk(s, c, keep_gws ? lgcp_keep(lgcp_uha_grad_ws(d, n), keep_gws) : LgcpKeep{});
+  if (!lgcp_gemm_attrs()) return CMCD_ERR_HIP;
   int* counters = reinterpret_cast<int*>(ws + w.counters);
   // (a launch like its siblings, not a memset node; the captured case lgcp-uha-rc-n33 and the uha-rc-* / uha-w3332-* parity cases reach it)
-  if (lgcp_zero(stream, counters, cbD + cbIN) != CMCD_OK) return CMCD_ERR_HIP;
+  if (lgcp_zero(stream, counters, s.cbD + s.cbIN) != CMCD_OK) return CMCD_ERR_HIP;
+  const LgcpNetBufs nb{ws + w.slab1, ws + w.pre1, ws + w.u1, ws + w.slab2, ws + w.pre2, ws + w.u2, ws + w.sn};
+  const LgcpKinvRider zn_rider{0, 1, ws + w.zn, ws + w.kr};
   for (int64_t base = 0; base < n; base += kMP) {
     const int M = (int)((n - base) < kMP ? (n - base) : kMP);
-    LgcpUhaStepArgs sa{};
-    sa.seeds = seeds + base; sa.params = params; sa.tc = tc; sa.sched = ws + sw.sched;
-    sa.zr = ws + w.zr; sa.zrp = ws + w.zrp; sa.zn = ws + w.zn; sa.rpp = ws + w.rpp; sa.kr = ws + w.kr; sa.sn = ws + w.sn;
-    sa.w = ws + w.w; sa.fk = ws + w.fk; sa.gen = reinterpret_cast<uint32_t*>(ws + w.keys);
-    sa.gkey = reinterpret_cast<uint32_t*>(ws + w.gkey);
-    sa.out_loss = out_loss + base; sa.out_z = out_z + base * D; sa.partials = partials + base * CMCD_NSTATS;
-    sa.traj = traj; sa.n_total = n; sa.base = base; sa.lay = lay; sa.M = M; sa.D = D; sa.K = K; sa.i = 0;
-    sa.packed = 0; sa.nslab = kSplit;
+    LgcpUhaStepArgs sa = lgcp_uha_step_args(s, c, base, M, ws + w.zr, ws + w.zrp, ws + w.zn, false);
     hipLaunchKernelGGL(lgcp_uha_init_kernel, dim3(M), dim3(256), 0, stream, sa);
-    {   // K^-1 (z_0 - mu0)
-      GemmArgs g{};
-      g.M = M; g.Kdim = D; g.counters = counters;
-      g.seg[0] = GemmSeg{ws + w.zr, tc, ws + w.kr, D, 2 * D, D, D, mu0};
-      g.nblk0 = cbD;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), dim3(64 * kGemmWaves), gemm_lds, stream, g);
-    }
+    GemmArgs g{};
+    g.M = M; g.Kdim = D; g.counters = counters;
+    g.seg[0] = GemmSeg{ws + w.zr, tc, ws + w.kr, D, 2 * D, D, D, kLgcpMu0};   // K^-1 (z_0 - mu0)
+    g.nblk0 = s.cbD;
+    lgcp_gemm_launch<EPI_NONE>(s.cbD, stream, g);
     for (int i = 0; i < K; ++i) {
       sa.i = i;
-      lgcp_uha_net(d, lay, params, tc, M, i, ws + w.zr, ws + w.bias1, ws + w.slab1, ws + w.pre1, ws + w.u1, ws + w.slab2,
-                   ws + w.pre2, ws + w.u2, ws + w.sn, nullptr, nullptr, counters, gemm_lds, stream);
+      const float* bias1_i = ws + w.bias1 + (int64_t)i * IN, *emb_i = params + lay.g_emb + (int64_t)i * E;
+      GemmArgs ga{}, gb{};
+      ga.M = gb.M = M; ga.counters = gb.counters = counters;
+      lgcp_net_splitk(s, lay, params, tc, ga, ws + w.zr, bias1_i, emb_i, nb, nullptr, false, stream);
       hipLaunchKernelGGL(lgcp_uha_mid_kernel<4>, dim3(M), dim3(256), 0, stream, sa);
-      lgcp_uha_net(d, lay, params, tc, M, i, ws + w.zrp, ws + w.bias1, ws + w.slab1, ws + w.pre1, ws + w.u1, ws + w.slab2,
-                   ws + w.pre2, ws + w.u2, ws + w.sn, ws + w.zn, ws + w.kr, counters, gemm_lds, stream);
+      lgcp_net_splitk(s, lay, params, tc, gb, ws + w.zrp, bias1_i, emb_i, nb, &zn_rider, false, stream);
       hipLaunchKernelGGL(lgcp_uha_close_kernel<4>, dim3(M), dim3(256), 0, stream, sa);
     }
   }
+  return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
+}
+
+// -------------------------------------------------------------------------------------------------------------
+// The forward call of the d = 1600 path: the 2nd-order sequence above, the wide-batch path (cmcd_lgcp_wide.hip), or the
+// overdamped sequences here, in passes of <= kMP particles on up to kLanes streams.
+// -------------------------------------------------------------------------------------------------------------
+int lgcp_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, const int32_t* seeds, int64_t n,
+                 const float* params, const float* tc, float* ws, float* out_loss, float* out_z,
+                 double** partials_out, float* traj, void* stream_, bool tables_ready, float* keep_gws) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (d.mode == CMCD_MODE_CAIS_UHA_SN)
+    return lgcp_uha_forward(d, lay, sw, seeds, n, params, tc, ws, out_loss, out_z, partials_out, traj, stream, keep_gws);
+  if (lgcp_use_wide(d, n, traj != nullptr))
+    return lgcp_wide_forward(d, lay, sw, seeds, n, params, tc, ws, out_loss, out_z, partials_out, stream_, tables_ready);
+  const LgcpShape s = lgcp_shape(d);
+  const int D = s.D, E = s.E, IN = s.IN, K = s.K, cbD = s.cbD, cbIN = s.cbIN, tIN = s.tIN, tD = s.tD;
+  const LgcpWs w = lgcp_ws(d, n, sw.total_floats);
+  if (d.mode != CMCD_MODE_ULA && !tables_ready) {   // MCD_ULA has no network leaves at all
+    LgcpPrepArgs pa{params, ws + w.bias1, lay, D, E, K, IN};
+    hipLaunchKernelGGL(lgcp_prep_kernel, dim3((IN + 255) / 256, K + 1), dim3(256), 0, stream, pa);
+  }
+  if (!lgcp_gemm_attrs()) return CMCD_ERR_HIP;
+  // r04: the forward runs on the no-split-K GEMM (header above lgcp_nsk_kernel); weights re-packed once per call
+  const bool nsk = s.nsk;
+  if (nsk && !tables_ready) {
+    NskPack pk;
+    pk.add(tc, ws + w.kip, D, D, tD);
+    if (d.mode != CMCD_MODE_ULA) {
+      pk.add(params + lay.g_w1, ws + w.w1p, D, IN, tIN);     // the state rows W1[:d] only: the embedding rows are in bias1
+      pk.add(params + lay.g_w2, ws + w.w2p, IN, IN, tIN);
+      pk.add(params + lay.g_w3, ws + w.w3p, IN, D, tD);
+    }
+    pk.launch(s, stream);
+  }
+  const float* kinv = tc;
+  double* partials = reinterpret_cast<double*>(ws + w.partials);
+  *partials_out = partials;
+
+  // Passes of <= kMP particles are independent chains of 3 (K + 1) latency-bound launches: up to kLanes of them run side
+  // by side, lane 0 on the caller's stream, the others on per-thread side streams forked from / joined to it by events
+  // (capturable in a graph, like the reverse sweep's two streams).  One pass (the named N = 20 batch): no side stream.
+  const int lanes = lgcp_lanes(n);
+  LgcpDevSlot* slot = lgcp_dev_slot();
+  if (!slot) return CMCD_ERR_HIP;
+  hipStream_t* side = slot->fwd.side;
+  hipEvent_t* ev_join = slot->fwd.ev_join;
+  hipEvent_t& ev_fork = slot->fwd.ev_fork;
+  if (lanes > 1 && !ev_fork) {
+    for (int l = 1; l < kLanes; ++l) {
+      if (hipStreamCreateWithFlags(&side[l], hipStreamNonBlocking) != hipSuccess) return CMCD_ERR_HIP;
+      if (hipEventCreateWithFlags(&ev_join[l], hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
+    }
+    if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
+  }
+  if (lanes > 1 && hipEventRecord(ev_fork, stream) != hipSuccess) return CMCD_ERR_HIP;   // behind the prep launch
+  // from here on the side streams are forked from the caller's stream: every exit joins them again (an un-joined fork
+  // would invalidate a graph capture and leave work of this call running behind the caller's back)
+  bool forked[kLanes] = {false, false, false, false};
+  auto join_all = [&]() {
+    bool ok = true;
+    for (int l = 1; l < lanes; ++l) {
+      if (!forked[l]) continue;
+      ok = hipEventRecord(ev_join[l], side[l]) == hipSuccess && ok;
+      ok = hipStreamWaitEvent(stream, ev_join[l], 0) == hipSuccess && ok;
+    }
+    return ok;
+  };
+  auto bail = [&]() { join_all(); return (int)CMCD_ERR_HIP; };
+
+  int* counters[kLanes];
+  for (int l = 0; l < lanes; ++l) {
+    hipStream_t st_l = l == 0 ? stream : side[l];
+    if (l > 0) {
+      if (hipStreamWaitEvent(st_l, ev_fork, 0) != hipSuccess) return bail();
+      forked[l] = true;
+    }
+    counters[l] = reinterpret_cast<int*>(ws + w.lane[l].counters);     // (cleared with the lane's first pass below)
+  }
+  const int ula = d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0);
+  const LgcpKeep keep = keep_gws ? lgcp_keep(lgcp_grad_ws(d, n), keep_gws) : LgcpKeep{};
+  // groups of `lanes` passes; inside a group the launches are enqueued evaluation by evaluation, round-robin over the
+  // lanes, so that the chains advance together (the same weights are in flight for all of them)
+  for (int64_t gbase = 0; gbase < n; gbase += (int64_t)lanes * kMP) {
+    GemmArgs g[kLanes];
+    int M[kLanes], live = 0;
+    for (int l = 0; l < lanes; ++l) {
+      const int64_t base = gbase + (int64_t)l * kMP;
+      if (base >= n) break;
+      ++live;
+      hipStream_t st_l = l == 0 ? stream : side[l];
+      const LgcpLane& wl = w.lane[l];
+      M[l] = (int)((n - base) < kMP ? (n - base) : kMP);
+      // packed operands: the padding (rows >= M, inputs >= IN) must read as zeros; slots start at zero; the lane's arrival
+      // counters once per call (every lane is live in the first group).  One launch on the lane's stream (lgcp_zero_kernel).
+      if (lgcp_zero(st_l, ws + wl.slots, 3 * (int64_t)cbD * kMP,
+                    nsk ? ws + wl.nsk : nullptr, nsk ? kNskOps * kNskOperand + 3 * (int64_t)tD * kMP : 0,
+                    gbase == 0 ? counters[l] : nullptr, gbase == 0 ? cbD + cbIN : 0) != CMCD_OK)
+        return bail();
+      LgcpStateArgs st{};
+      st.seeds = seeds + base; st.params = params; st.tc = tc; st.x = nsk ? ws + wl.nsk : ws + wl.x; st.packed = nsk ? 1 : 0;
+      st.w = ws + wl.w; st.keys = reinterpret_cast<uint32_t*>(ws + wl.keys);
+      st.gkey = reinterpret_cast<uint32_t*>(ws + wl.gkey); st.gktab = reinterpret_cast<uint32_t*>(ws + w.gktab);
+      st.lay = lay; st.M = M[l]; st.D = D;
+      st.traj = traj; st.n_total = n; st.base = base;
+      hipLaunchKernelGGL(lgcp_init_kernel, dim3(M[l]), dim3(256), 0, st_l, st);
+
+      g[l] = GemmArgs{};
+      g[l].M = M[l]; g[l].counters = counters[l];
+      g[l].act.x = ws + wl.x; g[l].act.D = D; g[l].act.IN = IN;
+      StepEpi& se = g[l].step;
+      se.params = params; se.tc = tc; se.sched = ws + sw.sched; se.x = ws + wl.x; se.xp = ws + wl.xp;
+      se.kr = ws + wl.kr; se.b3 = params + lay.g_b3; se.factor = params + lay.g_factor;
+      se.gen = reinterpret_cast<uint32_t*>(ws + wl.keys); se.gkey = reinterpret_cast<uint32_t*>(ws + wl.gkey);
+      se.gktab = reinterpret_cast<uint32_t*>(ws + w.gktab);
+      se.wslot = ws + wl.slots; se.fkslot = se.wslot + cbD * kMP; se.lpslot = se.fkslot + cbD * kMP;
+      if (nsk) {   // one slot row per 16-column tile
+        se.wslot = ws + wl.nsk + kNskOps * kNskOperand; se.fkslot = se.wslot + tD * kMP; se.lpslot = se.fkslot + tD * kMP;
+      }
+      se.out_z = out_z + base * D; se.traj = traj; se.n_total = n; se.base = base; se.lay = lay;
+      se.D = D; se.K = K; se.var_mode = d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0; se.grad_clipping = d.grad_clipping;
+      se.ula = ula;
+    }
+    for (int i = 0; i <= K; ++i) {
+      // CAIS: s(z_i, i) serves both kernels; MCD_ULA_sn: s(z_i, i - 1) serves the backward kernel only
+      const int it = ula == 2 ? (i > 0 ? i - 1 : 0) : i;
+      const int ie = it < K ? it : K - 1;
+      const float* bias1_i = ws + w.bias1 + (int64_t)it * IN, *emb_i = params + lay.g_emb + (int64_t)ie * E;
+      for (int l = 0; l < live; ++l) {
+        hipStream_t st_l = l == 0 ? stream : side[l];
+        const LgcpLane& wl = w.lane[l];
+        GemmArgs& gl = g[l];
+        gl.step.i = i;
+        if (nsk) {
+          // evaluation i reads z_i from buffer i % 3, z_{i-1} from (i + 2) % 3 and writes z_{i+1} into (i + 1) % 3
+          float* const sb = ws + wl.nsk;
+          float* const xA = sb + (i % 3) * kNskOperand;
+          float* const u1A = sb + 3 * kNskOperand, *u2A = u1A + kNskOperand, *krA = u2A + kNskOperand;
+          NskArgs na{};
+          na.M = M[l]; na.D = D; na.IN = IN; na.xA = xA; na.xpA = sb + ((i + 2) % 3) * kNskOperand;
+          na.xnA = sb + ((i + 1) % 3) * kNskOperand; na.krA = krA; na.krOut = krA; na.step = gl.step;
+          // 17 .. 20 particles (the named batch): one workgroup per column tile serves both row blocks (16x16x4 + 4x4x1);
+          // otherwise one workgroup per (tile, 16-row half).  State-update launches carry one extra workgroup (key chain).
+          // Measured at N = 20 (profiles/r04_f_lgcp_nsk_per_launch_n20.txt): merged helps the launch that is otherwise two
+          // workgroups per CU (B: 9.96 -> 7.44 us) and costs the two that are one per CU either way (A 6.48 -> 7.08, C 7.64 ->
+          // 8.40: half as many CUs pull the bytes), so only launch B takes it.
+          const bool can_merge = M[l] > 16 && M[l] <= 20;
+          auto launch = [&](bool step, int tiles, bool want_merged = false) {
+            const bool merged = can_merge && want_merged;
+            const unsigned gy = (!merged && M[l] > 16) ? 2 : 1;
+            dim3 grid((unsigned)tiles + (step ? 1 : 0), gy);
+            na.pair_gx = 0;
+            if (gy == 2 && lgcp_xcd_pairs()) {   // both row halves of a column tile on one XCD (NskArgs::pair_gx)
+              na.pair_gx = (int)grid.x;
+              grid = dim3(16u * ((grid.x + 7) / 8), 1);
+            }
+            if (step) lgcp_nsk_launch<1>(merged, grid, st_l, na);
+            else lgcp_nsk_launch<0>(merged, grid, st_l, na);
+          };
+          // (gradient calls: this evaluation's rows of the kept tables)
+          const int64_t krow = (int64_t)i * n + gbase + (int64_t)l * kMP;
+          if (ula == 1) {   // MCD_ULA: one launch per evaluation, (x - mu0) K^-1 with the state update as its consumer
+            na.seg[0] = NskSeg{xA, ws + w.kip, D, NSK_STEP_NONET, kLgcpMu0}; na.nt0 = tD;
+            if (keep.on) na.keepKr = keep.kr + krow * D;
+            launch(true, tD);
+            continue;
+          }
+          // A: x W1[:D] -> u1 = [x; emb_i] + softplus(. + bias1_i)
+          na.seg[0] = NskSeg{xA, ws + w.w1p, IN, NSK_ACT1, 0.f}; na.nt0 = tIN;
+          na.bias = bias1_i; na.emb = emb_i; na.outA = u1A;
+          if (keep.on) { na.keepPre = keep.pre1 + krow * IN; na.keepU = keep.u1 + krow * IN; }
+          launch(false, tIN);
+          // B: u1 W2 -> u2 = u1 + softplus(. + b2)   |   (x - mu0) K^-1 -> kr
+          na.seg[0] = NskSeg{u1A, ws + w.w2p, IN, NSK_ACT2, 0.f};
+          na.seg[1] = NskSeg{xA, ws + w.kip, D, NSK_KR, kLgcpMu0};
+          na.bias = params + lay.g_b2; na.uA = u1A; na.outA = u2A;
+          if (keep.on) { na.keepPre = keep.pre2 + krow * IN; na.keepU = keep.u2 + krow * IN; na.keepKr = keep.kr + krow * D; }
+          launch(false, tIN + tD, true);
+          // C: u2 W3 -> the state update of evaluation i on the tile's elements
+          na.seg[0] = NskSeg{u2A, ws + w.w3p, D, NSK_STEP, 0.f}; na.nt0 = tD;
+          na.keepPre = nullptr; na.keepU = nullptr; na.keepKr = nullptr;
+          if (keep.on) na.keepSn = keep.sn + krow * D;
+          launch(true, tD);
+          continue;
+        }
+        if (ula == 1) {   // MCD_ULA: one launch per evaluation, [x - mu0] Kinv with the state update as its consumer
+          // the state is this launch's operand: z_i / z_{i-1} / z_{i+1} rotate through x, xp and the (unused: no network)
+          // u1 buffer instead of an in-place update that a slower workgroup of another column block could still be loading
+          float* const sb3[3] = {ws + wl.x, ws + wl.xp, ws + wl.u1};
+          gl.step.x = sb3[i % 3]; gl.step.xp = sb3[(i + 2) % 3]; gl.step.xn = sb3[(i + 1) % 3];
+          gl.Kdim = D; gl.Kdim1 = 0;
+          gl.seg[0] = GemmSeg{gl.step.x, kinv, ws + wl.kr, D, D, D, D, kLgcpMu0};
+          gl.nblk0 = cbD; gl.epi_seg = -1;
+          lgcp_gemm_launch<EPI_STEP_NONET>(cbD, st_l, gl);
+          continue;
+        }
+        // A, B | (x - mu0) K^-1, C with the state update of evaluation i as its consumer (lgcp_net_splitk)
+        const LgcpNetBufs nb{ws + wl.slab1, ws + wl.pre1, ws + wl.u1, ws + wl.slab2, ws + wl.pre2, ws + wl.u2, ws + wl.sn};
+        const LgcpKinvRider rider{1, 1, ws + wl.x, ws + wl.kr};
+        lgcp_net_splitk(s, lay, params, kinv, gl, ws + wl.x, bias1_i, emb_i, nb, &rider, true, st_l);
+      }
+    }
+    for (int l = 0; l < live; ++l) {
+      hipStream_t st_l = l == 0 ? stream : side[l];
+      const int64_t base = gbase + (int64_t)l * kMP;
+      const StepEpi& se = g[l].step;
+      LgcpFinalArgs fa{ws + w.lane[l].w, se.wslot, se.lpslot, tc, out_loss + base, partials + base * CMCD_NSTATS, M[l], D,
+                       nsk ? tD : cbD};
+      hipLaunchKernelGGL(lgcp_final_kernel, dim3(M[l]), dim3(64), 0, st_l, fa);
+    }
+  }
+  if (!join_all()) return CMCD_ERR_HIP;
   return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
 }
 
@@ -2803,72 +2682,6 @@ static int lgcp_uha_forward(const cmcd_desc& d, const cmcd_layout& lay, const Ws
 // GEMMs each against transposed weight copies.  The O(width^2) parameter gradients are deferred: every evaluation's
 // (input, u1, u2, d a1, d a2, d o) rows are kept and contracted at the end by A^T B products (inner dimension 2 K n).
 // -------------------------------------------------------------------------------------------------------------
-struct LgcpUhaFwdSet { int64_t zin, slab1, pre1, u1, slab2, pre2, u2, sn; };
-
-struct LgcpUhaGradWs {
-  int64_t wt1, wt2, wt3;                        // W1[:2D]^T [IN][2D], W2^T [IN][IN], W3^T [D][IN]
-  LgcpUhaFwdSet fs[2];                          // evaluation A = s([z; rho]), B = s([z; rho'])
-  int64_t kr, hv;                               // [kSplit][kMP][D]
-  int64_t v, dO, arp, gb, lrn, arppc;           // [kMP][D]
-  int64_t du2s, ts;                             // [kSplit][kMP][IN]
-  int64_t du2, du1, da2, da1;                   // [kMP][IN]
-  int64_t dxf;                                  // [kSplit][kMP][2D]
-  int64_t XIN, U1, U2, DA1, DA2, DO;            // [2 K n][2D | IN | IN | IN | IN | D]
-  int64_t zero_lo, zero_hi;
-  int64_t lz, lr, gmu_acc, glam_acc;            // [kMP][D]
-  int64_t geta, gepsd;                          // [kMP]
-  int64_t S, S2, gb2, gbeta, geps, counters;
-  int64_t sc;                                   // [(K+1)][n][8]
-  int64_t kpre1, kpre2, ksn, kkr;               // kept by the forward (lgcp_uha_keep): [2 K n][IN] x 2, [2 K n][D], [(K+1) n][D]
-  bool keep;
-  int64_t bops, wt3p, wt2p, wt1p, kip1;         // keep: packed dO | v (one round) | da2 | da1 (two rounds), packed W3^T, W2^T, W1[:2D]^T, K^-1
-  int64_t total;
-};
-
-static LgcpUhaGradWs lgcp_uha_grad_ws(const cmcd_desc& d, int64_t n) {
-  const int64_t D = d.dim, IN = 2 * D + d.emb_dim, K = d.nbridges, R = 2 * K * n;
-  LgcpUhaGradWs w;
-  int64_t o = 0;
-  auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; };
-  w.wt1 = take(IN * 2 * D); w.wt2 = take(IN * IN); w.wt3 = take(D * IN);
-  for (int b = 0; b < 2; ++b) {
-    LgcpUhaFwdSet& f = w.fs[b];
-    f.zin = take(kMP * 2 * D); f.slab1 = take(kSplit * kMP * IN); f.pre1 = take(kMP * IN); f.u1 = take(kMP * IN);
-    f.slab2 = take(kSplit * kMP * IN); f.pre2 = take(kMP * IN); f.u2 = take(kMP * IN); f.sn = take(kSplit * kMP * D);
-  }
-  w.kr = take(kSplit * kMP * D); w.hv = take(kSplit * kMP * D);
-  w.v = take(kMP * D); w.dO = take(kMP * D); w.arp = take(kMP * D); w.gb = take(kMP * D); w.lrn = take(kMP * D);
-  w.arppc = take(kMP * D);
-  w.du2s = take(kSplit * kMP * IN); w.ts = take(kSplit * kMP * IN);
-  w.du2 = take(kMP * IN); w.du1 = take(kMP * IN); w.da2 = take(kMP * IN); w.da1 = take(kMP * IN);
-  w.dxf = take(kSplit * kMP * 2 * D);
-  w.XIN = take(R * 2 * D); w.U1 = take(R * IN); w.U2 = take(R * IN); w.DA1 = take(R * IN); w.DA2 = take(R * IN); w.DO = take(R * D);
-  w.zero_lo = o;
-  w.lz = take(kMP * D); w.lr = take(kMP * D); w.gmu_acc = take(kMP * D); w.glam_acc = take(kMP * D);
-  w.geta = take(kMP); w.gepsd = take(kMP);
-  w.S = take((K + 1) * IN); w.S2 = take((K + 1) * IN); w.gb2 = take(IN); w.gbeta = take(K); w.geps = take(K);
-  w.counters = take(((D + 63) / 64) + ((IN + 63) / 64));
-  w.sc = take((K + 1) * n * 8);
-  w.zero_hi = o;
-  // the forward's kept activations (behind everything else, outside the cleared range)
-  w.keep = lgcp_uha_nsk_ok(d) && R * (2 * IN + D) + (K + 1) * n * D <= (int64_t(1) << 28);
-  w.kpre1 = take(w.keep ? R * IN : 0); w.kpre2 = take(w.keep ? R * IN : 0);
-  w.ksn = take(w.keep ? R * D : 0); w.kkr = take(w.keep ? (K + 1) * n * D : 0);
-  {
-    const int64_t tIN = (IN + 15) / 16, tD = D / 16, t2D = 2 * D / 16, c1 = kNskChunks * 256, c2 = 2 * c1;
-    w.bops = take(w.keep ? 6 * kNskOperand : 0);        // dO, v: kNskOperand each; da2, da1: 2 kNskOperand each
-    w.wt3p = take(w.keep ? tIN * c1 : 0); w.wt2p = take(w.keep ? tIN * c2 : 0); w.wt1p = take(w.keep ? t2D * c2 : 0);
-    w.kip1 = take(w.keep ? tD * c1 : 0);
-  }
-  w.total = o;
-  return w;
-}
-
-static LgcpKeep lgcp_uha_keep(const cmcd_desc& d, int64_t n, float* gws) {
-  const LgcpUhaGradWs g = lgcp_uha_grad_ws(d, n);
-  if (!g.keep) return LgcpKeep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
-  return LgcpKeep{gws + g.kpre1, gws + g.U1, gws + g.kpre2, gws + g.U2, gws + g.kkr, gws + g.ksn, true};
-}
 
 struct LgcpUhaAdjArgs {
   const float* params;
@@ -3154,44 +2967,29 @@ __global__ __launch_bounds__(256) void lgcp_uha_scal_reduce_kernel(const float* 
   }
 }
 
-static int64_t lgcp_uha_grad_ws_total(const cmcd_desc& d, int64_t n) { return lgcp_uha_grad_ws(d, n).total; }
-
 static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, int64_t n, const float* params,
                          int64_t n_params, const float* tc, float* ws, const float* traj, float* gws, float omega,
                          float* grad, hipStream_t stream) {
-  const int D = d.dim, E = d.emb_dim, IN = 2 * D + E, K = d.nbridges;
+  const LgcpShape s = lgcp_shape(d);
+  const int D = s.D, E = s.E, IN = s.IN, K = s.K, cbD = s.cbD, tD = s.tD, big = s.nch;
   const LgcpUhaWs w = lgcp_uha_ws(d, n, sw.total_floats);
   const LgcpUhaGradWs g = lgcp_uha_grad_ws(d, n);
   if (lgcp_zero(stream, grad, n_params, gws + g.zero_lo, g.zero_hi - g.zero_lo) != CMCD_OK) return CMCD_ERR_HIP;
-  {
-    const dim3 tb(32, 8);
-    hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (2 * D + 31) / 32), tb, 0, stream, params + lay.g_w1,
-                       gws + g.wt1, 2 * D, IN, IN, 2 * D);
-    hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((IN + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w2,
-                       gws + g.wt2, IN, IN, IN, IN);
-    hipLaunchKernelGGL(lgcp_transpose_kernel, dim3((D + 31) / 32, (IN + 31) / 32), tb, 0, stream, params + lay.g_w3,
-                       gws + g.wt3, IN, D, D, IN);
-  }
-  const int gemm_lds = lgcp_gemm_attrs();
-  if (gemm_lds < 0) return CMCD_ERR_HIP;
+  lgcp_transpose_weights(s, lay, params, g, gws, 2 * D, stream);
+  if (!lgcp_gemm_attrs()) return CMCD_ERR_HIP;
   const float* kinv = tc;
-  const float mu0 = 3.8812819069514780f;
-  const dim3 gblock(64 * kGemmWaves);
-  const int cbD = (D + 63) / 64, cbIN = (IN + 63) / 64, cb2D = (2 * D + 63) / 64;
   int* counters = reinterpret_cast<int*>(gws + g.counters);
   const float* bias1 = ws + w.bias1;    // still in the forward workspace (lgcp_uha_forward's prep)
-  const LgcpKeep keep = lgcp_uha_keep(d, n, gws);
+  const LgcpKeep keep = lgcp_keep(g, gws);
   const bool kept = keep.on;
   // r04: with the activations kept, passes of <= 20 particles run the seven products of a bridge on the no-split-K GEMM too
-  const int tIN = (IN + 15) / 16, tD = D / 16, t2D = 2 * D / 16, big = 2 * kNskChunks;
   if (kept) {
-    NskPackArgs pk{};
-    pk.src[0] = gws + g.wt3; pk.dst[0] = gws + g.wt3p; pk.K[0] = D; pk.N[0] = IN; pk.ntile[0] = tIN;
-    pk.src[1] = gws + g.wt2; pk.dst[1] = gws + g.wt2p; pk.K[1] = IN; pk.N[1] = IN; pk.ntile[1] = tIN; pk.nch[1] = big;
-    pk.src[2] = gws + g.wt1; pk.dst[2] = gws + g.wt1p; pk.K[2] = IN; pk.N[2] = 2 * D; pk.ntile[2] = t2D; pk.nch[2] = big;
-    pk.src[3] = tc; pk.dst[3] = gws + g.kip1; pk.K[3] = D; pk.N[3] = D; pk.ntile[3] = tD;
-    const int64_t groups = (int64_t)tIN * big * 64;
-    hipLaunchKernelGGL(lgcp_nsk_pack_kernel, dim3((unsigned)((groups + 255) / 256), 4), dim3(256), 0, stream, pk);
+    NskPack pk;
+    pk.add(gws + g.wt3, gws + g.wt3p, D, IN, s.tIN);
+    pk.add(gws + g.wt2, gws + g.wt2p, IN, IN, s.tIN, big);
+    pk.add(gws + g.wt1, gws + g.wt1p, IN, 2 * D, s.tZW, big);
+    pk.add(tc, gws + g.kip1, D, D, tD);
+    pk.launch(s, stream);
   }
 
   for (int64_t base = 0; base < n; base += kMP) {
@@ -3207,80 +3005,55 @@ static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLay
 
     const bool nskb = kept && M <= 20;
     const bool merged = M > 16;
-    float* const dOp = gws + g.bops, *vp = dOp + kNskOperand, *da2p = vp + kNskOperand, *da1p = da2p + 2 * kNskOperand;
+    const LgcpBackOps ops(s, g, gws);
+    float* const dOp = ops.dO, *vp = ops.v, *da1p = ops.da1;
     // per-pass accumulators (gmu_acc | glam_acc) start from zero (the first pass's by the call's clear above; lz / lr are
     // initialised at point K); the padding of the packed operands must read as zeros
     if (lgcp_zero(stream, gws + g.gmu_acc, base > 0 ? 2 * ((kMP * (int64_t)D + 3) & ~int64_t(3)) : 0,
-                  nskb ? dOp : nullptr, nskb ? 6 * (int64_t)kNskOperand : 0) != CMCD_OK)
+                  nskb ? dOp : nullptr, nskb ? ops.floats : 0) != CMCD_OK)
       return CMCD_ERR_HIP;
     if (nskb) { aa.dOp = dOp; aa.vp = vp; aa.bslab = 1; }
+    auto fresh_args = [&]() { GemmArgs ga{}; ga.M = M; ga.counters = counters; return ga; };
+    auto product = [&](GemmArgs& ga, const GemmSeg& sg, int kdim, int nblk) {    // a one-segment product on the split-K GEMM
+      ga.Kdim = kdim; ga.seg[0] = sg; ga.nblk0 = nblk;
+      lgcp_gemm_launch<EPI_NONE>(nblk, stream, ga);
+    };
+    GemmArgs gp = fresh_args();
     auto kr_at = [&](int e) {   // K^-1 (z_e - mu0)
-      GemmArgs gm{};
-      gm.M = M; gm.Kdim = D; gm.counters = counters;
-      gm.seg[0] = GemmSeg{traj + ((int64_t)e * n + base) * D, kinv, gws + g.kr, D, D, D, D, mu0};
-      gm.nblk0 = cbD;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), gblock, gemm_lds, stream, gm);
+      product(gp, GemmSeg{traj + ((int64_t)e * n + base) * D, kinv, gws + g.kr, D, D, D, D, kLgcpMu0}, D, cbD);
     };
     // back-propagation of one network evaluation (buffer set f, table row `row`, time index i) from the cotangent in dO:
     // leaves d u1 (residual path) and the d a1 W1[:2D]^T slabs
-    auto net_backward = [&](const LgcpUhaFwdSet& f, int64_t row, int i) {
-      if (nskb) {
-        NskArgs na{};
-        na.M = M; na.D = 2 * D; na.IN = IN; na.nch_out = big;
-        // d u2 = d o W3^T (one round of the contraction), d a2 = d u2 sigmoid(pre2)
-        na.seg[0] = NskSeg{dOp, gws + g.wt3p, IN, 0, 0.f}; na.nt0 = tIN;
-        na.bPre = keep.pre2 + row * IN; na.bDuPrev = nullptr; na.bDu = gws + g.du2; na.outA = da2p;
-        na.bDaBig = gws + g.DA2 + row * IN; na.bSumA = gws + g.gb2; na.bSumU = nullptr;
-        if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<3, true>), dim3((unsigned)tIN, 1), gblock, 0, stream, na);
-        else hipLaunchKernelGGL((lgcp_nsk_kernel<3, false>), dim3((unsigned)tIN, 1), gblock, 0, stream, na);
-        // d u1 = d u2 + d a2 W2^T (two rounds), d a1 = d u1 sigmoid(pre1)
-        na.seg[0] = NskSeg{da2p, gws + g.wt2p, IN, 0, 0.f}; na.seg[0].nch = big;
-        na.bPre = keep.pre1 + row * IN; na.bDuPrev = gws + g.du2; na.bDu = gws + g.du1; na.outA = da1p;
-        na.bDaBig = gws + g.DA1 + row * IN; na.bSumA = gws + g.S + (int64_t)i * IN; na.bSumU = gws + g.S2 + (int64_t)i * IN;
-        if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<3, true, 2>), dim3((unsigned)tIN, 1), gblock, 0, stream, na);
-        else hipLaunchKernelGGL((lgcp_nsk_kernel<3, false, 2>), dim3((unsigned)tIN, 1), gblock, 0, stream, na);
-        // d a1 W1[:2D]^T: plain, row-major
+    auto net_backward = [&](const LgcpFwdSet& f, int64_t row, int i) {
+      const LgcpEvalActs acts = kept ? LgcpEvalActs{keep.pre1 + row * IN, keep.u1 + row * IN, keep.pre2 + row * IN, keep.u2 + row * IN}
+                                     : LgcpEvalActs{gws + f.pre1, gws + f.u1, gws + f.pre2, gws + f.u2};
+      GemmArgs gm = fresh_args();
+      lgcp_net_backward(s, g, gws, M, nskb, kept, acts, row, i, gm, stream);
+      if (nskb) {   // d a1 W1[:2D]^T: plain, row-major
         NskArgs nb{};
         nb.M = M; nb.D = 2 * D; nb.IN = IN;
-        nb.seg[0] = NskSeg{da1p, gws + g.wt1p, 2 * D, NSK_OUT, 0.f}; nb.seg[0].nch = big; nb.nt0 = t2D; nb.outN = gws + g.dxf;
-        if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<0, true, 2>), dim3((unsigned)t2D, 1), gblock, 0, stream, nb);
-        else hipLaunchKernelGGL((lgcp_nsk_kernel<0, false, 2>), dim3((unsigned)t2D, 1), gblock, 0, stream, nb);
+        nb.seg[0] = NskSeg{da1p, gws + g.wt1p, 2 * D, NSK_OUT, 0.f}; nb.seg[0].nch = big; nb.nt0 = s.tZW; nb.outN = gws + g.dxf;
+        lgcp_nsk_launch<0, 2>(merged, dim3((unsigned)s.tZW, 1), stream, nb);
         return;
       }
-      GemmArgs gm{};
-      gm.M = M; gm.counters = counters; gm.epi_seg = -1;
-      gm.Kdim = D;
-      gm.seg[0] = GemmSeg{gws + g.dO, gws + g.wt3, gws + g.du2s, IN, D, IN, IN};
-      gm.nblk0 = cbIN;
-      LgcpActbArgs& ab = gm.actb;
-      ab.pre = kept ? keep.pre2 + row * IN : gws + f.pre2; ab.du_prev = nullptr; ab.u_src = kept ? keep.u2 + row * IN : gws + f.u2;
-      ab.du_out = gws + g.du2; ab.da_out = gws + g.da2; ab.da_big = gws + g.DA2; ab.u_big = kept ? nullptr : gws + g.U2;
-      ab.gb = gws + g.gb2; ab.row0 = row; ab.IN = IN; ab.mode = 2;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACTB>, dim3(cbIN, kSplit), gblock, gemm_lds, stream, gm);
-      gm.Kdim = IN;
-      gm.seg[0] = GemmSeg{gws + g.da2, gws + g.wt2, gws + g.ts, IN, IN, IN, IN};
-      ab.pre = kept ? keep.pre1 + row * IN : gws + f.pre1; ab.du_prev = gws + g.du2; ab.u_src = kept ? keep.u1 + row * IN : gws + f.u1;
-      ab.du_out = gws + g.du1; ab.da_out = gws + g.da1; ab.da_big = gws + g.DA1; ab.u_big = kept ? nullptr : gws + g.U1;
-      ab.S = gws + g.S + (int64_t)i * IN; ab.S2 = gws + g.S2 + (int64_t)i * IN; ab.mode = 1;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_ACTB>, dim3(cbIN, kSplit), gblock, gemm_lds, stream, gm);
-      gm.seg[0] = GemmSeg{gws + g.da1, gws + g.wt1, gws + g.dxf, 2 * D, IN, 2 * D, 2 * D};
-      gm.nblk0 = cb2D;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cb2D, kSplit), gblock, gemm_lds, stream, gm);
+      product(gm, GemmSeg{gws + g.da1, gws + g.wt1, gws + g.dxf, 2 * D, IN, 2 * D, 2 * D}, IN, s.cbZW);
     };
     auto hv_product = [&]() {
       if (nskb) {
         NskArgs nb{};
         nb.M = M; nb.D = 2 * D; nb.IN = IN;
         nb.seg[0] = NskSeg{vp, gws + g.kip1, D, NSK_KR, 0.f}; nb.nt0 = tD; nb.krOutN = gws + g.hv;
-        if (merged) hipLaunchKernelGGL((lgcp_nsk_kernel<0, true>), dim3((unsigned)tD, 1), gblock, 0, stream, nb);
-        else hipLaunchKernelGGL((lgcp_nsk_kernel<0, false>), dim3((unsigned)tD, 1), gblock, 0, stream, nb);
+        lgcp_nsk_launch<0>(merged, dim3((unsigned)tD, 1), stream, nb);
         return;
       }
-      GemmArgs gm{};
-      gm.M = M; gm.Kdim = D; gm.counters = counters;
-      gm.seg[0] = GemmSeg{gws + g.v, kinv, gws + g.hv, D, D, D, D};
-      gm.nblk0 = cbD;
-      hipLaunchKernelGGL(lgcp_gemm_kernel<EPI_NONE>, dim3(cbD, kSplit), gblock, gemm_lds, stream, gm);
+      product(gp, GemmSeg{gws + g.v, kinv, gws + g.hv, D, D, D, D}, D, cbD);
+    };
+    // the recompute of one evaluation into buffer set f (no K^-1 rider: kr_at)
+    auto net_at = [&](const LgcpFwdSet& f, int i) {
+      GemmArgs gn = fresh_args();
+      const LgcpNetBufs nb{gws + f.slab1, gws + f.pre1, gws + f.u1, gws + f.slab2, gws + f.pre2, gws + f.u2, gws + f.sn};
+      lgcp_net_splitk(s, lay, params, kinv, gn, gws + f.zin, bias1 + (int64_t)i * IN, params + lay.g_emb + (int64_t)i * E, nb,
+                      nullptr, false, stream);
     };
 
     if (kept) {
@@ -3299,19 +3072,15 @@ static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLay
       }
       hipLaunchKernelGGL(lgcp_uha_adj_point_kernel, dim3(M), dim3(64 * kUhaAdjW), 0, stream, aa);
       hv_product();
-      if (!kept) hipLaunchKernelGGL(lgcp_uha_gather_kernel, dim3((M * D + 255) / 256), dim3(256), 0, stream, aa);
-      const LgcpUhaFwdSet& fa = g.fs[0];
-      const LgcpUhaFwdSet& fb = g.fs[1];
       if (!kept) {
-        lgcp_uha_net(d, lay, params, kinv, M, i, gws + fa.zin, bias1, gws + fa.slab1, gws + fa.pre1, gws + fa.u1, gws + fa.slab2,
-                     gws + fa.pre2, gws + fa.u2, gws + fa.sn, nullptr, nullptr, counters, gemm_lds, stream);
-        lgcp_uha_net(d, lay, params, kinv, M, i, gws + fb.zin, bias1, gws + fb.slab1, gws + fb.pre1, gws + fb.u1, gws + fb.slab2,
-                     gws + fb.pre2, gws + fb.u2, gws + fb.sn, nullptr, nullptr, counters, gemm_lds, stream);
+        hipLaunchKernelGGL(lgcp_uha_gather_kernel, dim3((M * D + 255) / 256), dim3(256), 0, stream, aa);
+        net_at(g.fs[0], i);
+        net_at(g.fs[1], i);
       }
       hipLaunchKernelGGL(lgcp_uha_adj_b_kernel, dim3(M), dim3(64 * kUhaAdjW), 0, stream, aa);
-      net_backward(fb, rowB, i);
+      net_backward(g.fs[1], rowB, i);
       hipLaunchKernelGGL(lgcp_uha_adj_a_kernel, dim3(M), dim3(64 * kUhaAdjW), 0, stream, aa);
-      net_backward(fa, rowA, i);
+      net_backward(g.fs[0], rowA, i);
       hipLaunchKernelGGL(lgcp_uha_adj_fin_kernel, dim3(M), dim3(64 * kUhaAdjW), 0, stream, aa);
       if (!kept) kr_at(i);
     }
@@ -3320,25 +3089,208 @@ static int lgcp_uha_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLay
     hipLaunchKernelGGL(lgcp_uha_adj_point_kernel, dim3(M), dim3(64 * kUhaAdjW), 0, stream, aa);
     hv_product();
     hipLaunchKernelGGL(lgcp_uha_adj_z0_kernel, dim3(M), dim3(256), 0, stream, aa);
-    hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, gws + g.gmu_acc, (int64_t)M, D, D,
-                       grad + lay.vd_mean, 1.0f, 1);
-    hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, gws + g.glam_acc, (int64_t)M, D, D,
-                       grad + lay.vd_logdiag, 1.0f, 1);
+    lgcp_q_grad_sums(s, lay, g, gws, M, grad, stream);
   }
   // ---- deferred parameter contractions over all 2 K n rows
-  const int64_t R = (int64_t)2 * K * n;
-  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, dim3((IN + 127) / 128, (IN + 127) / 128, kTnSplit), dim3(256), 0, stream, gws + g.U1, gws + g.DA2,
-                     grad + lay.g_w2, R, IN, IN, IN, IN, IN);                                   // dW2 = U1^T dA2
-  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, dim3((D + 127) / 128, (IN + 127) / 128, kTnSplit), dim3(256), 0, stream, gws + g.U2, gws + g.DO,
-                     grad + lay.g_w3, R, IN, D, IN, D, D);                                      // dW3 = U2^T dO
-  hipLaunchKernelGGL(lgcp_tn_gemm_kernel, dim3((IN + 127) / 128, (2 * D + 127) / 128, kTnSplit), dim3(256), 0, stream, gws + g.XIN, gws + g.DA1,
-                     grad + lay.g_w1, R, 2 * D, IN, 2 * D, IN, IN);                             // dW1[:2D] = [z; rho]^T dA1
-  hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, gws + g.DO, R, D, D, grad + lay.g_b3, 1.0f, 0);
-  hipLaunchKernelGGL(lgcp_colsum_kernel, dim3((IN + 255) / 256), dim3(256), 0, stream, gws + g.gb2, (int64_t)1, IN, IN, grad + lay.g_b2, 1.0f, 0);
+  lgcp_param_contractions(s, lay, g, gws, gws + g.XIN, (int64_t)2 * K * n, grad, stream);
   hipLaunchKernelGGL(lgcp_uha_scal_reduce_kernel, dim3(K + 1), dim3(256), 0, stream, gws + g.sc, n, K, gws + g.gbeta, gws + g.geps,
                      grad + lay.gamma, grad + lay.g_factor);
   // schedule (cos^2), embedding table, W1[2d:], b1 from the S / S2 / beta / eps tables
   int rc = launch_net_tails(d, 2 * D, CMCD_EPS_COS_SQ, lay, sw, params, gws, g.S, g.S2, g.gbeta, g.geps, IN, nullptr, grad, stream);
+  if (rc != CMCD_OK) return rc;
+  return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
+}
+
+// -------------------------------------------------------------------------------------------------------------
+// The gradient call of the d = 1600 path: the 2nd-order sweep above, or the overdamped reverse sweep (header above
+// lgcp_transpose_kernel) in passes of <= kMP particles.
+// -------------------------------------------------------------------------------------------------------------
+int lgcp_grad(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout& sw, int64_t n, const float* params,
+              int64_t n_params, const float* tc, float* ws, const float* traj, float* gws, float omega,
+              const float* omega_vec, bool bptt, float* grad, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (d.mode == CMCD_MODE_CAIS_UHA_SN) {
+    if (!bptt || omega_vec) return CMCD_ERR_UNSUPPORTED;   // the mode has no stop_gradient variant
+    return lgcp_uha_grad(d, lay, sw, n, params, n_params, tc, ws, traj, gws, omega, grad, stream);
+  }
+  const LgcpShape s = lgcp_shape(d);
+  const int D = s.D, E = s.E, IN = s.IN, K = s.K, cbD = s.cbD, cbIN = s.cbIN, tD = s.tD;
+  const LgcpWs w = lgcp_ws(d, n, sw.total_floats);
+  const LgcpGradWs g = lgcp_grad_ws(d, n);
+  if (lgcp_zero(stream, grad, n_params, gws + g.zero_lo, g.zero_hi - g.zero_lo) != CMCD_OK) return CMCD_ERR_HIP;
+  const int ula = d.mode == CMCD_MODE_ULA ? 1 : (d.mode == CMCD_MODE_ULA_SN ? 2 : 0);
+  const bool net = ula != 1;
+  if (net) lgcp_transpose_weights(s, lay, params, g, gws, IN, stream);
+  if (!lgcp_gemm_attrs()) return CMCD_ERR_HIP;
+  const float* kinv = tc;
+  // r04: with the activations kept, passes of <= 20 particles run the three backward products on the no-split-K GEMM too
+  // (lgcp_nsk_kernel<3, ..>: the backward activation as the consumer, column sums by the tile's one workgroup); the packed
+  // W3^T / W2^T / W1[:D]^T copies are made once per call, K^-1 is the forward's packed copy
+  const bool nskb_ok = g.keep && net;
+  if (nskb_ok) {
+    NskPack pk;
+    pk.add(gws + g.wt3, gws + g.wt3p, D, IN, s.tIN);
+    pk.add(gws + g.wt2, gws + g.wt2p, IN, IN, s.tIN);
+    pk.add(gws + g.wt1, gws + g.wt1p, IN, D, tD, 0, IN);   // first D columns of W1^T
+    pk.launch(s, stream);
+  }
+  // Two streams: the forward recompute of evaluation e-1 (side stream, its own buffer set) overlaps the adjoint /
+  // backward launches of evaluation e (caller's stream).  Every kernel here is launch-latency-bound, so the two
+  // chains run side by side; events order the hand-overs (fork / join, capturable in a graph).
+  LgcpDevSlot* slot = lgcp_dev_slot();
+  if (!slot) return CMCD_ERR_HIP;
+  hipStream_t& side = slot->sweep.side;
+  hipEvent_t* ev_fwd = slot->sweep.ev_fwd;
+  hipEvent_t* ev_bwd = slot->sweep.ev_bwd;
+  hipEvent_t& ev_fork = slot->sweep.ev_fork;
+  if (!side) {
+    if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) return CMCD_ERR_HIP;
+    for (int b = 0; b < 2; ++b) {
+      if (hipEventCreateWithFlags(&ev_fwd[b], hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
+      if (hipEventCreateWithFlags(&ev_bwd[b], hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
+    }
+    if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return CMCD_ERR_HIP;
+  }
+  // r04: the forward kept pre1 / u1 / pre2 / u2 / kr / sn of every evaluation (lgcp_keep): nothing to recompute, one stream
+  const LgcpKeep keep = lgcp_keep(g, gws);
+  const bool kept = keep.on;
+  // bias1 rows are still in the forward workspace (lgcp_forward's prep)
+  for (int64_t base = 0; base < n; base += kMP) {
+    const int M = (int)((n - base) < kMP ? (n - base) : kMP);
+    const bool nskb = nskb_ok && kept && M <= 20;      // (21 .. 32 particles: two workgroups per column tile — the split-K form)
+    const LgcpBackOps ops(s, g, gws);
+    float* const dOp = ops.dO, *vp = ops.v, *da1p = ops.da1;
+    {
+      // lambda / g (lamn | gE) and the accumulators (gmu_acc | glam_acc) start from zero for every pass (the first one's by the
+      // call's clear above); the padding of the packed operands (rows >= M, inputs past the contraction) must read as zeros
+      const int64_t pair = base > 0 ? 2 * ((kMP * (int64_t)D + 3) & ~int64_t(3)) : 0;
+      if (lgcp_zero(stream, gws + g.lamn, pair, gws + g.gmu_acc, pair, nskb ? dOp : nullptr, nskb ? ops.floats : 0) != CMCD_OK)
+        return CMCD_ERR_HIP;
+    }
+    if (!kept && (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess)) return CMCD_ERR_HIP;
+
+    // forward recompute at z_e into buffer set e & 1, on stream st: the forward path's three launches with K^-1 (z_e - mu0)
+    // beside the first (lgcp_net_splitk; the third has no consumer here: the adjoint step sums its slabs)
+    int* side_counters = reinterpret_cast<int*>(gws + g.counters);
+    int* main_counters = side_counters + cbD + cbIN;
+    auto forward_at = [&](int e, hipStream_t st) {
+      const LgcpFwdSet& f = g.fs[e & 1];
+      const int er = ula == 2 ? (e > 0 ? e - 1 : 0) : e;       // MCD_ULA_sn: s(z_e, e - 1)
+      const int ie = er < K ? er : K - 1;
+      const float* xe = traj + ((int64_t)e * n + base) * D;
+      GemmArgs gm{};
+      gm.M = M; gm.counters = side_counters;
+      if (!net) {   // MCD_ULA: the target's K^-1 product is all there is to recompute
+        gm.Kdim = D;
+        gm.seg[0] = GemmSeg{xe, kinv, gws + f.kr, D, D, D, D, kLgcpMu0};
+        gm.nblk0 = cbD;
+        lgcp_gemm_launch<EPI_NONE>(cbD, st, gm);
+        return;
+      }
+      const LgcpNetBufs nb{gws + f.slab1, gws + f.pre1, gws + f.u1, gws + f.slab2, gws + f.pre2, gws + f.u2, gws + f.sn};
+      const LgcpKinvRider rider{0, 0, xe, gws + f.kr};
+      lgcp_net_splitk(s, lay, params, kinv, gm, xe, ws + w.bias1 + (int64_t)er * IN, params + lay.g_emb + (int64_t)ie * E, nb,
+                      &rider, false, st);
+    };
+
+    if (!kept) {
+      forward_at(K, side);
+      if (hipEventRecord(ev_fwd[K & 1], side) != hipSuccess) return CMCD_ERR_HIP;
+    }
+    for (int e = K; e >= 0; --e) {
+      if (!kept) {
+        if (e > 0) {  // next evaluation's recompute: its buffer set was last read by the backward pass of e+1
+          if (e + 1 <= K && hipStreamWaitEvent(side, ev_bwd[(e - 1) & 1], 0) != hipSuccess) return CMCD_ERR_HIP;
+          forward_at(e - 1, side);
+          if (hipEventRecord(ev_fwd[(e - 1) & 1], side) != hipSuccess) return CMCD_ERR_HIP;
+        }
+        if (hipStreamWaitEvent(stream, ev_fwd[e & 1], 0) != hipSuccess) return CMCD_ERR_HIP;
+      }
+      const LgcpFwdSet& f = g.fs[e & 1];
+      const int64_t row0 = (int64_t)e * n + base;
+      // this evaluation's activations: the recompute's buffer set, or its rows of the tables the forward kept
+      const float* e_kr = kept ? keep.kr + row0 * D : gws + f.kr;
+      const float* e_sn = kept ? keep.sn + row0 * D : gws + f.sn;
+      const LgcpEvalActs acts = kept ? LgcpEvalActs{keep.pre1 + row0 * IN, keep.u1 + row0 * IN, keep.pre2 + row0 * IN, keep.u2 + row0 * IN}
+                                     : LgcpEvalActs{gws + f.pre1, gws + f.u1, gws + f.pre2, gws + f.u2};
+      GemmArgs gm{};
+      gm.M = M;
+      // ---- adjoint step (of evaluation ev: its kr / sn are the recompute's buffers, or rows of the kept tables)
+      auto adj_args = [&](int ev) {
+        const int64_t rv = (int64_t)ev * n + base;
+        LgcpAdjArgs aa{};
+        aa.params = params; aa.tc = tc; aa.sched = ws + sw.sched; aa.traj = traj;
+        aa.kr = kept ? keep.kr + rv * D : e_kr; aa.sn = kept ? keep.sn + rv * D : e_sn;
+        aa.nslab = kept ? 1 : kSplit;
+        aa.b3 = params + lay.g_b3; aa.factor = params + lay.g_factor; aa.lamn = gws + g.lamn; aa.gE = gws + g.gE;
+        aa.gprev = gws + g.gprev; aa.dO = gws + g.dO; aa.v = gws + g.v; aa.lam_part = gws + g.lam_part;
+        aa.gmu_acc = gws + g.gmu_acc; aa.glam_acc = gws + g.glam_acc; aa.part = gws + g.adjpart;
+        aa.DObig = gws + g.DO; aa.lay = lay; aa.n = n; aa.base = base;
+        aa.M = M; aa.D = D; aa.K = K; aa.e = ev; aa.grad_clipping = d.grad_clipping; aa.omega = omega;
+        aa.ula = ula; aa.omega_vec = omega_vec; aa.bptt = bptt ? 1 : 0; aa.var_mode = d.mode == CMCD_MODE_CAIS_VAR_SN ? 1 : 0;
+        if (nskb) { aa.dOp = dOp; aa.vp = vp; }
+        return aa;
+      };
+      // kept + reparameterised: the step of evaluation e was fused behind lambda_{e+1} by the previous iteration
+      const bool fuse = kept && bptt;
+      if (!(fuse && e < K)) hipLaunchKernelGGL(lgcp_adj_step_kernel, dim3(cbD, M), dim3(64), 0, stream, adj_args(e));
+      // lambda_e from the products left in hv / dxf (nslab slabs each), with the adjoint step of e - 1 behind it when fused
+      auto lam_step = [&](int nslab) {
+        LgcpLamArgs la{};
+        la.params = params; la.tc = tc; la.traj = traj; la.dxf = net ? gws + g.dxf : nullptr; la.hv = gws + g.hv;
+        la.du1 = net ? gws + g.du1 : nullptr;
+        la.v = gws + g.v; la.lam_part = gws + g.lam_part; la.gprev = gws + g.gprev; la.lamn = gws + g.lamn;
+        la.gE = gws + g.gE; la.gmu_acc = gws + g.gmu_acc; la.glam_acc = gws + g.glam_acc; la.lay = lay; la.n = n;
+        la.base = base; la.M = M; la.D = D; la.IN = IN; la.e = e; la.omega = omega; la.no_net = net ? 0 : 1; la.nslab = nslab;
+        if (fuse && e > 0) hipLaunchKernelGGL(lgcp_lam_adj_kernel, dim3(cbD, M), dim3(64), 0, stream, la, adj_args(e - 1));
+        else hipLaunchKernelGGL(lgcp_lam_finish_kernel, dim3((M * D + 255) / 256), dim3(256), 0, stream, la);
+      };
+      if (!net) {   // MCD_ULA: lambda_e = lam_part - H_p v, one GEMM
+        gm.Kdim = D; gm.Kdim1 = 0;
+        gm.seg[0] = GemmSeg{gws + g.v, kinv, gws + g.hv, D, D, D, D};
+        gm.nblk0 = cbD;
+        lgcp_gemm_launch<EPI_NONE>(cbD, stream, gm);
+        lam_step(kSplit);
+        if (!kept && hipEventRecord(ev_bwd[e & 1], stream) != hipSuccess) return CMCD_ERR_HIP;
+        continue;
+      }
+      // ---- net backward down to d a1 (the time index the network saw at this evaluation: e, or e - 1 in MCD_ULA_sn)
+      gm.counters = main_counters;
+      lgcp_net_backward(s, g, gws, M, nskb, kept, acts, row0, ula == 2 ? (e > 0 ? e - 1 : 0) : e, gm, stream);
+      if (!bptt) {   // z detached: no lambda, no Hessian product; this evaluation's buffers are free after actb
+        if (!kept && hipEventRecord(ev_bwd[e & 1], stream) != hipSuccess) return CMCD_ERR_HIP;
+        continue;
+      }
+      // ---- d a1 W1[:D]^T | v K^-1: two independent products, one launch
+      if (nskb) {   // plain products, row-major
+        NskArgs nb{};
+        nb.M = M; nb.D = D; nb.IN = IN;
+        nb.seg[0] = NskSeg{da1p, gws + g.wt1p, D, NSK_OUT, 0.f}; nb.nt0 = tD; nb.outN = gws + g.dxf;
+        nb.seg[1] = NskSeg{vp, ws + w.kip, D, NSK_KR, 0.f}; nb.krOutN = gws + g.hv;
+        lgcp_nsk_launch<0>(M > 16, dim3((unsigned)(2 * tD), 1), stream, nb);
+        lam_step(1);
+        continue;
+      }
+      gm.Kdim = IN; gm.Kdim1 = D;
+      gm.seg[0] = GemmSeg{gws + g.da1, gws + g.wt1, gws + g.dxf, D, IN, IN, D};
+      gm.seg[1] = GemmSeg{gws + g.v, kinv, gws + g.hv, D, D, D, D};
+      gm.nblk0 = cbD;
+      lgcp_gemm_launch<EPI_NONE>(2 * cbD, stream, gm);
+      lam_step(kSplit);
+      if (!kept && hipEventRecord(ev_bwd[e & 1], stream) != hipSuccess) return CMCD_ERR_HIP;
+    }
+    lgcp_q_grad_sums(s, lay, g, gws, M, grad, stream);
+  }
+  // ---- deferred parameter contractions over all (K+1) n rows
+  if (net) lgcp_param_contractions(s, lay, g, gws, traj, (int64_t)(K + 1) * n, grad, stream);
+  {
+    const int slots = (int)(n * cbD);
+    LgcpAdjRedArgs ra{gws + g.adjpart, ws + sw.sched, gws + g.gbeta, gws + g.geps, gws + g.gfac, K, slots};
+    hipLaunchKernelGGL(lgcp_adj_reduce_kernel, dim3(K + 1), dim3(64), 0, stream, ra);
+  }
+  if (net)
+    hipLaunchKernelGGL(lgcp_colsum_kernel, dim3(1), dim3(256), 0, stream, gws + g.gfac, (int64_t)(K + 1), 1, 1, grad + lay.g_factor, 1.0f, 0);
+  int rc = launch_geffner_tails(d, lay, sw, params, gws, g.S, g.S2, g.gbeta, g.geps, IN, grad, stream_, net);
   if (rc != CMCD_OK) return rc;
   return hipGetLastError() == hipSuccess ? CMCD_OK : CMCD_ERR_HIP;
 }

@@ -631,23 +631,22 @@ static WideWs wide_ws(const cmcd_desc& d, int64_t n, int64_t base) {
   w.KpD = w.ldx; w.KpIN = w.ldu;
   w.NpD = (int)rup(D, kWCols); w.NpIN = (int)rup(IN, kWCols);
   w.ctD = w.NpD / kWCols; w.ctIN = w.NpIN / kWCols;
-  int64_t o = base;
-  auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 3) & ~int64_t(3); return r; };
-  w.bias1 = take((K + 1) * IN);
-  w.w1p = take((int64_t)w.KpD * w.NpIN);
-  w.w2p = take((int64_t)w.KpIN * w.NpIN);
-  w.w3p = take((int64_t)w.KpIN * w.NpD);
-  w.kip = take((int64_t)w.KpD * w.NpD);
-  w.b2 = take(w.NpIN); w.b3 = take(w.NpD); w.mean = take(w.NpD); w.sd = take(w.NpD); w.counts = take(w.NpD);
-  w.x = take((int64_t)w.Mp * w.ldx); w.xp = take((int64_t)w.Mp * w.ldx); w.xn = take((int64_t)w.Mp * w.ldx);
-  w.kr = take((int64_t)w.Mp * w.ldx);
-  w.u1 = take((int64_t)w.Mp * w.ldu); w.u2 = take((int64_t)w.Mp * w.ldu);
-  w.w0 = take(w.Mp);
-  w.gktab = take(2 * K * n);
-  w.slots = take((int64_t)3 * w.ctD * w.Mp);
-  o = (o + 1) & ~int64_t(1);
-  w.partials = take(n * CMCD_NSTATS * 2);
-  w.total = o;
+  WsBump b{base};
+  w.bias1 = b.take((K + 1) * IN);
+  w.w1p = b.take((int64_t)w.KpD * w.NpIN);
+  w.w2p = b.take((int64_t)w.KpIN * w.NpIN);
+  w.w3p = b.take((int64_t)w.KpIN * w.NpD);
+  w.kip = b.take((int64_t)w.KpD * w.NpD);
+  w.b2 = b.take(w.NpIN); w.b3 = b.take(w.NpD); w.mean = b.take(w.NpD); w.sd = b.take(w.NpD); w.counts = b.take(w.NpD);
+  w.x = b.take((int64_t)w.Mp * w.ldx); w.xp = b.take((int64_t)w.Mp * w.ldx); w.xn = b.take((int64_t)w.Mp * w.ldx);
+  w.kr = b.take((int64_t)w.Mp * w.ldx);
+  w.u1 = b.take((int64_t)w.Mp * w.ldu); w.u2 = b.take((int64_t)w.Mp * w.ldu);
+  w.w0 = b.take(w.Mp);
+  w.gktab = b.take(2 * K * n);
+  w.slots = b.take((int64_t)3 * w.ctD * w.Mp);
+  b.align_double();
+  w.partials = b.take(n * CMCD_NSTATS * 2);
+  w.total = b.o;
   return w;
 }
 
@@ -735,7 +734,6 @@ int lgcp_wide_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout
   WideInitArgs ia{seeds, params, ws + w.x, ws + w.w0, reinterpret_cast<uint32_t*>(ws + w.gktab), lay, n, D, w.ldx, K};
   hipLaunchKernelGGL(lgcp_wide_init_kernel, dim3((unsigned)n), dim3(256), 0, stream, ia);
 
-  const float mu0 = 3.8812819069514780f;      // log(126) - 0.5 * 1.91 (model_handler.py:346); the state update reads tc's copy
   WideArgs g{};
   g.M = (int)n; g.RT = w.Mp / kWRows;
   g.D = D; g.IN = IN; g.ldx = w.ldx; g.ldu = w.ldu;
@@ -769,7 +767,7 @@ int lgcp_wide_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout
     // after this evaluation: prev <- cur, cur <- next (the old prev is the buffer the next evaluation writes)
     xbuf[0] = st.xn; xbuf[2] = xbuf[1]; xbuf[1] = xc;
     if (ula == 1) {    // MCD_ULA: one launch per evaluation, (x - mu0) K^-1 with the state update as its consumer
-      g.seg[0] = WideSeg{xc, ws + w.kip, w.ldx, w.NpD, w.KpD, WEPI_STEP_NONET, mu0, D};
+      g.seg[0] = WideSeg{xc, ws + w.kip, w.ldx, w.NpD, w.KpD, WEPI_STEP_NONET, kLgcpMu0, D};
       g.nct0 = w.ctD;
       launch(w.ctD, 3);
       continue;
@@ -784,7 +782,7 @@ int lgcp_wide_forward(const cmcd_desc& d, const cmcd_layout& lay, const WsLayout
     launch(w.ctIN, 0);
     // B: the second layer and, beside it, the K^-1 product (needs only the state; consumed by C)
     g.seg[0] = WideSeg{ws + w.u1, ws + w.w2p, w.ldu, w.NpIN, w.KpIN, WEPI_ACT2, 0.f, IN};
-    g.seg[1] = WideSeg{xc, ws + w.kip, w.ldx, w.NpD, w.KpD, WEPI_KR, mu0, D};
+    g.seg[1] = WideSeg{xc, ws + w.kip, w.ldx, w.NpD, w.KpD, WEPI_KR, kLgcpMu0, D};
     g.nct0 = w.ctIN;
     g.bias = ws + w.b2; g.u_prev = ws + w.u1; g.u_out = ws + w.u2; g.kr_out = ws + w.kr;
     launch(w.ctIN + w.ctD, 1);

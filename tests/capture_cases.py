@@ -314,7 +314,7 @@ class LgcpWideCase(Builder):
 
 
 # ------------------------------------------------------------------------------------------ the launch rules at d = 1600
-# Restated from cmcd_lgcp.hip (lgcp_lanes, lgcp_nsk_ok, lgcp_grad_ws / lgcp_keep, lgcp_uha_nsk_ok, lgcp_uha_grad_ws,
+# Restated from cmcd_lgcp.hip (lgcp_lanes, lgcp_shape's nsk rule at both widths, lgcp_grad_ws / lgcp_keep, lgcp_uha_grad_ws,
 # lgcp_use_wide) and cmcd_common.h, on lc.passes_of: what a case reaches, so that a changed rule fails an assertion instead of
 # silently un-testing a site.
 LGCP_LANES = 4                  # kLanes
@@ -328,7 +328,7 @@ def lgcp_facts(case, forward_only=False):
       passes        lc.passes_of(n);
       lanes         passes the forward runs side by side, lane 0 on the caller's stream and the others on side streams
                     (lgcp_lanes); the 2nd-order sequence walks its passes in turn on the caller's stream: 1;
-      kept          the forward keeps every evaluation's activations for the reverse sweep (lgcp_keep / lgcp_uha_keep); False:
+      kept          the forward keeps every evaluation's activations for the reverse sweep (lgcp_keep); False:
                     the sweep recomputes them — overdamped: on a side stream; None for a forward-only call;
       side_streams  the call forks work onto another stream, i.e. its captured graph has parallel branches;
       wide          a forward-only call of >= 225 particles takes the wide-batch path (one stream)."""

@@ -26,7 +26,7 @@ M <= 16 rows takes the no-split-K GEMM, 17 .. 20 its merged instance (rows 16 ..
   w1612-21  21   2  21            emb_dim = 12: tIN = 101 with a ragged last tile, IN % 128 != 0; split-K family
   w1612-37  37   2  32 + 5        the same width on both GEMM families
   w1604     20   2  20            emb_dim = 4
-  w1670-5   5    2  5             emb_dim = 70: IN > 1664, lgcp_nsk_ok false, recompute by the library's own choice
+  w1670-5   5    2  5             emb_dim = 70: IN > 1664, LgcpShape::nsk false, recompute by the library's own choice
   w1670-37  37   2  32 + 5
   cos       20   3  20            eps_schedule = "cos_sq", init_eps = 1e-3
   lin       20   3  20            eps_schedule = "linear"
@@ -41,9 +41,9 @@ M <= 16 rows takes the no-split-K GEMM, 17 .. 20 its merged instance (rows 16 ..
                                   21, 33 at K = 2 and n = 52 at K = 1: the no-split-K forward, the sweep on kept activations
 
 The 2nd-order mode's other launch sequence (`uha_route`): the split-K forward (lgcp_uha_forward below its early return:
-lgcp_uha_init_kernel unpacked, lgcp_gemm_kernel<EPI_NONE> on the 2 D-pitch state, lgcp_uha_net with slabs and arrival counters,
+lgcp_uha_init_kernel unpacked, lgcp_gemm_kernel<EPI_NONE> on the 2 D-pitch state, lgcp_net_splitk with slabs and arrival counters,
 lgcp_uha_mid_kernel<4> / lgcp_uha_close_kernel<4> summing kSplit slabs) and the recompute sweep (the `!kept` branch of
-lgcp_uha_grad: kr_at, lgcp_uha_gather_kernel, two lgcp_uha_net per bridge into the two LgcpUhaFwdSets, the EPI_ACTB products
+lgcp_uha_grad: kr_at, lgcp_uha_gather_kernel, two lgcp_net_splitk per bridge into the two LgcpFwdSets, the EPI_ACTB products
 writing U1 / U2, the kSplit sums of the lgcp_uha_adj_* kernels), pinned by form 3 or taken by the library itself at IN > 3328.
 
   id            n    K  form  over         what it reaches
@@ -175,13 +175,13 @@ def gemm_of(m):
     return "nsk" if m <= 16 else "merged" if m <= 20 else "split-k"
 
 
-# ---- the 2nd-order mode's launch rules, restated from cmcd_lgcp.hip (lgcp_uha_nsk_ok, lgcp_uha_grad_ws)
+# ---- the 2nd-order mode's launch rules, restated from cmcd_lgcp.hip (lgcp_shape's nsk rule, lgcp_uha_grad_ws)
 NSK_CHUNKS = 104                # kNskChunks: 16-deep chunks of a packed operand
 KEEP_FLOATS = 1 << 28           # cap of the tables the forward keeps for the sweep
 
 
 def uha_nsk_ok(dim, emb_dim, form):
-    """lgcp_uha_nsk_ok: the no-split-K forward serves d <= 1664 in whole 16-column tiles and widths up to two rounds of chunks."""
+    """lgcp_shape's nsk rule at width 2 d: the no-split-K forward serves d <= 1664 in whole 16-column tiles and widths up to two rounds of chunks."""
     return form != 3 and dim % 16 == 0 and dim <= 16 * NSK_CHUNKS and 2 * dim + emb_dim <= 32 * NSK_CHUNKS
 
 
